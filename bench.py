@@ -8,10 +8,17 @@ per clip) stay in HBM.  One "step" = `passes_per_step` back-to-back passes over 
 so a step is sized (from two calibration passes, before the warm-up) such that the K timed steps last at least
 --min-seconds (default 3 s) -- long enough for clocks and power to settle and for an outside sampler to see the
 GPU busy.  `value` is audio-seconds per second over the whole timed region either way; `ms_per_pass`,
-`passes_per_step`, the first and last quartile of the step times, the shader clock read inside a probe kernel
-and the board power sampled during the timed region are reported beside it.
+`passes_per_step` and the first and last quartile of the step times are reported beside it.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.
+`--dump-outputs DIR` writes what the last timed step computed (DIR/packed_subfingerprints.npy: the eight 32-bit
+words of every packed sub-fingerprint, exact in float64, with DIR/clip_index.npy; a seeded sample of whole clips
+if the batch exceeds 64 MB) so that two builds can be compared output for output on the same seeded inputs.
+`--full` adds everything else: the shader clock read inside a probe kernel and the board power sampled during the
+timed region, the per-kernel stage times and roofline of the headline, its parity against the CPU oracle, the CPU
+baselines and the side legs below (other processing configurations, compare, sliding compare, files).
 
 N > 1 without a launcher: this process -- before it touches torch.cuda or HIP -- starts N fresh ranks
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`),
@@ -20,11 +27,11 @@ relays rank 0's single JSON line and exits non-zero if any rank failed.  Under a
 
 With N > 1 every rank fingerprints its own 100 000 clips (weak scaling, no data-path collective: clips are
 independent); the timed region is bracketed by barrier + synchronize and the slowest rank's time is used.
-The compare leg (a side measurement) is BASELINE configs[2] at N = 1 (1 query vs 1 M fingerprints) and
+The compare leg (a side measurement, --full) is BASELINE configs[2] at N = 1 (1 query vs 1 M fingerprints) and
 configs[3] at N > 1: 10 M fingerprints in contiguous index shards of 10 M / N per rank, the planted match in
 a non-zero rank, one RCCL MAX all-reduce of the 8-byte (score, ~index) key, timed separately from the scan.
 
-`--backend gloo --clips 0` is the CPU dry run of the launcher, the rendezvous, the shard arithmetic and the
+`--full --backend gloo --clips 0` is the CPU dry run of the launcher, the rendezvous, the shard arithmetic and the
 key reduction (no kernels run, `value` is null); tests/test_bench_launcher.py drives it at world size 2.
 """
 from __future__ import annotations
@@ -173,7 +180,30 @@ def parse_args(argv=None):
                          "the library's communicator, barrier, destroy -- on a single GPU")
     ap.add_argument("--no-sliding", action="store_true", help="skip the ragged-corpus (sliding compare) leg")
     ap.add_argument("--no-files", action="store_true", help="skip the file leg (BASELINE configs[0] on the bird fixtures)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: telemetry, stage times and roofline, oracle parity, CPU baselines and the side "
+                         "legs (the --corpus / --corpus-hbm / --no-* options apply to this mode only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the packed sub-fingerprints of the last timed step to DIR as .npy (float64)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, packed, np) -> None:
+    """--dump-outputs: what the last timed step left in `packed` (clips x sub-fingerprints x 32 bytes), as the eight
+    little-endian 32-bit words of each packed sub-fingerprint in float64 (exact), and the clip each row belongs to.
+    A batch larger than DUMP_BUDGET_BYTES is written as a seeded sample of whole clips, in clip order."""
+    n, per = int(packed.shape[0]), int(packed.shape[1])
+    row_bytes = per * (packed.shape[2] // 4) * 8 + 8
+    idx = np.arange(n)
+    if n * row_bytes > DUMP_BUDGET_BYTES:
+        idx = np.sort(np.random.default_rng(SEED).choice(n, DUMP_BUDGET_BYTES // row_bytes, replace=False))
+    host = packed.cpu().numpy()[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "packed_subfingerprints.npy"), host.view("<u4").astype(np.float64))
+    np.save(os.path.join(out_dir, "clip_index.npy"), idx.astype(np.float64))
 
 
 def quiet_stdout(fn):
@@ -755,10 +785,11 @@ def run_rank(args) -> int:
             step()
         barrier()
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-        tele = Telemetry(lb, torch) if rank == 0 else None
+        tele = Telemetry(lb, torch) if rank == 0 and args.full else None
         if tele:
             tele.start()
-        det.set_stage_timing(True)      # HIP events around each kernel, on the launch stream, inside the timed region
+        if args.full:
+            det.set_stage_timing(True)  # HIP events around each kernel, on the launch stream, inside the timed region
         t0 = time.perf_counter()
         for s in range(args.steps):
             ev[s][0].record()
@@ -774,7 +805,9 @@ def run_rank(args) -> int:
             elapsed = float(t.item())
         ms_per_step = elapsed * 1e3 / args.steps
         value = n_gpus * n_clips * passes * args.steps / elapsed       # audio-seconds per second, whole job
-        if dist_on:
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, packed, np)
+        if dist_on and args.full:
             # the OPTIONAL gather of sharded fingerprinting (160 B per clip; the path itself needs no collective), untimed:
             # every rank's first clips in rank order, checked against what this rank holds
             head = min(16, n_clips)
@@ -782,12 +815,6 @@ def run_rank(args) -> int:
             assert allp.shape[0] == head * world and torch.equal(allp[rank * head:(rank + 1) * head], packed[:head])
             result["gather_packed"] = {"clips_per_rank": head, "gathered": int(allp.shape[0])}
         step_ms = [a.elapsed_time(b) for a, b in ev]
-        kern_avg_ms = sum(step_ms) / len(step_ms) / passes              # one pass, HIP events on the launch stream
-        stage1_ms, stage2_ms, launches = det.stage_times()      # summed over the timed passes
-        det.set_stage_timing(False)
-        launches_per_pass = launches // (args.steps * passes)
-        rows_ms = stage1_ms / launches                          # dominant kernel: average launch duration
-        clips_per_launch = n_clips / launches_per_pass
         qn = max(1, len(step_ms) // 4)
         sustained = {
             "timed_region_s": round(elapsed, 3), "passes_per_step": passes, "passes_timed": passes * args.steps,
@@ -798,12 +825,7 @@ def run_rank(args) -> int:
         }
         if tele:
             sustained.update(tele.summary())
-
         if rank == 0:
-            alg_bytes = algorithmic_bytes_per_clip(SAMPLES, WINDOW, STRIDE)
-            canon_flops = per * 128 * 2.5 * WINDOW * 10            # 2.5 W log2 W per window (SURVEY 8d)
-            traffic, traffic_src = profile_traffic(args.variant, clips_per_launch)
-            achieved = alg_bytes * clips_per_launch / (rows_ms * 1e-3) / 1e9
             result.update({
                 "value": round(value, 1), "ms_per_step": round(ms_per_step, 4),
                 "ms_per_pass": round(ms_per_step / passes, 4), "passes_per_step": passes, "sustained": sustained,
@@ -815,26 +837,39 @@ def run_rank(args) -> int:
                     "parallelism": f"clips sharded x{n_gpus}, no collective",
                 },
                 "per_gpu_value": round(value / n_gpus, 1),
-                "roofline": {
-                    # 93 canonical flop per algorithmic byte against a ridge of ~20 -- the kernel is
-                    # bound by FP32 VALU issue and LDS latency, not by HBM.  achieved / peak / frac are the HBM-side
-                    # figures the contract asks for (algorithmic bytes / launch duration); the VALU figures follow.
-                    "bound": "valu",
-                    "kernel": "stage 1, windows -> frame rows (frame_rows_pruned_kernel when the pruned FFT applies, "
-                              "else fft_bands_kernel): dominant kernel of the pass",
-                    "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 5),
-                    "traffic": traffic, "traffic_source": traffic_src,
-                    "algorithmic_bytes_per_clip": alg_bytes, "clips_per_launch": clips_per_launch,
-                    "launches_per_pass": launches_per_pass, "kernel_ms_avg": round(rows_ms, 4),
-                    "stage2_kernel_ms_avg": round(stage2_ms / launches, 4), "pass_ms_avg": round(kern_avg_ms, 4),
-                    "fp32_canonical_tflops": round(canon_flops * clips_per_launch / (rows_ms * 1e-3) / 1e12, 3),
-                    "fp32_peak_tflops": FP32_PEAK_TFLOPS,
-                    "fp32_frac_canonical": round(canon_flops * clips_per_launch / (rows_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 4),
-                    **executed_fields(RATE, WINDOW, canon_flops * clips_per_launch / (rows_ms * 1e-3) / 1e12, args.variant),
-                    "whole_pass_achieved_GBps": round(alg_bytes * n_clips / (kern_avg_ms * 1e-3) / 1e9, 2),
-                },
             })
+
+        if args.full:
+            kern_avg_ms = sum(step_ms) / len(step_ms) / passes              # one pass, HIP events on the launch stream
+            stage1_ms, stage2_ms, launches = det.stage_times()      # summed over the timed passes
+            det.set_stage_timing(False)
+            launches_per_pass = launches // (args.steps * passes)
+            rows_ms = stage1_ms / launches                          # dominant kernel: average launch duration
+            clips_per_launch = n_clips / launches_per_pass
+        if rank == 0 and args.full:
+            alg_bytes = algorithmic_bytes_per_clip(SAMPLES, WINDOW, STRIDE)
+            canon_flops = per * 128 * 2.5 * WINDOW * 10            # 2.5 W log2 W per window (SURVEY 8d)
+            traffic, traffic_src = profile_traffic(args.variant, clips_per_launch)
+            achieved = alg_bytes * clips_per_launch / (rows_ms * 1e-3) / 1e9
+            result["roofline"] = {
+                # 93 canonical flop per algorithmic byte against a ridge of ~20 -- the kernel is
+                # bound by FP32 VALU issue and LDS latency, not by HBM.  achieved / peak / frac are the HBM-side
+                # figures the contract asks for (algorithmic bytes / launch duration); the VALU figures follow.
+                "bound": "valu",
+                "kernel": "stage 1, windows -> frame rows (frame_rows_pruned_kernel when the pruned FFT applies, "
+                          "else fft_bands_kernel): dominant kernel of the pass",
+                "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 5),
+                "traffic": traffic, "traffic_source": traffic_src,
+                "algorithmic_bytes_per_clip": alg_bytes, "clips_per_launch": clips_per_launch,
+                "launches_per_pass": launches_per_pass, "kernel_ms_avg": round(rows_ms, 4),
+                "stage2_kernel_ms_avg": round(stage2_ms / launches, 4), "pass_ms_avg": round(kern_avg_ms, 4),
+                "fp32_canonical_tflops": round(canon_flops * clips_per_launch / (rows_ms * 1e-3) / 1e12, 3),
+                "fp32_peak_tflops": FP32_PEAK_TFLOPS,
+                "fp32_frac_canonical": round(canon_flops * clips_per_launch / (rows_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 4),
+                **executed_fields(RATE, WINDOW, canon_flops * clips_per_launch / (rows_ms * 1e-3) / 1e12, args.variant),
+                "whole_pass_achieved_GBps": round(alg_bytes * n_clips / (kern_avg_ms * 1e-3) / 1e9, 2),
+            }
             # parity of the bench's own data against the oracle (untimed, the oracle is the checker)
             from oracle import oracle as O
             cfg = O.Config(RATE, WINDOW, STRIDE)
@@ -868,7 +903,7 @@ def run_rank(args) -> int:
                 }
         del clips, packed
         # ---- the other processing configurations of BASELINE.json (side measurements, one GPU) ---------------
-        if world == 1 and not args.no_other_configs:
+        if world == 1 and args.full and not args.no_other_configs:
             from oracle import oracle as O
             others = {}
             for key, rate, window, seconds, n_o, stereo in (("configs0_settings", 5512, 2048, 9, 20_000, False),
@@ -920,7 +955,7 @@ def run_rank(args) -> int:
 
     # =========================== compare leg (side measurement) ===========================================
     total = args.corpus if args.corpus >= 0 else (1_000_000 if world == 1 else 10_000_000)
-    if total > 0:
+    if args.full and total > 0:
         per = 5
         begin, end = sharded.shard_range(total, rank, world)
         planted = (PLANTED_1GPU if world == 1 else PLANTED_SHARDED) % total
@@ -1150,11 +1185,11 @@ def run_rank(args) -> int:
                 big.dispose()
 
     # =========================== sliding compare on a ragged corpus (side measurement) ====================
-    if world == 1 and not dry and not args.no_sliding and args.corpus != 0:
+    if world == 1 and not dry and args.full and not args.no_sliding and args.corpus != 0:
         result["compare_sliding"] = sliding_leg(args, torch, np)
 
     # =========================== the reference's own workload: files (BASELINE configs[0]) ================
-    if world == 1 and not dry and not args.no_files:
+    if world == 1 and not dry and args.full and not args.no_files:
         files = files_leg(args, torch, np)
         if files:
             result["configs0_files"] = files

@@ -1,4 +1,4 @@
-"""bench.py's own multi-rank launcher, driven on CPU: `python bench.py --gpus 2 --backend gloo --clips 0`
+"""bench.py's own multi-rank launcher, driven on CPU: `python bench.py --gpus 2 --full --backend gloo --clips 0`
 must start two fresh ranks through torch.distributed.run, rendezvous on 127.0.0.1, reduce the per-shard
 (score, ~index) keys with MAX and print ONE JSON line that reports two ranks and the planted index."""
 import json
@@ -17,7 +17,7 @@ def _run(*extra, env_extra=None):
 
 
 def test_gpus_flag_launches_that_many_ranks():
-    out = _run("--gpus", "2", "--backend", "gloo", "--clips", "0", "--corpus", "2000")
+    out = _run("--gpus", "2", "--full", "--backend", "gloo", "--clips", "0", "--corpus", "2000")
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -46,7 +46,7 @@ def test_world_size_eight_with_planted_index_off_rank_zero():
     """BASELINE configs[3]'s shard arithmetic at the size the driver will run it: 10 M entries over EIGHT ranks
     (1.25 M each), the planted match at 7 777 777 -- rank 6, never rank 0 -- found through the MAX reduction of the
     (score, ~index) keys."""
-    out = _run("--gpus", "8", "--backend", "gloo", "--clips", "0")
+    out = _run("--gpus", "8", "--full", "--backend", "gloo", "--clips", "0")
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert r["n_gpus"] == 8 and r["rccl_ranks"] == 8 and sorted(d["rank"] for d in r["devices"]) == list(range(8))
@@ -59,7 +59,7 @@ def test_world_size_eight_with_planted_index_off_rank_zero():
 def test_world_size_eight_with_empty_shards():
     """Fewer entries than ranks: three ranks own one entry, five own none and must still join the reduction with
     the neutral key; the planted entry (index 7 777 777 % 3 = 1) wins."""
-    out = _run("--gpus", "8", "--backend", "gloo", "--clips", "0", "--corpus", "3")
+    out = _run("--gpus", "8", "--full", "--backend", "gloo", "--clips", "0", "--corpus", "3")
     assert out.returncode == 0, out.stderr[-2000:]
     c = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])["compare"]
     assert sorted(c["entries_per_rank"]) == [0] * 5 + [1] * 3 and sum(c["entries_per_rank"]) == 3
@@ -69,7 +69,7 @@ def test_world_size_eight_with_empty_shards():
 def test_force_dist_takes_the_collective_branches_at_one_rank():
     """`--force-dist` at world size 1 (gloo here; tests/test_gpu_ragged.py::test_bench_collective_paths_on_nccl_at_one_rank runs the same switch on the nccl backend):
     the process group exists, the reduction goes through torch.distributed and the line says so."""
-    out = _run("--gpus", "1", "--force-dist", "--backend", "gloo", "--clips", "0", "--corpus", "2000")
+    out = _run("--gpus", "1", "--full", "--force-dist", "--backend", "gloo", "--clips", "0", "--corpus", "2000")
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert r["n_gpus"] == 1 and r["rccl_ranks"] == 1 and "force_dist" in r and [d["rank"] for d in r["devices"]] == [0]
@@ -108,3 +108,36 @@ def test_self_check_rejects_impossible_figures():
     v = b.self_check(bad)
     assert len(v) == 4 and any("179.2" in m for m in v) and any("achieved 9000.0" in m for m in v)
     assert any("frac = 1.125" in m for m in v) and any("layout_GBps" in m for m in v)
+
+
+def test_plain_dry_run_has_no_side_legs():
+    """Without --full the run is the headline alone: the dry run (no fingerprint leg) prints a line with no compare leg."""
+    out = _run("--gpus", "2", "--backend", "gloo", "--clips", "0", "--corpus", "2000")
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert r["n_gpus"] == 2 and r["rccl_ranks"] == 2 and "compare" not in r and r["self_check"]["ok"]
+
+
+def test_dump_outputs_writes_exact_words_and_samples_large_batches(tmp_path, monkeypatch):
+    """--dump-outputs: the packed sub-fingerprints as their 32-bit words in float64 (exact), every clip while the batch fits
+    the budget, else the same seeded sample of whole clips on every run, in clip order, with the clip indices."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    packed = torch.from_numpy(np.random.default_rng(5).integers(0, 256, (40, 5, 32), dtype=np.uint8))
+    want = packed.numpy().view("<u4")
+    b.dump_outputs(str(tmp_path / "all"), packed, np)
+    words = np.load(tmp_path / "all" / "packed_subfingerprints.npy")
+    assert words.dtype == np.float64 and words.shape == (40, 5, 8) and words.max() > 2 ** 31
+    assert np.array_equal(words.astype(np.uint32), want)
+    assert np.array_equal(np.load(tmp_path / "all" / "clip_index.npy"), np.arange(40))
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 10 * (5 * 8 * 8 + 8))
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), packed, np)
+    idx = np.load(tmp_path / "s1" / "clip_index.npy")
+    assert idx.shape == (10,) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "clip_index.npy"))
+    sample = np.load(tmp_path / "s1" / "packed_subfingerprints.npy")
+    assert np.array_equal(sample.astype(np.uint32), want[idx.astype(np.int64)])
+    total = sum(f.stat().st_size for f in (tmp_path / "s1").iterdir())
+    assert total <= 10 * (5 * 8 * 8 + 8) + 2 * 128

@@ -519,7 +519,7 @@ def test_sharded_entry_point_with_two_ranks_in_one_process(lb, gpu, oracle):
 
 def test_bench_collective_paths_on_nccl_at_one_rank(gpu):
     """Every branch bench.py takes at N > 1 that is well defined at one rank, on the REAL backend: `torch.distributed.run
-    --nproc-per-node=1 bench.py --gpus 1 --force-dist` initialises the nccl (= RCCL) process group on this GPU, gathers
+    --nproc-per-node=1 bench.py --gpus 1 --full --force-dist` initialises the nccl (= RCCL) process group on this GPU, gathers
     the device descriptions, MAX-reduces passes / elapsed / stats, broadcasts the library communicator's id and the
     query, gathers packed fingerprints, runs the sharded query through ncclAllReduce inside the library, and tears the
     group down.  The bench is a CHILD process (a process that has touched the GPU must never exec another program)."""
@@ -532,7 +532,7 @@ def test_bench_collective_paths_on_nccl_at_one_rank(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--clips", "2000",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--force-dist", "--clips", "2000",
            "--corpus", "200000", "--corpus-hbm", "0", "--steps", "2", "--warmup", "1", "--min-seconds", "0.2",
            "--no-cpu-baseline", "--no-other-configs", "--no-sliding", "--no-files"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
@@ -547,6 +547,36 @@ def test_bench_collective_paths_on_nccl_at_one_rank(gpu):
     assert c["collective_fallback"] is False and c["found_planted"] is True and c["allreduce_ms"] is not None
     assert r["parity"]["bit_exact"] is True if "parity" in r else True
     assert r["self_check"]["ok"]
+
+
+def test_bench_plain_run_dumps_its_outputs(gpu, lb, oracle, tmp_path):
+    """A plain `bench.py` run times the headline alone (no side leg, no parity, no roofline) for exactly --steps steps, and
+    --dump-outputs writes the packed sub-fingerprints of its last step: bit for bit the oracle's for the same seeded clips.
+    The bench is a CHILD process."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--clips", "300",
+           "--min-seconds", "0.1", "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
+    assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["metric"] == "audio_seconds_fingerprinted_per_sec" and r["unit"] == "audio-s/s" and r["higher_is_better"] is True
+    assert r["dtype"] == "f32" and r["value"] > 0 and r["ms_per_step"] > 0 and r["steps"] == 3
+    assert r["sustained"]["passes_timed"] == 3 * r["passes_per_step"]
+    assert not {"roofline", "parity", "cpu_baseline", "other_configs", "compare", "compare_hbm", "compare_sliding",
+                "configs0_files"} & r.keys()
+    words = np.load(out_dir / "packed_subfingerprints.npy")
+    idx = np.load(out_dir / "clip_index.npy")
+    assert words.dtype == np.float64 and idx.dtype == np.float64
+    assert words.shape == (300, 5, 8) and np.array_equal(idx, np.arange(300))
+    n = 12
+    got = lb.unpack_packed(words[:n].astype(np.uint32), 200).reshape(n, 5, 200)
+    want = oracle.fingerprint_batch(oracle.synth_clips(0x4C424144, 0, n, 44100, 44100), oracle.Config(44100, 1024, 64))
+    assert np.array_equal(got, want)
 
 
 @pytest.mark.parametrize("L,seed", [(200, 1), (199, 2), (64, 3)])

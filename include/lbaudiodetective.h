@@ -495,6 +495,31 @@ OSStatus LBAudioDetectiveCorpusQueryBatchKeysDevice(LBAudioDetectiveCorpusRef in
 /* Per-entry scores (debug / parity): device pointer to count float32. */
 OSStatus LBAudioDetectiveCorpusScoresDevice(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
                                             UInt32 inRange, Float32* outScores, void* inStream);
+/* Top-K queries: the inK best matches per query, selected on the device.  Entry e scores exactly what
+ * LBAudioDetectiveCorpusScoresDevice returns for it; the list holds the entries with score > 0, score descending, equal
+ * scores lowest index first, cut at inK (K = 1 is LBAudioDetectiveCorpusQuery's answer, bit for bit).  *outCount =
+ * min(inK, entries with score > 0); unused slots get index -1 and score 0.  1 <= inK <= LBAD_TOPK_MAX, inRange == 0 means
+ * the sub-fingerprint length.  The batch forms write inCount x inK results (query q's list at q * inK) and inCount counts;
+ * a batch equals inCount single calls, bit for bit.  The KeysDevice form writes inCount x inK 64-bit keys (as
+ * LBAudioDetectiveCorpusQueryKeyDevice, global index = inIndexBase + local; each row descending, 0-padded) to the device
+ * pointer outKeys, asynchronously on inStream; the keys of several shards merge by taking the K largest.  The corpus owns
+ * the scratch (scores, histograms, candidates), grown on demand; a call waits for the previous top-K call's device work
+ * before it reuses it. */
+#define LBAD_TOPK_MAX 1024
+OSStatus LBAudioDetectiveCorpusQueryTopK(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                         UInt32 inRange, UInt32 inK, SInt64* outIndices, Float32* outScores, UInt32* outCount);
+OSStatus LBAudioDetectiveCorpusQueryBatchTopK(LBAudioDetectiveCorpusRef inCorpus, const LBAudioDetectiveFingerprintRef* inQueries,
+                                              UInt32 inCount, UInt32 inRange, UInt32 inK,
+                                              SInt64* outIndices, Float32* outScores, UInt32* outCounts);
+OSStatus LBAudioDetectiveCorpusQueryBatchTopKKeysDevice(LBAudioDetectiveCorpusRef inCorpus,
+                                                        const LBAudioDetectiveFingerprintRef* inQueries, UInt32 inCount,
+                                                        UInt32 inRange, UInt32 inK, UInt64 inIndexBase,
+                                                        void* outKeys, void* inStream);
+/* The selection on its own: inRows rows of inCount float32 scores (device, row r at inScores + r * inCount) to inRows x inK
+ * keys at the device pointer outKeys (index = inIndexBase + position in the row; inIndexBase + inCount <= 2^32).  Scores
+ * that are <= 0 or NaN are never selected.  Allocates its own scratch and returns once the keys are written. */
+OSStatus LBAudioDetectiveTopKKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, UInt32 inK,
+                                                  UInt64 inIndexBase, void* outKeys, void* inStream);
 /* Binary corpus file ("LBADCRP1" header + the stored entries' planes; a ragged corpus: "LBADCRP2" header + the
  * entries' sub-fingerprint counts + the records); Load recognises both, reserves max(inCapacity, stored count)
  * entries and, for a ragged corpus, records in proportion. */

@@ -166,6 +166,10 @@ _SIGNATURES = {
     "LBAudioDetectiveCorpusQueryBatch": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, _P(SInt64), _P(Float32)]),
     "LBAudioDetectiveCorpusQueryBatchKeysDevice": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt64, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusScoresDevice": (OSStatus, [Ref, Ref, UInt32, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusQueryTopK": (OSStatus, [Ref, Ref, UInt32, UInt32, _P(SInt64), _P(Float32), _P(UInt32)]),
+    "LBAudioDetectiveCorpusQueryBatchTopK": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, _P(SInt64), _P(Float32), _P(UInt32)]),
+    "LBAudioDetectiveCorpusQueryBatchTopKKeysDevice": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, UInt64, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveTopKKeysFromScoresDevice": (OSStatus, [C.c_void_p, UInt64, UInt32, UInt32, UInt64, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusSetKernelVariant": (OSStatus, [Ref, UInt32]),
     "LBAudioDetectiveCorpusSave": (OSStatus, [Ref, C.c_char_p]),
     "LBAudioDetectiveCorpusLoad": (Ref, [C.c_char_p, UInt64]),

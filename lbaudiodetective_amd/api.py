@@ -637,6 +637,35 @@ class Corpus:
                "CorpusScoresDevice")
         return out
 
+    def query_topk(self, fp: Fingerprint, k: int, range_: int = 0):
+        """The k best matches (LBAudioDetectiveCorpusQueryTopK): (indices int64[n], scores float32[n]), score descending,
+        equal scores lowest index first, n = min(k, entries scoring above 0); k = 1 is query()'s answer."""
+        return self.query_batch_topk([fp], k, range_)[0]
+
+    def query_batch_topk(self, fps, k: int, range_: int = 0):
+        """query_topk for several queries in one call -> list of (indices, scores); equal to separate calls, bit for bit."""
+        n = len(fps)
+        refs = (N.Ref * max(1, n))(*[f._ref for f in fps])
+        idx = np.full((max(1, n), max(1, k)), -1, dtype=np.int64)
+        sc = np.zeros((max(1, n), max(1, k)), dtype=np.float32)
+        cnt = np.zeros(max(1, n), dtype=np.uint32)
+        _check(self._L.LBAudioDetectiveCorpusQueryBatchTopK(self._ref, refs, n, range_, k, idx.ctypes.data_as(C.POINTER(N.SInt64)),
+                                                            sc.ctypes.data_as(C.POINTER(N.Float32)),
+                                                            cnt.ctypes.data_as(C.POINTER(N.UInt32))), "CorpusQueryBatchTopK")
+        return [(idx[i, :cnt[i]].copy(), sc[i, :cnt[i]].copy()) for i in range(n)]
+
+    def query_batch_topk_keys_device(self, fps, k: int, keys_out, range_: int = 0, index_base: int = 0, stream=None):
+        """Writes len(fps) x k 64-bit keys (global index = index_base + local; rows descending, 0-padded) into keys_out
+        (torch int64 on the device, contiguous), asynchronously."""
+        n = len(fps)
+        if keys_out.numel() < n * k or not keys_out.is_contiguous():
+            raise ValueError("keys_out must be a contiguous tensor of at least len(fps) * k int64")
+        refs = (N.Ref * max(1, n))(*[f._ref for f in fps])
+        _check(self._L.LBAudioDetectiveCorpusQueryBatchTopKKeysDevice(self._ref, refs, n, range_, k, index_base,
+                                                                     keys_out.data_ptr(), _stream_ptr(stream)),
+               "CorpusQueryBatchTopKKeysDevice")
+        return keys_out
+
     @staticmethod
     def decode_key(key: int):
         idx, score = N.SInt64(-1), N.Float32(0.0)
@@ -729,6 +758,26 @@ def synth_ragged_corpus_device(seed: int, first: int, counts, subfp_len: int, st
            "SynthRaggedCorpusDevice")
     torch.cuda.current_stream().synchronize() if stream is None else stream.synchronize()   # d_off is a temporary
     return out
+
+
+def topk_keys_from_scores_device(scores, k: int, index_base: int = 0, stream=None):
+    """LBAudioDetectiveTopKKeysFromScoresDevice: the k largest (score, ~index) keys of every row of `scores` (torch float32 on
+    the device, [n] or [rows, n]) -> torch int64 [rows, k] (or [k]), rows descending, 0-padded; scores <= 0 or NaN are never
+    selected."""
+    import torch
+    s = scores.contiguous()
+    rows, n = (1, s.numel()) if s.dim() == 1 else (s.shape[0], s.shape[1])
+    out = torch.empty((rows, k), dtype=torch.int64, device=s.device)
+    _check(N.lib().LBAudioDetectiveTopKKeysFromScoresDevice(s.data_ptr(), n, rows, k, index_base, out.data_ptr(),
+                                                            _stream_ptr(stream)), "TopKKeysFromScoresDevice")
+    return out[0] if s.dim() == 1 else out
+
+
+def decode_topk_keys(keys):
+    """(indices int64[n], scores float32[n]) of one row of top-K keys (any int64 sequence; zero keys are padding)."""
+    k = np.asarray(keys.cpu().numpy() if hasattr(keys, "cpu") else keys, dtype=np.int64).astype(np.uint64)
+    k = k[k != 0]
+    return (0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32)
 
 
 def synth_corpus_device(seed: int, first: int, n_entries: int, n_sub: int, subfp_len: int, out=None, stream=None):

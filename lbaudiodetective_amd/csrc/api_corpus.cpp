@@ -437,6 +437,13 @@ void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->append_event) (void)hipEventDestroy(c->append_event);
     if (c->shard_stale_event) (void)hipEventDestroy(c->shard_stale_event);
+    if (c->topk_ev) { (void)hipEventSynchronize(c->topk_ev); (void)hipEventDestroy(c->topk_ev); }
+    if (c->d_topk_scores) (void)hipFree(c->d_topk_scores);
+    if (c->d_topk_scratch) (void)hipFree(c->d_topk_scratch);
+    if (c->d_topk_q) (void)hipFree(c->d_topk_q);
+    if (c->h_topk_q) (void)hipHostFree(c->h_topk_q);
+    if (c->d_topk_scan_keys) (void)hipFree(c->d_topk_scan_keys);
+    if (c->d_topk_keys) (void)hipFree(c->d_topk_keys);
     if (c->d_fast_key) (void)hipFree(c->d_fast_key);
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -591,6 +598,161 @@ OSStatus LBAudioDetectiveCorpusQueryBatch(LBAudioDetectiveCorpusRef c, const LBA
     return noErr;
     LBAD_GUARD_END
 }
+
+// ---- top-K queries: exact per-entry scores (the unchanged scans' scores path), then the selection of k_topk.hip ------
+namespace lbad {
+namespace {
+
+OSStatus grow_topk(void** ptr, size_t* cap, size_t bytes) {
+    if (*cap >= bytes) return noErr;
+    if (*ptr) (void)hipFree(*ptr);
+    *ptr = nullptr;
+    *cap = 0;
+    LBAD_HIP(hipMalloc(ptr, bytes));
+    *cap = bytes;
+    return noErr;
+}
+
+// inCount queries, their keys to keys (device, inCount x k): groups of up to kQueryBatchMax queries write their score rows
+// (uniform corpus, the specialised shape: ONE pass of the batch scan; otherwise one scores scan per query), then one
+// selection over the group's rows
+OSStatus topk_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range, uint32_t k,
+                        uint64_t index_base, unsigned long long* keys, hipStream_t stream) {
+    if (!c || !qs || !keys || n == 0 || k == 0 || k > kTopKMax) return kLBAudioDetectiveArgumentInvalid;
+    if (index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!qs[i] || qs[i]->length != c->subfp_len || qs[i]->count == 0) return kLBAudioDetectiveArgumentInvalid;
+    if (range == 0) range = c->subfp_len;   // LBAudioDetective.m:443-445
+    bool batch_scan = !c->ragged && c->variant != 1;
+    for (uint32_t i = 0; i < n && batch_scan; ++i) batch_scan = planes_fast_supported(c->subfp_len, c->n_sub, qs[i]->count);
+    // the previous call's scans and selection may still read / write the scratch (on whatever stream it ran)
+    if (c->topk_ev) LBAD_HIP(hipEventSynchronize(c->topk_ev));
+    else LBAD_HIP(hipEventCreateWithFlags(&c->topk_ev, hipEventDisableTiming));
+    if (c->count == 0) {
+        LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * k * sizeof(unsigned long long), stream));
+        LBAD_HIP(hipEventRecord(c->topk_ev, stream));
+        return noErr;
+    }
+    const uint32_t rows = n < kQueryBatchMax ? n : kQueryBatchMax;
+    OSStatus st = grow_topk(reinterpret_cast<void**>(&c->d_topk_scores), &c->topk_scores_cap, (size_t)rows * c->count * sizeof(float));
+    if (st == noErr) st = grow_topk(&c->d_topk_scratch, &c->topk_scratch_cap, topk_scratch_bytes(rows));
+    if (st != noErr) return st;
+    if (!c->d_topk_scan_keys) LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_topk_scan_keys), kQueryBatchMax * sizeof(unsigned long long)));
+    const uint32_t kw = plane_query_words();
+    if (batch_scan) {
+        const size_t bytes = (size_t)n * kw * sizeof(uint32_t);   // every group's blocks at once: the copies are asynchronous
+        if (c->topk_q_cap < bytes) {
+            if (c->d_topk_q) (void)hipFree(c->d_topk_q);
+            if (c->h_topk_q) (void)hipHostFree(c->h_topk_q);
+            c->d_topk_q = nullptr;
+            c->h_topk_q = nullptr;
+            c->topk_q_cap = 0;
+            LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_topk_q), bytes));
+            LBAD_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_topk_q), bytes, hipHostMallocDefault));
+            c->topk_q_cap = bytes;
+        }
+        std::memset(c->h_topk_q, 0, bytes);
+        std::vector<uint32_t> slots, block;
+        for (uint32_t i = 0; i < n; ++i) {
+            pack_fingerprint(qs[i], slots);
+            build_plane_query(slots.data(), c->n_sub, range, block);
+            std::memcpy(c->h_topk_q + (size_t)i * kw, block.data(), block.size() * sizeof(uint32_t));
+        }
+        LBAD_HIP(hipMemcpyAsync(c->d_topk_q, c->h_topk_q, bytes, hipMemcpyHostToDevice, stream));
+    }
+    for (uint32_t q0 = 0; q0 < n; q0 += kQueryBatchMax) {
+        const uint32_t g = n - q0 < kQueryBatchMax ? n - q0 : kQueryBatchMax;
+        if (batch_scan) {
+            LBAD_HIP(launch_compare_planes_batch_scores(c->d_planes, c->capacity, c->count, c->n_sub, c->d_topk_q + (size_t)q0 * kw, g,
+                                                        c->d_topk_scores, stream));
+        } else {
+            for (uint32_t i = 0; i < g; ++i) {
+                st = run_query(c, qs[q0 + i], range, 0, c->d_topk_scores + (size_t)i * c->count, c->d_topk_scan_keys + i, stream);
+                if (st != noErr) return st;
+            }
+        }
+        LBAD_HIP(launch_topk_keys(c->d_topk_scores, c->count, g, k, index_base, c->d_topk_scratch, keys + (size_t)q0 * k, stream));
+    }
+    LBAD_HIP(hipEventRecord(c->topk_ev, stream));
+    return noErr;
+}
+
+// host-returning form: keys through the corpus' own buffer on the null stream, then decoded
+OSStatus topk_host_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range, uint32_t k,
+                        SInt64* out_idx, Float32* out_scores, UInt32* out_counts) {
+    if (!c || !qs || n == 0 || k == 0 || k > kTopKMax || !out_idx || !out_scores || !out_counts) return kLBAudioDetectiveArgumentInvalid;
+    if (c->topk_ev) LBAD_HIP(hipEventSynchronize(c->topk_ev));    // (the key buffer is the previous call's until then)
+    const size_t words = (size_t)n * k;
+    OSStatus st = grow_topk(reinterpret_cast<void**>(&c->d_topk_keys), &c->topk_keys_cap, words * sizeof(unsigned long long));
+    if (st == noErr) st = topk_keys_impl(c, qs, n, range, k, 0, c->d_topk_keys, nullptr);
+    if (st != noErr) return st;
+    std::vector<unsigned long long> keys(words);
+    LBAD_HIP(hipMemcpy(keys.data(), c->d_topk_keys, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < n; ++q) {
+        UInt32 got = 0;
+        for (uint32_t i = 0; i < k; ++i) {
+            LBAudioDetectiveCorpusDecodeKey(keys[(size_t)q * k + i], out_idx + (size_t)q * k + i, out_scores + (size_t)q * k + i);
+            if (out_idx[(size_t)q * k + i] >= 0) ++got;
+        }
+        out_counts[q] = got;
+    }
+    return noErr;
+}
+
+}  // namespace
+}  // namespace lbad
+
+extern "C" {
+
+OSStatus LBAudioDetectiveCorpusQueryBatchTopKKeysDevice(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
+                                                        UInt32 inCount, UInt32 inRange, UInt32 inK, UInt64 inIndexBase,
+                                                        void* outKeys, void* inStream) {
+    LBAD_GUARD_BEGIN
+    return lbad::topk_keys_impl(c, inQueries, inCount, inRange, inK, inIndexBase, static_cast<unsigned long long*>(outKeys),
+                                static_cast<hipStream_t>(inStream));
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusQueryBatchTopK(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
+                                              UInt32 inCount, UInt32 inRange, UInt32 inK, SInt64* outIndices, Float32* outScores,
+                                              UInt32* outCounts) {
+    LBAD_GUARD_BEGIN
+    return lbad::topk_host_impl(c, inQueries, inCount, inRange, inK, outIndices, outScores, outCounts);
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusQueryTopK(LBAudioDetectiveCorpusRef c, LBAudioDetectiveFingerprintRef inQuery, UInt32 inRange,
+                                         UInt32 inK, SInt64* outIndices, Float32* outScores, UInt32* outCount) {
+    LBAD_GUARD_BEGIN
+    if (!inQuery) return kLBAudioDetectiveArgumentInvalid;
+    return lbad::topk_host_impl(c, &inQuery, 1, inRange, inK, outIndices, outScores, outCount);
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveTopKKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, UInt32 inK,
+                                                  UInt64 inIndexBase, void* outKeys, void* inStream) {
+    LBAD_GUARD_BEGIN
+    if (!inScores || !outKeys || inRows == 0 || inK == 0 || inK > lbad::kTopKMax) return kLBAudioDetectiveArgumentInvalid;
+    if (inCount > 0x100000000ull || inIndexBase + inCount > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
+    hipStream_t stream = static_cast<hipStream_t>(inStream);
+    unsigned long long* keys = static_cast<unsigned long long*>(outKeys);
+    constexpr uint32_t kRowsPerLaunch = 64;                // bounds the scratch (about 11 MiB)
+    const uint32_t rows = inRows < kRowsPerLaunch ? inRows : kRowsPerLaunch;
+    void* scratch = nullptr;
+    LBAD_HIP(hipMalloc(&scratch, lbad::topk_scratch_bytes(rows)));
+    OSStatus st = noErr;
+    for (uint32_t r0 = 0; r0 < inRows && st == noErr; r0 += rows) {
+        const uint32_t g = inRows - r0 < rows ? inRows - r0 : rows;
+        st = lbad::hip_status(lbad::launch_topk_keys(inScores + (size_t)r0 * inCount, inCount, g, inK, inIndexBase, scratch,
+                                                     keys + (size_t)r0 * inK, stream), "top-K selection", __LINE__);
+    }
+    const OSStatus done = lbad::hip_status(hipStreamSynchronize(stream), "top-K selection", __LINE__);
+    (void)hipFree(scratch);
+    return st != noErr ? st : done;
+    LBAD_GUARD_END
+}
+
+}  // extern "C"
 
 // ---- corpus file: header + the planes of the stored entries, plane-major ----------------------------
 namespace {

@@ -259,6 +259,19 @@ hipError_t launch_compare_planes_batch(const uint4* d_planes, uint64_t plane_str
                                        const uint32_t* d_qblocks, uint32_t n_queries, uint64_t index_base,
                                        unsigned long long* d_keys, hipStream_t stream);
 void pack_fingerprint(const struct ::LBAudioDetectiveFingerprint* fp, std::vector<uint32_t>& out);
+// the batch scan's scores-writing form: d_scores receives n_queries rows of n_entries scores (row q at d_scores + q * n_entries)
+hipError_t launch_compare_planes_batch_scores(const uint4* d_planes, uint64_t plane_stride, uint64_t n_entries, uint32_t n_sub,
+                                              const uint32_t* d_qblocks, uint32_t n_queries, float* d_scores, hipStream_t stream);
+constexpr uint32_t kQueryBatchMax = 8;   // queries per pass of the batch scan (k_compare.hip: kQueryBatch)
+
+// top-K selection (k_topk.hip): per row of n scores (row r at d_scores + r * n) the k <= kTopKMax largest keys
+// (score bits << 32) | (0xFFFFFFFF - (index_base + e)) of the entries whose score is > 0 (NaN never), descending, 0-padded,
+// to d_keys + r * k.  d_scratch: topk_scratch_bytes(rows) bytes, initialised by the sequence itself; a fixed sequence of
+// launches on `stream`, no host round trip.  index_base + n <= 2^32.
+constexpr uint32_t kTopKMax = LBAD_TOPK_MAX;
+size_t topk_scratch_bytes(uint32_t rows);
+hipError_t launch_topk_keys(const float* d_scores, uint64_t n, uint32_t rows, uint32_t k, uint64_t index_base, void* d_scratch,
+                            unsigned long long* d_keys, hipStream_t stream);
 
 // ragged corpus (k_sliding.hip): a stream of 32-byte sub-fingerprint records, entries of any length back to back
 bool sliding_supported(uint32_t subfp_len);
@@ -484,4 +497,19 @@ struct LBAudioDetectiveCorpus {
     bool shard_stale = false;                    // a sharded query timed out: work may still be queued behind the key block
     hipEvent_t shard_stale_event = nullptr;      // ... recorded behind that work when the call gave up (the stream may be gone by the next call)
     uint64_t query_seq = 0;
+    // top-K queries (api_corpus.cpp): score rows (up to kQueryBatchMax x count floats), the selection's scratch, the staged
+    // query blocks of the batch scan, the scans' own key words (the top-1 state -- d_key, the polled slots -- stays
+    // untouched) and the keys of the host-returning forms.  Grown on demand; a call reuses them only after topk_ev, recorded
+    // behind the previous call's last kernel.
+    float* d_topk_scores = nullptr;
+    size_t topk_scores_cap = 0;                  // bytes, and so on below
+    void* d_topk_scratch = nullptr;
+    size_t topk_scratch_cap = 0;
+    uint32_t* d_topk_q = nullptr;
+    uint32_t* h_topk_q = nullptr;
+    size_t topk_q_cap = 0;
+    unsigned long long* d_topk_scan_keys = nullptr;   // kQueryBatchMax words
+    unsigned long long* d_topk_keys = nullptr;
+    size_t topk_keys_cap = 0;
+    hipEvent_t topk_ev = nullptr;
 };

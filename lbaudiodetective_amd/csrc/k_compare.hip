@@ -386,8 +386,12 @@ __global__ __launch_bounds__(kPlaneThreads) void compare_planes_kernel(const uin
 // scalar instruction -- and the quotient by two fused multiply-adds on (rh, rl) from the query block instead of an IEEE division
 // per sub-fingerprint: 125 instructions per (entry, query).
 constexpr int kQueryBatch = 8;
+static_assert(kQueryBatch == (int)kQueryBatchMax, "internal.hpp names the batch size");
 
-template <int NSUB>
+// SCORES (top-K queries): keys_out is then a float array and query q's score of entry e goes to [q * n_entries + e] instead
+// of the running maxima -- the same match, bit for bit.  (The pointer is reused rather than added: a further argument moves
+// the hidden kernel arguments, and the SCORES = false instances of the top-1 batch keep their exact code.)
+template <int NSUB, bool SCORES = false>
 __global__ __launch_bounds__(kThreads) void compare_planes_batch_kernel(const uint4* __restrict__ planes,
                                                                         uint64_t stride, uint64_t n_entries,
                                                                         const uint32_t* __restrict__ qblocks,
@@ -431,11 +435,16 @@ __global__ __launch_bounds__(kThreads) void compare_planes_batch_kernel(const ui
                 }
                 const float cand = __fdiv_rn(sum, (float)NSUB);
                 const float match = (0.0f < cand) ? cand : 0.0f;
-                const unsigned long long k = make_key(match, index_base + e);
-                best[q] = k > best[q] ? k : best[q];
+                if constexpr (SCORES) {
+                    reinterpret_cast<float*>(keys_out)[(uint64_t)q * n_entries + e] = match;
+                } else {
+                    const unsigned long long k = make_key(match, index_base + e);
+                    best[q] = k > best[q] ? k : best[q];
+                }
             }
         }
     }
+    if constexpr (SCORES) return;
 #pragma unroll
     for (int q = 0; q < kQueryBatch; ++q) {
         if ((uint32_t)q < n_queries) block_max_key(best[q], keys_out + q);
@@ -608,6 +617,34 @@ static hipError_t launch_batch_n(const uint4* d_planes, uint64_t stride, uint64_
 }
 
 uint32_t plane_query_words() { return kPlaneQueryWords; }
+
+template <int NSUB>
+static hipError_t launch_batch_scores_n(const uint4* d_planes, uint64_t stride, uint64_t n_entries, const uint32_t* d_qblocks,
+                                        uint32_t n_queries, float* d_scores, hipStream_t stream) {
+    for (uint32_t q0 = 0; q0 < n_queries; q0 += kQueryBatch) {
+        const uint32_t nq = n_queries - q0 < (uint32_t)kQueryBatch ? n_queries - q0 : (uint32_t)kQueryBatch;
+        hipLaunchKernelGGL((compare_planes_batch_kernel<NSUB, true>), dim3(grid_for(n_entries)), dim3(kThreads), 0, stream,
+                           d_planes, stride, n_entries, d_qblocks + (size_t)q0 * kPlaneQueryWords, nq, (uint64_t)0,
+                           reinterpret_cast<unsigned long long*>(d_scores + (size_t)q0 * n_entries));
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_compare_planes_batch_scores(const uint4* d_planes, uint64_t plane_stride, uint64_t n_entries, uint32_t n_sub,
+                                              const uint32_t* d_qblocks, uint32_t n_queries, float* d_scores, hipStream_t stream) {
+    if (n_entries == 0 || n_queries == 0) return hipSuccess;
+    switch (n_sub) {
+        case 1: return launch_batch_scores_n<1>(d_planes, plane_stride, n_entries, d_qblocks, n_queries, d_scores, stream);
+        case 2: return launch_batch_scores_n<2>(d_planes, plane_stride, n_entries, d_qblocks, n_queries, d_scores, stream);
+        case 3: return launch_batch_scores_n<3>(d_planes, plane_stride, n_entries, d_qblocks, n_queries, d_scores, stream);
+        case 4: return launch_batch_scores_n<4>(d_planes, plane_stride, n_entries, d_qblocks, n_queries, d_scores, stream);
+        case 5: return launch_batch_scores_n<5>(d_planes, plane_stride, n_entries, d_qblocks, n_queries, d_scores, stream);
+        case 6: return launch_batch_scores_n<6>(d_planes, plane_stride, n_entries, d_qblocks, n_queries, d_scores, stream);
+        case 7: return launch_batch_scores_n<7>(d_planes, plane_stride, n_entries, d_qblocks, n_queries, d_scores, stream);
+        case 8: return launch_batch_scores_n<8>(d_planes, plane_stride, n_entries, d_qblocks, n_queries, d_scores, stream);
+        default: return hipErrorNotSupported;
+    }
+}
 
 // d_qblocks: n_queries blocks of plane_query_words() words each (build_plane_query output, zero padded)
 hipError_t launch_compare_planes_batch(const uint4* d_planes, uint64_t plane_stride, uint64_t n_entries, uint32_t n_sub,

@@ -55,6 +55,29 @@ def allreduce_best(key_tensor, group=None):
     return key_tensor
 
 
+def merge_topk_keys(gathered, k: int):
+    """[R, Q, K] int64 top-K keys of R shards (rows descending, 0-padded) -> [Q, k]: the k largest of each query's R * K keys.
+    The keys are non-negative as int64 (score bits <= 0x7F800000) and distinct apart from the zero padding (shards never
+    share an index), so the k largest are the global top-k in the library's order: score descending, lowest index first."""
+    import torch
+    r, q, kk = gathered.shape
+    flat = gathered.permute(1, 0, 2).reshape(q, r * kk)
+    return torch.sort(flat, dim=1, descending=True).values[:, :k].contiguous()
+
+
+def gather_topk_keys(local_keys, k: int, group=None):
+    """Collective: this rank's [Q, K] top-K keys -> the merged [Q, k] of every rank (one all_gather_into_tensor)."""
+    import torch
+    import torch.distributed as dist
+    if not _collective(group):
+        return merge_topk_keys(local_keys.unsqueeze(0), k)
+    world = dist.get_world_size(group)
+    q, kk = local_keys.shape
+    out = torch.empty((world * q, kk), dtype=local_keys.dtype, device=local_keys.device)   # (rank-major; gloo wants it flat)
+    dist.all_gather_into_tensor(out, local_keys.contiguous(), group=group)
+    return merge_topk_keys(out.view(world, q, kk), k)
+
+
 def gather_packed(local_packed, group=None):
     """Optional last step of sharded fingerprinting: every rank contributes its [n_local, count, 32]
     packed sub-fingerprints (160 B per one-second clip) and receives all of them in rank order.  Ranks
@@ -154,6 +177,16 @@ class ShardedCorpus:
         self.local.query_batch_keys_device(fps, keys_out, range_, index_base=self.begin)
         allreduce_best(keys_out, self.group)
         return [decode_key(int(k)) for k in keys_out.tolist()]
+
+    def query_topk(self, fps, k: int, range_: int = 0):
+        """Collective: the k best matches of every query over all shards -> list of (global indices, scores).  This rank's
+        keys (index_base = its first global index), one all-gather of the [Q, k] keys through torch.distributed, the merge."""
+        import torch
+        from .api import decode_topk_keys
+        keys = torch.zeros((len(fps), k), dtype=torch.int64, device="cuda")
+        self.local.query_batch_topk_keys_device(fps, k, keys, range_, index_base=self.begin)
+        merged = gather_topk_keys(keys, k, self.group).cpu()
+        return [decode_topk_keys(row) for row in merged]
 
     def query(self, fp, range_: int = 0, key_out=None):
         """Collective: every rank calls it with the same query; returns (global index, score)."""

@@ -682,6 +682,22 @@ void lbo_corpus_best_packed(const uint64_t* query, uint32_t n_query, const uint6
     *best_score = best;
 }
 
+/* Every entry's score of the packed compare (the checker of the device scans at full corpus size: 10 M entries of
+ * 5 x 200 Booleans are 1.6 GB packed, 10 GB as Booleans).  Same mask and loop as lbo_corpus_best_packed. */
+void lbo_corpus_scores_packed(const uint64_t* query, uint32_t n_query, const uint64_t* corpus,
+                              uint64_t n_entries, uint32_t n_sub, uint32_t subfp_len, uint32_t range,
+                              int nthreads, float* scores_out) {
+    uint64_t mask[4] = {0, 0, 0, 0};
+    const uint32_t lim = range < subfp_len ? range : subfp_len;
+    for (uint32_t i = 0; i < lim && i < 256u; i += 2) mask[i >> 6] |= 1ull << (i & 63u);
+    (void)nthreads;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1)
+#endif
+    for (int64_t e = 0; e < (int64_t)n_entries; ++e)
+        scores_out[e] = packed_compare_fp(query, n_query, corpus + 4 * (size_t)e * n_sub, n_sub, mask);
+}
+
 /* ------------------------------------------------------------------------------------------
  * synthetic inputs (integer arithmetic only, so a device generator can match bit for bit)
  * ---------------------------------------------------------------------------------------- */

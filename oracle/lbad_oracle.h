@@ -149,6 +149,10 @@ void lbo_pack_bools(const uint8_t* bools, uint64_t n_rows, uint32_t subfp_len, u
 void lbo_corpus_best_packed(const uint64_t* query, uint32_t n_query, const uint64_t* corpus,
                             uint64_t n_entries, uint32_t n_sub, uint32_t subfp_len, uint32_t range,
                             int nthreads, int64_t* best_index, float* best_score);
+/* every entry's score of the same packed compare (scores_out: n_entries floats) */
+void lbo_corpus_scores_packed(const uint64_t* query, uint32_t n_query, const uint64_t* corpus,
+                              uint64_t n_entries, uint32_t n_sub, uint32_t subfp_len, uint32_t range,
+                              int nthreads, float* scores_out);
 
 /* Deterministic integer synthetic PCM (bench/test input, not a reference function). */
 void lbo_synth_sine_table(int16_t* table1024);

@@ -90,6 +90,8 @@ def lib():
     sig("lbo_pack_bools", None, [u8p, C.c_uint64, C.c_uint32, u64p])
     sig("lbo_corpus_best_packed", None, [u64p, C.c_uint32, u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_float)])
+    sig("lbo_corpus_scores_packed", None, [u64p, C.c_uint32, u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_int, f32p])
     sig("lbo_synth_ragged_count", C.c_uint32, [C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32])
     sig("lbo_file_decode", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint64), C.POINTER(C.c_double)])
     sig("lbo_file_decode_bytes", C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint64),
@@ -304,6 +306,19 @@ def corpus_best_packed(query_words: np.ndarray, corpus_words: np.ndarray, subfp_
                                  corpus_words.reshape(-1) if corpus_words.size else np.zeros(4, np.uint64),
                                  n_entries, n_sub, subfp_len, range_, nthreads, C.byref(bi), C.byref(bs))
     return int(bi.value), float(bs.value)
+
+
+def corpus_scores_packed(query_words: np.ndarray, corpus_words: np.ndarray, subfp_len: int, range_: int, nthreads: int = 1):
+    """Every entry's score of the packed compare: query [n_query, 4], corpus [n_entries, n_sub, 4] uint64 -> float32
+    [n_entries] (no copy of a contiguous uint64 corpus)."""
+    query_words = np.ascontiguousarray(query_words, np.uint64)
+    corpus_words = np.ascontiguousarray(corpus_words, np.uint64)
+    n_entries, n_sub, _ = corpus_words.shape
+    out = np.zeros(max(n_entries, 1), np.float32)
+    lib().lbo_corpus_scores_packed(query_words.reshape(-1) if query_words.size else np.zeros(4, np.uint64),
+                                   query_words.shape[0], corpus_words.reshape(-1) if corpus_words.size else np.zeros(4, np.uint64),
+                                   n_entries, n_sub, subfp_len, range_, nthreads, out)
+    return out[:n_entries]
 
 
 def corpus_best_ragged(query: np.ndarray, entries, range_: int, nthreads: int = 1, want_scores: bool = False):

@@ -452,8 +452,9 @@ def _free_gib(gpu):
 def test_full_size_fingerprint_batch(lb, gpu, oracle):
     """configs[1]: 100 000 one-second 44.1 kHz clips.  (1) the specialised and the generic kernels
     agree on every sub-fingerprint of the whole batch; (2) identical clips planted at scattered
-    batch positions give identical bits; (3) a sample is bit-exact against the oracle; (4) a batch
-    processed in several launches (small scratch limit) equals the single-launch result."""
+    batch positions give identical bits; (3) the first 1000 clips, the twins and the last clip are
+    bit-exact against the oracle; (4) a batch processed in several launches (small scratch limit)
+    equals the single-launch result."""
     n = 100_000
     if _free_gib(gpu) < 60:
         pytest.skip("needs ~45 GiB of HBM")
@@ -481,6 +482,12 @@ def test_full_size_fingerprint_batch(lb, gpu, oracle):
     want = oracle.fingerprint_batch(host, oracle.Config(44100, 1024), nthreads=4)
     got = lb.unpack_packed(fast[pick].cpu().numpy(), 200).reshape(len(pick), 5, 200)
     assert np.array_equal(got, want)
+    # the first 1000 clips, the twins and the last clip against the oracle
+    pick = list(range(1000)) + twins[1:] + [n - 1]
+    want = oracle.fingerprint_batch(clips[pick].cpu().numpy(), oracle.Config(44100, 1024), nthreads=16)
+    got = lb.unpack_packed(fast[pick].cpu().numpy(), 200).reshape(len(pick), 5, 200)
+    bad = [pick[i] for i in range(len(pick)) if not np.array_equal(got[i], want[i])]
+    assert not bad, bad[:10]
     # every sub-fingerprint carries exactly 100 sign pairs with at most one Boolean set per pair
     words = fast.view(gpu.int32).reshape(-1, 8)
     both = words & (words >> 1) & 0x55555555
@@ -494,7 +501,7 @@ def test_full_size_fingerprint_batch(lb, gpu, oracle):
 ])
 def test_full_size_other_configurations(lb, gpu, oracle, name, rate, window, seconds, n, stereo):
     """The processing configurations of BASELINE configs[0] and configs[4] at batch size: specialised /
-    automatic and generic kernels agree on the whole batch, twins give identical bits, a sample is
+    automatic and generic kernels agree on the whole batch, twins give identical bits, 250 clips are
     bit-exact against the oracle, and a chunked run equals the single launch."""
     samples = rate * seconds
     if _free_gib(gpu) < 30:
@@ -521,20 +528,40 @@ def test_full_size_other_configurations(lb, gpu, oracle, name, rate, window, sec
     want = oracle.fingerprint_batch(clips[pick].cpu().numpy(), cfg, nthreads=4)
     got = lb.unpack_packed(auto[pick].cpu().numpy(), 200).reshape(want.shape)
     assert np.array_equal(got, want), name
+    # 250 clips against the oracle: the first 100, the last 50, a stride across the rest (the twins among them)
+    pick = sorted(set(range(100)) | set(range(n - 50, n)) | set(range(100, n - 50, (n - 150) // 100)) | set(twins))
+    assert len(pick) >= 200
+    want = oracle.fingerprint_batch(clips[pick].cpu().numpy(), cfg, nthreads=16)
+    got = lb.unpack_packed(auto[pick].cpu().numpy(), 200).reshape(want.shape)
+    bad = [pick[i] for i in range(len(pick)) if not np.array_equal(got[i], want[i])]
+    assert not bad, (name, bad[:10])
 
 
 @pytest.mark.parametrize("n", [1_000_000, 10_000_000])
 def test_full_size_corpus(lb, gpu, oracle, n):
     """configs[2]/[3]: 1 M and 10 M fingerprints.  The planted near-duplicate is found with the
     oracle's score; specialised and generic scans return the same key; 8 contiguous shards
-    max-reduced equal the whole-corpus answer (the all-reduce of config 4 on one device)."""
+    max-reduced equal the whole-corpus answer (the all-reduce of config 4 on one device); every key
+    of a batch of 9 queries (two groups of the batch scan) equals the oracle's best over all entries."""
     from lbaudiodetective_amd import sharded
     if _free_gib(gpu) < 8:
         pytest.skip("needs a few GiB of HBM")
     corpus = lb.Corpus(200, 5, n)
     step = 1 << 20
+    # fingerprints that are not the generator's, planted across the corpus (a twin pair among them) for the batch leg
+    extra = oracle.synth_corpus(CSEED + 9, 0, 7, 5, 200)
+    lo_twin, hi_twin = n // 3, n // 3 + n // 2
+    plant = {n - 1: extra[0], 0: extra[1], n // 2 + 1: extra[2], 3 * n // 4: extra[3], 123_457: extra[4],
+             lo_twin: extra[5], hi_twin: extra[5]}
+    host = []                                             # the packed rows as appended: the oracle's input
     for b in range(0, n, step):
-        corpus.append_packed_device(lb.synth_corpus_device(CSEED, b, min(step, n - b), 5, 200))
+        blk = lb.synth_corpus_device(CSEED, b, min(step, n - b), 5, 200)
+        for at, rows in plant.items():
+            if b <= at < b + blk.shape[0]:
+                blk[at - b] = gpu.from_numpy(np.ascontiguousarray(oracle.pack_bools(rows)).view(np.uint8)).cuda()
+        corpus.append_packed_device(blk)
+        host.append(blk.cpu().numpy().view(np.uint64).reshape(-1, 5, 4))
+    host = np.concatenate(host)
     planted = 777_777
     entry = oracle.synth_entry(CSEED, planted, 5, 200)
     q = _planted_query(oracle, entry, 0.07)
@@ -562,6 +589,27 @@ def test_full_size_corpus(lb, gpu, oracle, n):
     # scores elsewhere sit at chance level (essay p.43): sample the score vector
     scores = corpus.scores_device(fq, 200)[:: max(1, n // 4096)].cpu().numpy()
     assert 0.45 < float(np.median(scores)) < 0.55
+    # the batch scan (compare_planes_batch_kernel, groups of 8: 9 queries take two) against the oracle over every entry:
+    # near-copies of the planted rows, the twin pair (the lower index wins), the query above, an unplanted fingerprint,
+    # the all-zero query
+    corpus.set_kernel_variant(0)
+    qs = [_planted_query(oracle, extra[i], pct, seed=i) for i, pct in enumerate((0.02, 0.05, 0.1, 0.2, 0.3))]
+    qs += [extra[5], q, extra[6], np.zeros((5, 200), np.uint8)]
+    fqs = [lb.Fingerprint.from_bools(x) for x in qs]
+    keys = gpu.zeros(len(qs), dtype=gpu.int64, device="cuda")
+    base = (1 << 32) - n
+    for rg in (0, 199):
+        want = []
+        for x in qs:
+            s = oracle.corpus_scores_packed(oracle.pack_bools(x), host, 200, rg if rg else 200, nthreads=16)
+            i = int(np.argmax(s))
+            want.append((i, int(s[i].view(np.uint32))) if s[i] > 0 else (-1, 0))
+        got = corpus.query_batch(fqs, rg)
+        assert [(i, int(np.float32(s).view(np.uint32))) for i, s in got] == want, rg
+        corpus.query_batch_keys_device(fqs, keys, rg, index_base=base)
+        dec = [sharded.decode_key(int(k)) for k in keys.cpu().tolist()]
+        assert [(i, int(np.float32(s).view(np.uint32))) for i, s in dec] == [(i + base if i >= 0 else -1, s) for i, s in want], rg
+    assert [g[0] for g in got] == [n - 1, 0, n // 2 + 1, 3 * n // 4, 123_457, lo_twin, planted, got[7][0], -1]
 
 
 # ---------------------------------------------------------------------------------------------

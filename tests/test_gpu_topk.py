@@ -281,9 +281,15 @@ def test_full_size_uniform_corpus(lb, gpu, oracle):
     corpus.append_packed_device(packed)
     fq = lb.Fingerprint.from_bools(q)
     scores = corpus.scores_device(fq).cpu().numpy()
+    # every one of the 10 M scores against the oracle's, from the packed rows as appended
+    words = packed.cpu().numpy().view(np.uint64).reshape(n, 5, 4)
+    want = oracle.corpus_scores_packed(oracle.pack_bools(q), words, 200, 200, nthreads=16)
+    bad = np.nonzero(scores.view(np.uint32) != want.view(np.uint32))[0]
+    assert len(bad) == 0, (len(bad), bad[:5])
     for k in (10, 1024):
         idx, sc = corpus.query_topk(fq, k)
         _same((idx, sc), _expected(scores, k), k)
+        _same((idx, sc), _expected(want, k), ("oracle", k))
     idx, sc = corpus.query_topk(fq, 10)
     assert sc[0] == 1.0 and 4321 in idx.tolist() and 9_999_999 in idx.tolist()
     for i, s in zip(idx[:6], sc[:6]):
@@ -291,10 +297,12 @@ def test_full_size_uniform_corpus(lb, gpu, oracle):
         assert np.float32(oracle.compare_fp(q, e, 200)).view(np.uint32) == np.float32(s).view(np.uint32), i
     assert (int(idx[0]), float(sc[0])) == corpus.query(fq)
     # a batch of 8 near-copies against the full corpus
-    qs = [lb.Fingerprint.from_bools(_near(rng, q, f)) for f in range(8)]
+    near = [_near(rng, q, f) for f in range(8)]
+    qs = [lb.Fingerprint.from_bools(x) for x in near]
     batch = corpus.query_batch_topk(qs, 10)
-    for fqi, got in zip(qs, batch):
+    for x, fqi, got in zip(near, qs, batch):
         _same(got, _expected(corpus.scores_device(fqi).cpu().numpy(), 10))
+        _same(got, _expected(oracle.corpus_scores_packed(oracle.pack_bools(x), words, 200, 200, nthreads=16), 10), "oracle")
 
 
 def test_two_shards_in_one_process(lb, gpu, oracle):

@@ -211,6 +211,47 @@ def test_packed_popcount_scan_equals_boolean_loop(oracle):
     assert oracle.corpus_best_packed(oracle.pack_bools(z), oracle.pack_bools(c), 200, 200) == oracle.corpus_best(z, c, 200) == (-1, 0.0)
 
 
+def _best_of(scores):
+    """The best-match loop of Tests.m:57-91 over a score vector: strict '<' from 0.0, lowest index on ties, -1 when nothing
+    scores above 0."""
+    if len(scores) == 0 or not (scores.max() > 0):
+        return -1, 0.0
+    i = int(np.argmax(scores))                                   # (argmax returns the first maximum)
+    return i, float(scores[i])
+
+
+@pytest.mark.parametrize("L", [1, 2, 33, 199, 200, 256])
+def test_packed_scores_equal_the_boolean_compare(oracle, L):
+    """lbo_corpus_scores_packed (the checker of the device scans at full corpus size) scores every entry as compare_fp
+    (Fp.m:119-149: swap and slide when the counts differ) does, bit for bit, and its arg-max is corpus_best: queries
+    shorter than, as long as and longer than the entries, ranges 0 (= L), 1, 2, L/2 + 1, L, L + 7, Boolean pairs with both
+    Booleans set, all-zero entries and sub-fingerprints, the all-zero query, ties."""
+    rng = np.random.default_rng(L)
+    n, ns = 70, 3
+    corpus = (rng.random((n, ns, L)) < 0.45).astype(np.uint8)      # (about a fifth of the pairs are 11)
+    corpus[5] = 0
+    corpus[n - 1] = 0
+    corpus[9, 1] = 0
+    corpus[40] = corpus[11]                                        # a tie: entry 11 must win it
+    for nq in (1, ns, ns + 2):
+        base = np.concatenate([corpus[11], corpus[12]])[:nq]
+        queries = [base, (rng.random((nq, L)) < 0.5).astype(np.uint8), np.zeros((nq, L), np.uint8)]
+        for qi, q in enumerate(queries):
+            for rg in (0, 1, 2, L // 2 + 1, L, L + 7):
+                r = rg if rg else L
+                got = oracle.corpus_scores_packed(oracle.pack_bools(q), oracle.pack_bools(corpus), L, r, nthreads=3)
+                want = np.array([oracle.compare_fp(q, e, r) for e in corpus], np.float32)
+                assert got.dtype == np.float32 and got.shape == (n,)
+                assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (nq, qi, rg)
+                bi, bs = oracle.corpus_best(q, corpus, r)
+                assert _best_of(got) == (bi, bs), (nq, qi, rg)
+                if qi == 2:
+                    assert bi == -1 and not got.any()
+                elif qi == 0 and nq == ns:                       # a copy of entry 11 (and 40) scores the maximum
+                    assert got[11] == got[40] == got.max() and bi <= 11
+    assert oracle.corpus_scores_packed(oracle.pack_bools(corpus[0]), np.zeros((0, ns, 4), np.uint64), L, L).shape == (0,)
+
+
 def test_ragged_best_match_against_python(oracle):
     """lbo_corpus_best_ragged (entries of different lengths, the shape of LBAudioDetectiveTests.m:57-91) against the
     pure-Python restatement of Fp.m:119-176 entry by entry; strict '<' from 0.0 (T.m:60,80): the lowest index wins

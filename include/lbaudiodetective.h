@@ -520,6 +520,47 @@ OSStatus LBAudioDetectiveCorpusQueryBatchTopKKeysDevice(LBAudioDetectiveCorpusRe
  * that are <= 0 or NaN are never selected.  Allocates its own scratch and returns once the keys are written. */
 OSStatus LBAudioDetectiveTopKKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, UInt32 inK,
                                                   UInt64 inIndexBase, void* outKeys, void* inStream);
+/* Where a match lies.  LBAudioDetectiveFingerprintCompareToFingerprint (Fp.m:119-149) slides the shorter fingerprint along
+ * the longer one; the corpus passes the query as its first argument.  Entry longer than the query ("A"): the query slides
+ * along the entry.  Otherwise ("B", equal lengths included): the entry slides along the query.  With n1 >= n2 the two counts,
+ * offset o = 0 .. n1 - n2 scores q_o = (float32 sum over i = 0 .. n2 - 1, in that order, of the sub-fingerprint ratio of
+ * the longer side's i + o against the shorter side's i) / n2, correctly rounded.  The entry's score is max(0, max q_o), bit
+ * for bit what LBAudioDetectiveCorpusScoresDevice returns for it, and its offset the LOWEST o that reaches it.  The LAG is
+ * signed: +offset in A (the query's sub-fingerprint 0 lines up with the entry's sub-fingerprint lag), -offset in B (the
+ * entry's sub-fingerprint 0 lines up with the query's sub-fingerprint -lag); 0 for equal lengths.  Unused result slots
+ * (index -1, a zero key) get lag 0.  One sub-fingerprint is one frame of 128 analysis windows, so for the PCM entry points
+ * lag x 128 x analysis stride / processing sample rate is the position in seconds (5512 Hz, stride 64: 1.486 s per
+ * sub-fingerprint); the file entry points advance by their own hop (LBAudioDetectiveSetFileHopMode) instead of the stride.
+ *
+ * Alignment runs after selection, on the (query, entry) pairs the top-1 / top-K paths produce; the scans are the same.
+ * Arguments are checked as for the top-K calls: queries of the corpus' sub-fingerprint length, inCount >= 1,
+ * 1 <= inK <= LBAD_TOPK_MAX, inIndexBase + entries <= 2^32; NULL handles and pointers are kLBAudioDetectiveArgumentInvalid,
+ * and without a device every call returns kLBAudioDetectiveDeviceUnavailable.  The corpus owns the scratch, grown on demand;
+ * a call waits for the previous alignment's device work before it reuses it.
+ *
+ * AlignKeysDevice: inCount x inK keys at the device pointer inKeys (rows as QueryBatchTopKKeysDevice writes them, query q's
+ * row at q * inK, index = inIndexBase + entry) -> inCount x inK SInt32 lags at the device pointer outLags and, unless outScores
+ * is NULL, the recomputed Float32 scores (equal to the keys' scores, bit for bit).  A key that is zero or names an index
+ * outside [inIndexBase, inIndexBase + entries) gets lag 0 and score 0.  Asynchronous on inStream, no host round trip: the
+ * building block of a sharded top-K, where every rank aligns its own keys before the merge.
+ * QueryBatchTopKAligned: LBAudioDetectiveCorpusQueryBatchTopK's indices, scores and counts, bit for bit, plus the lags.
+ * QueryAligned: LBAudioDetectiveCorpusQuery's index and score (bound pruning on or off) plus the winner's lag.
+ * MatchProfile: every q_o of the query against entry inEntry, in offset order, to the host array outScores; *outCount =
+ * n1 - n2 + 1.  Slot o's lag is *outFirstLag + o in A and *outFirstLag - o in B (*outFirstLag is 0), and the profile's maximum
+ * is the entry's score.  A capacity below the count returns kLBAudioDetectiveArgumentInvalid with *outCount set (outScores may
+ * then be NULL): the caller sizes the buffer and calls again. */
+OSStatus LBAudioDetectiveCorpusAlignKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const LBAudioDetectiveFingerprintRef* inQueries,
+                                               UInt32 inCount, UInt32 inRange, UInt32 inK, const void* inKeys, UInt64 inIndexBase,
+                                               void* outLags, void* outScores, void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryBatchTopKAligned(LBAudioDetectiveCorpusRef inCorpus,
+                                                     const LBAudioDetectiveFingerprintRef* inQueries, UInt32 inCount,
+                                                     UInt32 inRange, UInt32 inK, SInt64* outIndices, Float32* outScores,
+                                                     SInt32* outLags, UInt32* outCounts);
+OSStatus LBAudioDetectiveCorpusQueryAligned(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                            UInt32 inRange, SInt64* outIndex, Float32* outScore, SInt32* outLag);
+OSStatus LBAudioDetectiveCorpusMatchProfile(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                            UInt32 inRange, UInt64 inEntry, Float32* outScores, UInt64 inCapacity,
+                                            UInt64* outCount, SInt32* outFirstLag);
 /* Binary corpus file ("LBADCRP1" header + the stored entries' planes; a ragged corpus: "LBADCRP2" header + the
  * entries' sub-fingerprint counts + the records); Load recognises both, reserves max(inCapacity, stored count)
  * entries and, for a ragged corpus, records in proportion. */

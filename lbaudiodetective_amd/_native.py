@@ -170,6 +170,10 @@ _SIGNATURES = {
     "LBAudioDetectiveCorpusQueryBatchTopK": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, _P(SInt64), _P(Float32), _P(UInt32)]),
     "LBAudioDetectiveCorpusQueryBatchTopKKeysDevice": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, UInt64, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveTopKKeysFromScoresDevice": (OSStatus, [C.c_void_p, UInt64, UInt32, UInt32, UInt64, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusAlignKeysDevice": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, C.c_void_p, UInt64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusQueryBatchTopKAligned": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, _P(SInt64), _P(Float32), _P(SInt32), _P(UInt32)]),
+    "LBAudioDetectiveCorpusQueryAligned": (OSStatus, [Ref, Ref, UInt32, _P(SInt64), _P(Float32), _P(SInt32)]),
+    "LBAudioDetectiveCorpusMatchProfile": (OSStatus, [Ref, Ref, UInt32, UInt64, _P(Float32), UInt64, _P(UInt64), _P(SInt32)]),
     "LBAudioDetectiveCorpusSetKernelVariant": (OSStatus, [Ref, UInt32]),
     "LBAudioDetectiveCorpusSave": (OSStatus, [Ref, C.c_char_p]),
     "LBAudioDetectiveCorpusLoad": (Ref, [C.c_char_p, UInt64]),

@@ -666,6 +666,65 @@ class Corpus:
                "CorpusQueryBatchTopKKeysDevice")
         return keys_out
 
+    # ---- where a match lies (LBAudioDetectiveCorpusQueryAligned and kin): lag > 0, the query's sub-fingerprint 0 lines up
+    # with the entry's sub-fingerprint lag (the entry is the longer one); lag < 0, the entry's sub-fingerprint 0 lines up with
+    # the query's sub-fingerprint -lag; 0 for equal lengths and for empty slots.  Positions in seconds: lag x 128 x analysis
+    # stride / processing sample rate (PCM entry points).
+    def query_aligned(self, fp: Fingerprint, range_: int = 0):
+        """query()'s (index, score), bit for bit, plus the winner's lag."""
+        idx, score, lag = N.SInt64(-1), N.Float32(0.0), N.SInt32(0)
+        _check(self._L.LBAudioDetectiveCorpusQueryAligned(self._ref, fp._ref, range_, C.byref(idx), C.byref(score), C.byref(lag)),
+               "CorpusQueryAligned")
+        return int(idx.value), float(score.value), int(lag.value)
+
+    def query_topk_aligned(self, fp: Fingerprint, k: int, range_: int = 0):
+        """query_topk()'s (indices, scores) plus every match's lag (int32)."""
+        return self.query_batch_topk_aligned([fp], k, range_)[0]
+
+    def query_batch_topk_aligned(self, fps, k: int, range_: int = 0):
+        """query_batch_topk() with lags -> list of (indices, scores, lags); indices and scores are query_batch_topk's."""
+        n = len(fps)
+        refs = (N.Ref * max(1, n))(*[f._ref for f in fps])
+        idx = np.full((max(1, n), max(1, k)), -1, dtype=np.int64)
+        sc = np.zeros((max(1, n), max(1, k)), dtype=np.float32)
+        lag = np.zeros((max(1, n), max(1, k)), dtype=np.int32)
+        cnt = np.zeros(max(1, n), dtype=np.uint32)
+        _check(self._L.LBAudioDetectiveCorpusQueryBatchTopKAligned(self._ref, refs, n, range_, k,
+                                                                   idx.ctypes.data_as(C.POINTER(N.SInt64)),
+                                                                   sc.ctypes.data_as(C.POINTER(N.Float32)),
+                                                                   lag.ctypes.data_as(C.POINTER(N.SInt32)),
+                                                                   cnt.ctypes.data_as(C.POINTER(N.UInt32))), "CorpusQueryBatchTopKAligned")
+        return [(idx[i, :cnt[i]].copy(), sc[i, :cnt[i]].copy(), lag[i, :cnt[i]].copy()) for i in range(n)]
+
+    def align_keys_device(self, fps, keys, k: int, index_base: int = 0, stream=None, want_scores: bool = False, range_: int = 0):
+        """LBAudioDetectiveCorpusAlignKeysDevice: the lags of len(fps) x k keys (torch int64 on the device, rows as
+        query_batch_topk_keys_device writes them) -> torch int32 [len(fps), k] on the device, asynchronously on `stream`; with
+        want_scores also the recomputed float32 scores.  Zero keys and indices outside this corpus get lag 0 and score 0."""
+        import torch
+        n = len(fps)
+        if keys.numel() < n * k or not keys.is_contiguous() or keys.dtype != torch.int64:
+            raise ValueError("keys must be a contiguous int64 tensor of at least len(fps) * k keys")
+        refs = (N.Ref * max(1, n))(*[f._ref for f in fps])
+        lags = torch.empty((max(1, n), k), dtype=torch.int32, device=keys.device)
+        scores = torch.empty((max(1, n), k), dtype=torch.float32, device=keys.device) if want_scores else None
+        _check(self._L.LBAudioDetectiveCorpusAlignKeysDevice(self._ref, refs, n, range_, k, keys.data_ptr(), index_base,
+                                                             lags.data_ptr(), scores.data_ptr() if want_scores else None,
+                                                             _stream_ptr(stream)), "CorpusAlignKeysDevice")
+        return (lags, scores) if want_scores else lags
+
+    def match_profile(self, fp: Fingerprint, entry: int, range_: int = 0):
+        """Every offset's score of fp against entry `entry` (LBAudioDetectiveCorpusMatchProfile) -> (float32 array, first_lag):
+        slot o lies at lag first_lag + o when the entry is longer than the query, first_lag - o otherwise; the maximum is the
+        entry's score."""
+        count, first = N.UInt64(0), N.SInt32(0)
+        st = self._L.LBAudioDetectiveCorpusMatchProfile(self._ref, fp._ref, range_, entry, None, 0, C.byref(count), C.byref(first))
+        if count.value == 0:                  # (a capacity of 0 is too small for any pair: only a refused call leaves it 0)
+            _check(st, "CorpusMatchProfile")
+        out = np.zeros(count.value, dtype=np.float32)
+        _check(self._L.LBAudioDetectiveCorpusMatchProfile(self._ref, fp._ref, range_, entry, out.ctypes.data_as(C.POINTER(N.Float32)),
+                                                          out.size, C.byref(count), C.byref(first)), "CorpusMatchProfile")
+        return out, int(first.value)
+
     @staticmethod
     def decode_key(key: int):
         idx, score = N.SInt64(-1), N.Float32(0.0)

@@ -444,6 +444,11 @@ void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
     if (c->h_topk_q) (void)hipHostFree(c->h_topk_q);
     if (c->d_topk_scan_keys) (void)hipFree(c->d_topk_scan_keys);
     if (c->d_topk_keys) (void)hipFree(c->d_topk_keys);
+    if (c->align_ev) { (void)hipEventSynchronize(c->align_ev); (void)hipEventDestroy(c->align_ev); }
+    if (c->d_align_q) (void)hipFree(c->d_align_q);
+    if (c->h_align_q) (void)hipHostFree(c->h_align_q);
+    if (c->d_align_best) (void)hipFree(c->d_align_best);
+    if (c->d_align_out) (void)hipFree(c->d_align_out);
     if (c->d_fast_key) (void)hipFree(c->d_fast_key);
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->stream) (void)hipStreamDestroy(c->stream);

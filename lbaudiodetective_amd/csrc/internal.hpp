@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <new>
@@ -273,6 +274,30 @@ size_t topk_scratch_bytes(uint32_t rows);
 hipError_t launch_topk_keys(const float* d_scores, uint64_t n, uint32_t rows, uint32_t k, uint64_t index_base, void* d_scratch,
                             unsigned long long* d_keys, hipStream_t stream);
 
+// alignment (k_align.hip): the best sliding offset of (query, entry) pairs, after selection.  A corpus as its kernels read it:
+struct AlignSource {
+    bool ragged = false;
+    const uint4* recs = nullptr;        // ragged: the records and the entries' record positions
+    const uint32_t* off = nullptr;
+    const uint4* planes = nullptr;      // uniform: the planes, plane stride `stride`
+    uint64_t stride = 0, count = 0;
+    uint32_t n_sub = 0, subfp_len = 0;
+    uint32_t range = 0;                 // >= 1 (0 resolved by the caller)
+};
+// a query's sub-fingerprints as the kernels read them (8 words each), appended to out
+void build_align_query(const struct ::LBAudioDetectiveFingerprint* q, bool ragged, std::vector<uint32_t>& out);
+// workgroups that share one pair of a keys launch; above 1, d_best must hold pairs words
+uint32_t align_parts(uint64_t pairs, uint64_t max_offsets);
+// n_queries x k keys (query q's row at d_keys + q * k, index = index_base + entry) -> lags (and, d_scores != null, the recomputed
+// scores) in the same places.  d_qwords: build_align_query blocks one after the other; d_qdesc: per query (first
+// sub-fingerprint in d_qwords, count).  max_offsets: a bound of n1 - n2 + 1 over the pairs (spreads long pairs).
+hipError_t launch_align_keys(const AlignSource& src, const uint32_t* d_qwords, const uint2* d_qdesc, uint32_t n_queries, uint32_t k,
+                             const unsigned long long* d_keys, uint64_t index_base, uint64_t max_offsets,
+                             unsigned long long* d_best, int32_t* d_lags, float* d_scores, hipStream_t stream);
+// every q_o of the pair (query of n_query sub-fingerprints at d_qwords, entry), n_offsets = n1 - n2 + 1 floats to d_out
+hipError_t launch_align_profile(const AlignSource& src, const uint32_t* d_qwords, uint32_t n_query, uint64_t entry, uint64_t n_offsets,
+                                float* d_out, hipStream_t stream);
+
 // ragged corpus (k_sliding.hip): a stream of 32-byte sub-fingerprint records, entries of any length back to back
 bool sliding_supported(uint32_t subfp_len);
 uint32_t sliding_query_words(uint32_t n_query);
@@ -512,4 +537,15 @@ struct LBAudioDetectiveCorpus {
     unsigned long long* d_topk_keys = nullptr;
     size_t topk_keys_cap = 0;
     hipEvent_t topk_ev = nullptr;
+    // alignment (api_align.cpp): the staged query words and their table (device + pinned), the per-pair maxima of a split
+    // launch, and the results of the host-returning forms (keys, lags or a profile) on their way back.  Grown on demand; a
+    // call reuses them only after align_ev, recorded behind the previous call's last kernel.
+    uint32_t* d_align_q = nullptr;
+    uint32_t* h_align_q = nullptr;
+    size_t align_q_cap = 0;                      // bytes, and so on below
+    unsigned long long* d_align_best = nullptr;
+    size_t align_best_cap = 0;
+    void* d_align_out = nullptr;
+    size_t align_out_cap = 0;
+    hipEvent_t align_ev = nullptr;
 };

@@ -78,6 +78,30 @@ def gather_topk_keys(local_keys, k: int, group=None):
     return merge_topk_keys(out.view(world, q, kk), k)
 
 
+def merge_topk_aligned(gathered, k: int):
+    """[R, Q, K, 2] int64 (key, lag) pairs of R shards -> ([Q, k] keys, [Q, k] lags): merge_topk_keys' keys in its order, each
+    lag carried with its key (the zero padding, the only keys that repeat, has lag 0)."""
+    import torch
+    r, q, kk, _ = gathered.shape
+    flat = gathered.permute(1, 0, 2, 3).reshape(q, r * kk, 2)
+    order = torch.sort(flat[..., 0], dim=1, descending=True).indices[:, :k]
+    return torch.gather(flat[..., 0], 1, order).contiguous(), torch.gather(flat[..., 1], 1, order).contiguous()
+
+
+def gather_topk_aligned(local_pairs, k: int, group=None):
+    """Collective: this rank's [Q, K, 2] (key, lag) pairs -> the merged ([Q, k] keys, [Q, k] lags) of every rank (one
+    all_gather_into_tensor: keys and lags travel together)."""
+    import torch
+    import torch.distributed as dist
+    if not _collective(group):
+        return merge_topk_aligned(local_pairs.unsqueeze(0), k)
+    world = dist.get_world_size(group)
+    q, kk, two = local_pairs.shape
+    out = torch.empty((world * q, kk, two), dtype=local_pairs.dtype, device=local_pairs.device)
+    dist.all_gather_into_tensor(out, local_pairs.contiguous(), group=group)
+    return merge_topk_aligned(out.view(world, q, kk, two), k)
+
+
 def gather_packed(local_packed, group=None):
     """Optional last step of sharded fingerprinting: every rank contributes its [n_local, count, 32]
     packed sub-fingerprints (160 B per one-second clip) and receives all of them in rank order.  Ranks
@@ -187,6 +211,23 @@ class ShardedCorpus:
         self.local.query_batch_topk_keys_device(fps, k, keys, range_, index_base=self.begin)
         merged = gather_topk_keys(keys, k, self.group).cpu()
         return [decode_topk_keys(row) for row in merged]
+
+    def query_topk_aligned(self, fps, k: int, range_: int = 0):
+        """Collective: query_topk with the lag of every match -> list of (global indices, scores, lags).  Each rank aligns
+        its own keys on the device (index_base = its first global index) before the exchange; keys and lags then travel as one
+        [Q, k, 2] all-gather and merge together."""
+        import numpy as np
+        import torch
+        from .api import decode_topk_keys
+        keys = torch.zeros((len(fps), k), dtype=torch.int64, device="cuda")
+        self.local.query_batch_topk_keys_device(fps, k, keys, range_, index_base=self.begin)
+        lags = self.local.align_keys_device(fps, keys, k, index_base=self.begin, range_=range_)
+        merged, merged_lags = gather_topk_aligned(torch.stack([keys, lags.to(torch.int64)], dim=2), k, self.group)
+        out = []
+        for row, lrow in zip(merged.cpu(), merged_lags.cpu()):
+            idx, sc = decode_topk_keys(row)
+            out.append((idx, sc, lrow[: len(idx)].numpy().astype(np.int32)))
+        return out
 
     def query(self, fp, range_: int = 0, key_out=None):
         """Collective: every rank calls it with the same query; returns (global index, score)."""

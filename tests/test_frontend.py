@@ -6,6 +6,8 @@ import struct
 import numpy as np
 import pytest
 
+import frontend_paths as fp
+
 BIRDS = os.path.join(os.path.dirname(__file__), "golden", "birds")
 
 _STEP = [7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97,
@@ -86,6 +88,71 @@ def test_host_front_end_equals_the_independent_oracle_on_every_fixture(lb, oracl
     for rate_out, mode in ((48000.0, 0), (8000.0, 1), (96000.0, 2), (44100.0, 0)):       # interpolating, copy
         y, _ = lb.read_audio_url(os.path.join(BIRDS, "Crow.caf"), rate_out, mode)
         assert np.array_equal(y, oracle.resample(x[:], 44100.0, rate_out, mode)), (rate_out, mode)
+
+
+def test_host_converter_equals_the_oracle_on_the_double_position_pairs(lb, oracle, tmp_path):
+    """The host converter's `!ph` loop (position n * ratio in double: fractional rates, large q) is the device kernel's
+    stated model; here it is compared with the oracle on every double-position pair of the converter grid, on the bit
+    patterns of every sample, short synthetic float32 CAF files, the three models, and the edge lengths of the pairs
+    that have them."""
+    p = str(tmp_path / "x.caf")
+    pairs = [(ri, ro) for ri, ro, _, _ in fp.GRID if fp.is_double_position(ri, ro, 0)]
+    assert len(pairs) == 13 and (44100.0, 5512.5) in pairs and (22254.54545, 5512.0) in pairs
+    for k, (rate_in, rate_out) in enumerate(pairs):
+        lengths = [fp.grid_frames(rate_in, rate_out, 1500)]
+        if (rate_in, rate_out) in fp.EDGE_PAIRS:
+            lengths += fp.edge_frames(rate_in, rate_out, 0) + fp.edge_frames(rate_in, rate_out, 1)
+        for n_in in sorted(set(lengths)):
+            x = fp.signal(n_in, 100 + k)[:, 0].astype(np.float32)
+            fp.write_f32_caf(p, rate_in, x)
+            dec, rate = oracle.decode_audio_file(p)
+            assert rate == rate_in
+            fp.assert_same_bits(dec, x, f"decode {rate_in} {n_in}")
+            for mode in (0, 1, 2):
+                y, yrate = lb.read_audio_url(p, rate_out, mode)
+                assert yrate == rate_out and y.size == fp.output_count(n_in, rate_in, rate_out)
+                fp.assert_same_bits(y, oracle.resample(x, rate_in, rate_out, mode), f"{rate_in} -> {rate_out} mode {mode} frames {n_in}")
+
+
+def test_branch_model_constants_come_from_the_sources():
+    """The model's constants are the kernel's (read with regular expressions, not repeated): the values below are what
+    the table in DESIGN.md section 2 was written for; a change of one of them must be followed by a look at the grid."""
+    assert {k: fp.K[k] for k in ("kThreads", "kRowLen", "kTapGroup", "kInMax", "kInMaxR", "kPeriods")} == \
+        dict(kThreads=256, kRowLen=64, kTapGroup=48, kInMax=3072, kInMaxR=2816, kPeriods=3)
+    assert fp.K["q_max"] == 16384 and fp.K["p_max"] == 1 << 24 and fp.K["res"] == 2048 and fp.K["zero_crossings"] == (24, 4)
+    # the table of phases as audiofile.cpp builds it: 44.1 kHz -> 5512 Hz has 1378 phases of (at most) 386 taps
+    assert fp.phase_table(44100.0, 5512.0, 0) == (11025, 1378, -192, 386)
+    assert fp.phase_table(44100.0, 5512.5, 0) is None and fp.phase_table(22254.54545, 5512.0, 0) is None
+    assert fp.phase_table(44100.0, 22051.0, 0) is None                       # whole rates, q = 22051 > 16384
+    assert fp.phase_table(48000.0, 16385.0, 0)[1] == 3277
+
+
+@pytest.mark.parametrize("row", range(len(fp.GRID)))
+def test_every_grid_case_takes_the_path_it_is_there_for(row):
+    rate_in, rate_out, want, kind = fp.GRID[row]
+    n_in = fp.grid_frames(rate_in, rate_out)
+    for mode, paths in want.items():
+        got = fp.converter_paths(rate_in, rate_out, mode, n_in)
+        assert got.info["n_out"] >= 5000 and got.info["n_out"] % 256 not in (0, 1)
+        assert (set(got) == paths) if kind == "only" else (paths <= set(got)), (rate_in, rate_out, mode, dict(got))
+    if fp.GRID[row][2][0] == {"rational-staged", "rational-q1"}:             # more slots than blocks: the slot loop strides
+        got = fp.converter_paths(rate_in, rate_out, 0, n_in)
+        assert got.info["slots"] > got.info["blocks"]
+
+
+def test_the_grid_reaches_every_converter_path():
+    seen, partial = set(), set()
+    for rate_in, rate_out, want, _ in fp.GRID:
+        for mode in want:
+            got = fp.converter_paths(rate_in, rate_out, mode, fp.grid_frames(rate_in, rate_out))
+            seen |= set(got)
+            if "last_group_periods" in got.info:
+                partial.add(got.info["last_group_periods"])
+    assert seen == set(fp.PATHS)
+    for rate_in, rate_out in fp.EDGE_PAIRS:                                  # the edge lengths add the partly filled period groups
+        for n_in in fp.edge_frames(rate_in, rate_out, 0):
+            partial.add(fp.converter_paths(rate_in, rate_out, 0, n_in).info.get("last_group_periods"))
+    assert {1, 2, 3} <= partial
 
 
 def test_oracle_file_reader_on_assorted_containers(lb, oracle, tmp_path):

@@ -8,6 +8,8 @@ import struct
 import numpy as np
 import pytest
 
+from frontend_paths import assert_same_bits
+
 pytestmark = pytest.mark.gpu
 
 BIRDS = os.path.join(os.path.dirname(__file__), "golden", "birds")
@@ -27,13 +29,13 @@ def test_device_front_end_equals_oracle_on_every_fixture(lb, gpu, oracle):
             det.set_resampler_mode(mode)
             got, file_frames, file_rate = det.convert_audio_url(p)
             assert file_frames == x.size and file_rate == rate
-            assert np.array_equal(got, oracle.resample(x, rate, 5512.0, mode)), (p, mode)
+            assert_same_bits(got, oracle.resample(x, rate, 5512.0, mode), (p, mode))     # bit patterns: -0.0 is not +0.0
     det.set_resampler_mode(0)
     d2 = lb.Detective().configure(sample_rate=44100)          # equal rates: the decoded samples themselves
     x, _ = oracle.decode_audio_file(_all_birds()[3])
-    assert np.array_equal(d2.convert_audio_url(_all_birds()[3])[0], x)
+    assert_same_bits(d2.convert_audio_url(_all_birds()[3])[0], x, "equal rates")
     d3 = lb.Detective().configure(sample_rate=48000)          # interpolating
-    assert np.array_equal(d3.convert_audio_url(_all_birds()[3])[0], oracle.resample(x, 44100.0, 48000.0, 0))
+    assert_same_bits(d3.convert_audio_url(_all_birds()[3])[0], oracle.resample(x, 44100.0, 48000.0, 0), "44100 -> 48000")
 
 
 def test_ima4_payload_at_an_odd_file_offset_and_stereo(lb, gpu, oracle, tmp_path):
@@ -69,10 +71,10 @@ def test_ima4_payload_at_an_odd_file_offset_and_stereo(lb, gpu, oracle, tmp_path
         open(path, "wb").write(build(pad, stereo))
         x, rate = oracle.decode_audio_file(path)
         d44 = lb.Detective().configure(sample_rate=rate)
-        assert np.array_equal(d44.convert_audio_url(path)[0], x), name            # the decoded samples themselves
+        assert_same_bits(d44.convert_audio_url(path)[0], x, name)                 # the decoded samples themselves
         got, frames, frate = det.convert_audio_url(path)
         assert frames == x.size and frate == rate
-        assert np.array_equal(got, oracle.resample(x, rate, 5512.0, 0)), name
+        assert_same_bits(got, oracle.resample(x, rate, 5512.0, 0), name)
         assert np.array_equal(det.process_audio_url(path).to_bools(), oracle.fingerprint_file(path, oracle.Config(), 1, 1, 0)), name
 
 

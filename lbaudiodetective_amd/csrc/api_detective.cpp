@@ -1,6 +1,7 @@
 // api_detective.cpp -- LBAudioDetective* driver: configuration, PCM/file entry points and the
 // batch hot path.  Mirrors LBAudioDetective/LBAudioDetective.m; line cites refer to it.
 #include "internal.hpp"
+#include "const_div.hpp"
 
 #include <new>
 #include "audiofile.hpp"
@@ -87,8 +88,9 @@ OSStatus ensure_plan(LBAudioDetective* d) {
     // [bands] lo, [bands] hi, [bands] divisor as float bits; then where the band's mean of row w goes inside a frame, as
     // multiplier and offset (w * mult + off): for rows of `bands` floats, and for the compact frame of plan.sparse
     // (off 0xFFFFFFFF: not stored); then the first word of the band's power terms in LDS (BandTable::term_at) and, one word,
-    // the end of the last band's
-    std::vector<uint32_t> tbl(8 * (size_t)p.bands + 1);
+    // the end of the last band's; then, from word 9 * bands on, RN(1 / divisor) and whether the short division of
+    // const_div.hpp is proven for the divisor (zero, non-integer and unchecked divisors are not)
+    std::vector<uint32_t> tbl(11 * (size_t)p.bands);
     for (uint32_t b = 0; b < p.bands; ++b) {
         tbl[b] = p.table.lo[b];
         tbl[p.bands + b] = p.table.hi[b];
@@ -104,6 +106,9 @@ OSStatus ensure_plan(LBAudioDetective* d) {
         tbl[5 * p.bands + b] = mult;
         tbl[6 * p.bands + b] = off;
         tbl[7 * p.bands + b] = p.table.term_at[b];
+        const float rcp = 1.0f / div;
+        std::memcpy(&tbl[9 * p.bands + b], &rcp, 4);
+        tbl[10 * p.bands + b] = band_div_proven(div) ? 1u : 0u;
     }
     tbl[8 * (size_t)p.bands] = p.table.term_end;
     LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&p.d_bands), tbl.size() * sizeof(uint32_t)));

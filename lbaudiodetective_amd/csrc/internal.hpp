@@ -91,7 +91,7 @@ struct Plan {
     BandTable table;
     // device copies
     float* d_tw = nullptr;        // [W/2] re then [W/2] im
-    uint32_t* d_bands = nullptr;  // [bands] lo, [bands] hi, [bands] divisor as float bits, ... (api_detective.cpp: eight rows + 1 word)
+    uint32_t* d_bands = nullptr;  // [bands] lo, [bands] hi, [bands] divisor as float bits, ... (api_detective.cpp: eight rows + 1 word, then RN(1 / divisor) and "short division proven" from word 9 * bands)
     float* d_bin_const = nullptr; // per-bin twiddles of the pruned kernel (only when pruned_ok)
     bool pruned_ok = false;
     bool full_ok = false;         // k_rows_full.hip applies

@@ -17,6 +17,7 @@
 // Every arithmetic operation is the reference's: x / sqrtf(n) pre-scale, (a +- b) / sqrtf(2)
 // butterflies, correctly rounded divisions.
 #include "internal.hpp"
+#include "const_div.hpp"
 
 #include <type_traits>
 
@@ -26,40 +27,8 @@ namespace {
 constexpr uint32_t kCand = 128;     // candidates ranked exhaustively
 constexpr int kChunkDw = 20;        // 16 floats + 4 pad: conflict-free ds_read_b128 across lanes
 
-// x / d for the Haar's three constant divisors without the ~11-instruction IEEE division sequence:
-//     q0 = x * r;  e = fma(-d, q0, x);  q = fma(e, r, q0)        with r = RN(1 / d).
-// tools/verify_const_div.c checks ALL 2^32 inputs for d = sqrtf(2), sqrtf(32), sqrtf(128): q equals the
-// correctly rounded quotient bit for bit whenever 2^-105 <= |x| < inf (and for +0; -0 gives +0, which
-// no later step can tell apart).  The guard records what a line met and the caller redoes the whole
-// line with true divisions when a lane saw anything else:
-//   * every dividend: min over t = 2 |x|bits - 1 (one shift-add per value, one min3 per pair); zero wraps
-//     to 0xFFFFFFFF and never trips it, anything in (0, 2^-100) does;
-//   * the 16 values a line starts from: max over |x|bits <= 2^126.  Later dividends are sums and
-//     differences of quotients, at most 4x the largest input after four levels, so they stay finite.
-constexpr uint32_t kFastDivLo = 0x0D800000u;   // 2^-100
-constexpr uint32_t kFastDivHi = 0x7E800000u;   // 2^126
-
-struct DivGuard {
-    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-    __device__ __forceinline__ void dividends(float a, float b) {
-        lo = min(lo, min((__float_as_uint(a) << 1) - 1u, (__float_as_uint(b) << 1) - 1u));
-    }
-    __device__ __forceinline__ void inputs(float a, float b) {
-        hi = max(hi, max(__float_as_uint(a) & 0x7fffffffu, __float_as_uint(b) & 0x7fffffffu));
-    }
-    __device__ __forceinline__ bool bad() const { return lo < 2u * kFastDivLo - 1u || hi > kFastDivHi; }
-};
-
-template <bool FAST>
-__device__ __forceinline__ float div_c(float x, float d, float r) {
-    if constexpr (FAST) {
-        const float q0 = __fmul_rn(x, r);
-        const float e = __fmaf_rn(-d, q0, x);
-        return __fmaf_rn(e, r, q0);
-    } else {
-        return __fdiv_rn(x, d);
-    }
-}
+// x / d for the Haar's three constant divisors goes through the short form of const_div.hpp (div_c) behind DivGuard: the
+// caller redoes a whole line with true divisions when a lane saw a dividend outside the proven range.
 
 constexpr uint32_t kHistBuckets = 2048;   // |v| bits >> 20
 

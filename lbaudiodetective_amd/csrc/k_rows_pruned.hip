@@ -17,10 +17,15 @@
 //     (two per CU) claim frames from per-XCD counters and refill the span buffer with
 //     global_load_lds behind the arithmetic of the current unit (see frame_rows_pruned_kernel).
 //
-// Executed work per window: ~10.3 k float operations instead of 25.6 k for the full transform;
-// results are bit-identical because every surviving butterfly is evaluated exactly as in the
-// full network.
+// Executed work, counted in the compiled main loop (one quarter frame per iteration; tests/test_isa_rows_pruned.py
+// pins the butterflies): 739 vector instructions per wave on the fast path, 629 of them the packed butterflies
+// (498 v_pk_fma_f32, 131 v_pk_add_f32), which is 2321 float operations per lane (an FMA = 2) or 18.6 k per window,
+// instead of 25.6 k for the full transform and with every slot of a packed instruction counted; results are
+// bit-identical because every surviving butterfly is evaluated exactly as in the full network.  The band means
+// divide by a per-band constant: three instructions per quotient behind a guard (const_div.hpp), the IEEE
+// sequence only in the waves whose guard trips.
 #include "internal.hpp"
+#include "const_div.hpp"
 #include "fft64_lane.hpp"
 
 namespace lbad {
@@ -43,7 +48,8 @@ constexpr int kTDw = kWaves * 8 * kWinDw;                 // per wave: 8 windows
 constexpr int kBinConst = 14;       // per-bin twiddle block, see rows_pruned_constants()
 constexpr int kConstStride = 20;    // 14 floats per bin padded to 80 B: lanes with different bins hit different banks
 constexpr int kConstDw = kBins * kConstStride;
-constexpr int kClaimOffset = 312;   // plan.d_bin_const: 308 constants, padding, then 8 claim counters (one per XCD)
+constexpr int kClaimOffset = 312;   // plan.d_bin_const: 308 constants, padding, then 8 claim counters (one per XCD) and the exit ticket
+constexpr int kClaimWords = 16;     // counters [0..7], ticket [8], padding
 constexpr int kLdsBytes = (kSpanDw + kTDw + kConstDw + 4) * 4;   // 75 856 B: two workgroups per CU
 constexpr int kWgPerCu = 2;
 static_assert(kWgPerCu * kLdsBytes <= 160 * 1024, "two workgroups must fit one CU's LDS");
@@ -152,15 +158,31 @@ template <int FMT>
 __device__ __forceinline__ void span_to_lds(const void* __restrict__ pcm_raw, uint64_t first, float* span, int wave,
                                             int lane) {
     if constexpr (FMT == 0) {
-        // `wave` is wave-uniform (an SGPR): chunk c = wave + 4 i, fully unrolled, LDS base through M0
-        const float* src = static_cast<const float*>(pcm_raw) + first + lane + 64 * wave;
-        float* dst = span + 80 * wave;
+        // `wave` is wave-uniform (an SGPR): chunk c = wave + 4 i, fully unrolled, LDS base through M0.  The chunks of a
+        // wave are 1024 B apart in HBM.  Four of them share one address and differ in the instruction's immediate
+        // offset, which the hardware adds on BOTH sides, so the LDS base gives it back; the address itself is a
+        // scalar base (the wave's first sample) plus one 32-bit lane offset, so that stepping it is scalar work too.
+        // The LDS bases are re-derived from `lbase` at every call (the empty asm hides that they never change):
+        // eleven loop-invariant scalars are more than the scalar file has left, they were spilled to vector lanes.
+        const uint64_t first_w = first + 64 * wave;
+        const uint64_t first_s = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(first_w >> 32)) << 32) |
+                                 (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)first_w);
+        const char* src = static_cast<const char*>(pcm_raw) + 4 * first_s;
+        const uint32_t lane_off = 4u * (uint32_t)lane;
+        uint32_t lbase = (uint32_t)(size_t)(lvoid_t*)(span + 80 * wave);
+        int tail_wave = wave;                             // likewise: no 64-bit mask of "wave < 3" kept over the loop
+        asm volatile("" : "+s"(lbase), "+s"(tail_wave));
         constexpr int kFull = (kSpan / 64) / kWaves;      // 47 chunks: 11 rounds of 4, then waves 0..2
-#pragma unroll
-        for (int i = 0; i < kFull; ++i)
-            __builtin_amdgcn_global_load_lds((gvoid_t*)(src + 64 * kWaves * i), (lvoid_t*)(dst + 80 * kWaves * i), 4, 0, 0);
-        if (wave < kSpan / 64 - kFull * kWaves)
-            __builtin_amdgcn_global_load_lds((gvoid_t*)(src + 64 * kWaves * kFull), (lvoid_t*)(dst + 80 * kWaves * kFull), 4, 0, 0);
+        static_assert(kFull == 11, "three groups of four loads");
+#define LBAD_SPAN_LOAD(I)                                                                                            \
+    __builtin_amdgcn_global_load_lds((gvoid_t*)(src + 4 * 64 * kWaves * ((I) & ~3) + lane_off),                      \
+                                     (lvoid_t*)(size_t)(lbase + 4 * (80 * kWaves * (I) - 64 * kWaves * ((I) & 3))),  \
+                                     4, 4 * 64 * kWaves * ((I) & 3), 0)
+        LBAD_SPAN_LOAD(0); LBAD_SPAN_LOAD(1); LBAD_SPAN_LOAD(2); LBAD_SPAN_LOAD(3);
+        LBAD_SPAN_LOAD(4); LBAD_SPAN_LOAD(5); LBAD_SPAN_LOAD(6); LBAD_SPAN_LOAD(7);
+        LBAD_SPAN_LOAD(8); LBAD_SPAN_LOAD(9); LBAD_SPAN_LOAD(10);
+        if (tail_wave < kSpan / 64 - kFull * kWaves) LBAD_SPAN_LOAD(11);
+#undef LBAD_SPAN_LOAD
     } else if constexpr (FMT == 1) {
         const int16_t* src = static_cast<const int16_t*>(pcm_raw) + first;
         for (int s = threadIdx.x; s < kSpan; s += kThreads)
@@ -178,6 +200,20 @@ __device__ __forceinline__ void span_to_lds(const void* __restrict__ pcm_raw, ui
 // to 40 % apart).  As soon as every wave holds its points of quarter frame u in registers, the span of
 // the next one streams into the same LDS buffer behind the arithmetic; the claim for the frame after
 // is in flight for three iterations, and the rows of u drain to HBM during u + 1.
+// No memset node in front of a launch: every workgroup takes a ticket when it is done with the counters (its last claim
+// has returned), and the last one leaves the counters and the ticket at zero for the next launch.  Launches that share
+// the counters never overlap: they belong to one plan, whose calls are serialised (StreamOrder orders different
+// streams, a captured graph keeps its stream's order).
+__device__ __forceinline__ void claims_done(uint32_t* claim_ctr) {
+    __threadfence();
+    if (atomicAdd(claim_ctr + 8, 1u) == gridDim.x - 1u) {
+        __threadfence();
+#pragma unroll
+        for (int i = 0; i < 9; ++i) atomicExch(claim_ctr + i, 0u);
+        __threadfence();
+    }
+}
+
 template <int FMT>
 __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(const void* __restrict__ pcm_raw,
                                                                          uint64_t samples_per_clip,
@@ -205,7 +241,10 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
     const uint64_t xcd_begin = (uint64_t)(blockIdx.x & 7) * units_per_xcd;     // units_per_xcd is a multiple of 4
     const uint64_t xcd_end = xcd_begin + units_per_xcd < n_units ? xcd_begin + units_per_xcd : n_units;
     uint64_t unit = xcd_begin + 4 * (uint64_t)(blockIdx.x >> 3);
-    if (unit >= xcd_end) return;
+    if (unit >= xcd_end) {
+        if (threadIdx.x == 0) claims_done(claim_ctr);
+        return;
+    }
 
     auto span_start = [&](uint64_t u) {
         const uint32_t frame = (uint32_t)(u >> 2);          // the launcher keeps unit numbers below 2^31
@@ -213,7 +252,10 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
         const uint32_t fi = frame - clip * frames_per_clip;
         return (uint64_t)clip * samples_per_clip + (uint64_t)(fi * 128 + (uint32_t)(u & 3) * kUnitWindows) * kStride;
     };
+    // the claimer keeps its counter's address in vector registers: the scalar file is full, and as a scalar pair
+    // it was spilled to vector lanes and fetched back at every claim
     uint32_t* my_ctr = claim_ctr + (blockIdx.x & 7);
+    asm volatile("" : "+v"(my_ctr));
     const bool claimer = threadIdx.x == 0;
     uint32_t claimed = 0;
 
@@ -223,6 +265,11 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
     const int band = lane & 31;
     const uint32_t b_lo = band_tbl[band], b_hi = band_tbl[kBands + band];
     const float b_div = __uint_as_float(band_tbl[2 * kBands + band]);
+    // the band's mean is p / b_div.  b_rcp = RN(1 / b_div); a band whose divisor is proven for the short form of
+    // const_div.hpp accepts dividends up to the largest finite float, any other band none (a sum of squares is >= +0,
+    // so its bit pattern orders like its value)
+    const float b_rcp = __uint_as_float(band_tbl[9 * kBands + band]);
+    const int b_fast_hi = band_tbl[10 * kBands + band] ? (int)kBandDivHi : -1;   // compared as bit patterns
     // where the band's mean of row w goes inside a frame of frame_dw floats: w * b_mult + b_off -- rows of 32 bands, or
     // the compact frame of plan.sparse (128 rows of the bands that can be non-zero; b_off = 0xFFFFFFFF: a band that is +0.0
     // in every window and that nobody reads)
@@ -377,8 +424,20 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
             for (int q = 0; q < 4; ++q)
                 if (v[q] == v[q] && fabsf(v[q]) != INFINITY) p[q] = __fadd_rn(p[q], v[q]);
         }
+        // three instructions per quotient where every lane of the wave has a proven divisor and dividends that are +0 or
+        // in [kBandDivLo, kBandDivHi]; otherwise (tiny sums, +inf by overflow, other divisors) the wave divides
+        DivGuard g;
+        g.dividends(p[0], p[1]);
+        g.dividends(p[2], p[3]);
+        const int p_max = max(max((int)__float_as_uint(p[0]), (int)__float_as_uint(p[1])),
+                              max((int)__float_as_uint(p[2]), (int)__float_as_uint(p[3])));
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(g.lo < 2u * kBandDivLo - 1u || p_max > b_fast_hi) == 0, 1)) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) out[q] = __fdiv_rn(p[q], b_div);
+            for (int q = 0; q < 4; ++q) out[q] = div_c<true>(p[q], b_div, b_rcp);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) out[q] = div_c<false>(p[q], b_div, b_rcp);
+        }
         // row = quarter * 32 + 8 * wave + 2 q + (lane >> 5)
         out_ptr = b_off != 0xFFFFFFFFu
                       ? frames + (unit >> 2) * frame_dw + (quarter * kUnitWindows + 8 * wave + (lane >> 5)) * b_mult + b_off
@@ -403,6 +462,7 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
         for (int q = 0; q < 4; ++q) out_ptr[q * 2 * b_mult] = out[q];
     }
 #endif
+    if (claimer) claims_done(claim_ctr);
 }
 
 }  // namespace
@@ -422,7 +482,7 @@ bool rows_pruned_supported(const Plan& p) {
 void rows_pruned_constants(std::vector<float>& out) {
     std::vector<float> re, im;
     make_twiddles(kW, re, im);
-    out.assign((size_t)kClaimOffset + 8, 0.0f);   // constants, padding, claim counters
+    out.assign((size_t)kClaimOffset + kClaimWords, 0.0f);   // constants, padding, claim counters and ticket (zero between launches)
     for (int k = 0; k < kBins; ++k) {
         float* c = &out[(size_t)k * kBinConst];
         // "+" tree of Z[k]: W_128^k, W_256^k, W_512^k
@@ -457,8 +517,6 @@ static hipError_t launch_rows_fmt(const Plan& plan, const float* d_bin_const, co
     uint64_t wg_per_xcd = ((uint64_t)n_cu * kWgPerCu + 7) / 8;
     if (wg_per_xcd > units_per_xcd / 4) wg_per_xcd = units_per_xcd / 4;
     uint32_t* claim = reinterpret_cast<uint32_t*>(const_cast<float*>(d_bin_const)) + kClaimOffset;
-    hipError_t e = hipMemsetAsync(claim, 0, 8 * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(frame_rows_pruned_kernel<FMT>, dim3((uint32_t)(wg_per_xcd * 8)), dim3(kThreads), kLdsBytes,
                        stream, d_pcm, samples_per_clip, frames_per_clip, n_units, units_per_xcd, d_bin_const,
                        plan.d_bands, claim, d_frames, compact ? plan.sparse.frame_dw() : 128u * kBands, compact ? 5u : 3u);

@@ -561,6 +561,46 @@ OSStatus LBAudioDetectiveCorpusQueryAligned(LBAudioDetectiveCorpusRef inCorpus, 
 OSStatus LBAudioDetectiveCorpusMatchProfile(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
                                             UInt32 inRange, UInt64 inEntry, Float32* outScores, UInt64 inCapacity,
                                             UInt64* outCount, SInt32* outFirstLag);
+/* Packed queries: fingerprints that are ALREADY on the device in the packed layout -- what LBAudioDetectiveFingerprintClipsDevice
+ * writes and LBAudioDetectiveCorpusAppendPackedDevice reads -- queried without a handle and without a visit to the host.
+ * inPackedQueries is a device pointer to inCount x inSubfingerprintsPerQuery x LBAD_PACKED_BYTES bytes: query q's
+ * sub-fingerprints one after the other from byte q * inSubfingerprintsPerQuery * LBAD_PACKED_BYTES on, 4-byte alignment
+ * suffices; every query of a call has the same number of sub-fingerprints (several lengths: several calls), and the
+ * sub-fingerprint length is the corpus'.  Bits at or above that length are ignored.  Builder kernels turn the rows into the
+ * blocks the scans read -- bit for bit what the handle-taking calls stage from a fingerprint with the same Booleans -- and the
+ * same scan, selection and alignment kernels run on them, so for both corpus kinds, any inRange (0: the sub-fingerprint
+ * length) and bound pruning on or off:
+ * QueryPackedKeysDevice writes inCount 64-bit keys to the device pointer outKeys, equal to LBAudioDetectiveCorpusQueryBatchKeysDevice's;
+ * QueryPackedTopKKeysDevice writes inCount x inK keys, equal to LBAudioDetectiveCorpusQueryBatchTopKKeysDevice's, and -- unless
+ * outLags is NULL -- inCount x inK SInt32 lags to the device pointer outLags, equal to LBAudioDetectiveCorpusAlignKeysDevice's
+ * on those keys.
+ * Both are asynchronous on inStream; nothing of the queries is copied to the host and the stream is never awaited.  Uniform
+ * corpus: the specialised shape (200 Booleans, as many sub-fingerprints as an entry, at most 8) takes the batch scan, eight
+ * queries per pass, even for one query; other shapes one generic scan per query, whose query must fit 48 KiB.  Ragged corpus:
+ * the queries share launches as in LBAudioDetectiveCorpusQueryBatchKeysDevice.  LBAudioDetectiveCorpusSetKernelVariant means what
+ * it means for the handle-taking calls (2 on a shape without the specialised scan: kLBAudioDetectiveArgumentInvalid).
+ * kLBAudioDetectiveArgumentInvalid: a NULL corpus or pointer (outLags excepted), inCount == 0, inSubfingerprintsPerQuery == 0,
+ * inK outside 1 .. LBAD_TOPK_MAX, inIndexBase + entries > 2^32, inCount x inSubfingerprintsPerQuery > 2^32 - 1, with lags
+ * inSubfingerprintsPerQuery > 0x7FFFFFFF; without a device kLBAudioDetectiveDeviceUnavailable.  An empty corpus gives zero keys
+ * and zero lags.  The corpus owns the builders' output, grown on demand; a call waits for the previous packed call's device
+ * work before it reuses it (and, as the calls it mirrors, for the previous top-K call and alignment). */
+OSStatus LBAudioDetectiveCorpusQueryPackedKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                     UInt32 inCount, UInt32 inSubfingerprintsPerQuery, UInt32 inRange,
+                                                     UInt64 inIndexBase, void* outKeys, void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryPackedTopKKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                         UInt32 inCount, UInt32 inSubfingerprintsPerQuery, UInt32 inRange,
+                                                         UInt32 inK, UInt64 inIndexBase, void* outKeys, void* outLags,
+                                                         void* inStream);
+/* Debug / tests: the query blocks themselves, copied to the host array outWords (*outCount words; a capacity below that, or a
+ * NULL outWords, returns kLBAudioDetectiveArgumentInvalid with *outCount set).  Exactly one source: inPackedQueries (device,
+ * as above; the builder kernels run on the null stream) or inBooleans (host, inCount x inPer x inSubfingerprintLength
+ * Booleans; the builders behind the handle-taking calls, no device needed).  inKind 0: the specialised uniform scan's blocks
+ * (length 200, inPer <= 8 sub-fingerprints per query and entry; 144 words per query); 1: the ragged scan's blocks
+ * ((inPer + 1) x 16 words); 2 / 3: the alignment's words for a ragged / uniform corpus (inPer x 8 words; 3 is also the generic
+ * uniform scan's query). */
+OSStatus LBAudioDetectiveDebugQueryBlocks(UInt32 inKind, const void* inPackedQueries, const Boolean* inBooleans, UInt32 inCount,
+                                          UInt32 inPer, UInt32 inSubfingerprintLength, UInt32 inRange, UInt32* outWords,
+                                          UInt64 inCapacity, UInt64* outCount);
 /* Binary corpus file ("LBADCRP1" header + the stored entries' planes; a ragged corpus: "LBADCRP2" header + the
  * entries' sub-fingerprint counts + the records); Load recognises both, reserves max(inCapacity, stored count)
  * entries and, for a ragged corpus, records in proportion. */

@@ -174,6 +174,11 @@ _SIGNATURES = {
     "LBAudioDetectiveCorpusQueryBatchTopKAligned": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, _P(SInt64), _P(Float32), _P(SInt32), _P(UInt32)]),
     "LBAudioDetectiveCorpusQueryAligned": (OSStatus, [Ref, Ref, UInt32, _P(SInt64), _P(Float32), _P(SInt32)]),
     "LBAudioDetectiveCorpusMatchProfile": (OSStatus, [Ref, Ref, UInt32, UInt64, _P(Float32), UInt64, _P(UInt64), _P(SInt32)]),
+    "LBAudioDetectiveCorpusQueryPackedKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, UInt32, UInt64, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusQueryPackedTopKKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, UInt32, UInt32, UInt64, C.c_void_p,
+                                                                   C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveDebugQueryBlocks": (OSStatus, [UInt32, C.c_void_p, C.c_void_p, UInt32, UInt32, UInt32, UInt32, C.c_void_p, UInt64,
+                                                    _P(UInt64)]),
     "LBAudioDetectiveCorpusSetKernelVariant": (OSStatus, [Ref, UInt32]),
     "LBAudioDetectiveCorpusSave": (OSStatus, [Ref, C.c_char_p]),
     "LBAudioDetectiveCorpusLoad": (Ref, [C.c_char_p, UInt64]),

@@ -666,6 +666,45 @@ class Corpus:
                "CorpusQueryBatchTopKKeysDevice")
         return keys_out
 
+    # ---- packed queries: fingerprints already on the device (what Detective.fingerprint_clips_device writes), no handles and
+    # no host round trip.  `packed`: a torch tensor on the device (uint8 [n, per, 32], or anything contiguous of that size) or
+    # a raw device address; the outputs likewise (a raw address is returned as given).
+    def query_packed_keys_device(self, packed, n_queries: int, per_query: int, keys_out=None, range_: int = 0, index_base: int = 0,
+                                 stream=None):
+        """LBAudioDetectiveCorpusQueryPackedKeysDevice: n_queries 64-bit keys (torch int64 on the device), equal to
+        query_batch_keys_device's for fingerprints with the same Booleans; asynchronous on `stream`."""
+        _packed_ok(packed, n_queries, per_query)
+        if keys_out is None:
+            import torch
+            keys_out = torch.empty(max(1, n_queries), dtype=torch.int64, device=packed.device if hasattr(packed, "device") else "cuda")
+        _out_ok(keys_out, n_queries, "keys_out")
+        _check(self._L.LBAudioDetectiveCorpusQueryPackedKeysDevice(self._ref, _dev_ptr(packed), n_queries, per_query, range_, index_base,
+                                                                  _dev_ptr(keys_out), _stream_ptr(stream)), "CorpusQueryPackedKeysDevice")
+        return keys_out
+
+    def query_packed_topk_keys_device(self, packed, n_queries: int, per_query: int, k: int, keys_out=None, lags_out=None,
+                                      aligned: bool = False, range_: int = 0, index_base: int = 0, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedTopKKeysDevice: n_queries x k keys (torch int64 [n, k] on the device, rows descending,
+        0-padded), equal to query_batch_topk_keys_device's; with aligned=True (or a lags_out) also the n x k int32 lags
+        align_keys_device gives for those keys -> (keys, lags).  Asynchronous on `stream`."""
+        _packed_ok(packed, n_queries, per_query)
+        want_lags = aligned or lags_out is not None
+        if keys_out is None or (want_lags and lags_out is None):
+            import torch
+            dev = packed.device if hasattr(packed, "device") else "cuda"
+            if keys_out is None:
+                keys_out = torch.empty((max(1, n_queries), max(1, k)), dtype=torch.int64, device=dev)
+            if want_lags and lags_out is None:
+                lags_out = torch.empty((max(1, n_queries), max(1, k)), dtype=torch.int32, device=dev)
+        _out_ok(keys_out, n_queries * k, "keys_out")
+        if want_lags:
+            _out_ok(lags_out, n_queries * k, "lags_out")
+        _check(self._L.LBAudioDetectiveCorpusQueryPackedTopKKeysDevice(self._ref, _dev_ptr(packed), n_queries, per_query, range_, k,
+                                                                      index_base, _dev_ptr(keys_out),
+                                                                      _dev_ptr(lags_out) if want_lags else None,
+                                                                      _stream_ptr(stream)), "CorpusQueryPackedTopKKeysDevice")
+        return (keys_out, lags_out) if want_lags else keys_out
+
     # ---- where a match lies (LBAudioDetectiveCorpusQueryAligned and kin): lag > 0, the query's sub-fingerprint 0 lines up
     # with the entry's sub-fingerprint lag (the entry is the longer one); lag < 0, the entry's sub-fingerprint 0 lines up with
     # the query's sub-fingerprint -lag; 0 for equal lengths and for empty slots.  Positions in seconds: lag x 128 x analysis
@@ -730,6 +769,49 @@ class Corpus:
         idx, score = N.SInt64(-1), N.Float32(0.0)
         N.lib().LBAudioDetectiveCorpusDecodeKey(key & 0xFFFFFFFFFFFFFFFF, C.byref(idx), C.byref(score))
         return int(idx.value), float(score.value)
+
+
+def _dev_ptr(x):
+    """device address of a torch tensor, or the raw address itself"""
+    return C.c_void_p(x.data_ptr()) if hasattr(x, "data_ptr") else C.c_void_p(int(x))
+
+
+def _packed_ok(packed, n_queries: int, per_query: int):
+    if hasattr(packed, "data_ptr"):
+        if not packed.is_cuda or not packed.is_contiguous() or packed.numel() * packed.element_size() < n_queries * per_query * N.PACKED_BYTES:
+            raise ValueError("packed must be a contiguous device tensor of at least n_queries * per_query * 32 bytes")
+
+
+def _out_ok(out, n: int, what: str):
+    if hasattr(out, "data_ptr") and (not out.is_cuda or not out.is_contiguous() or out.numel() < n):
+        raise ValueError(f"{what} must be a contiguous device tensor of at least {n} elements")
+
+
+def identify_clips_device(det: "Detective", corpus: "Corpus", clips, k: int = 1, aligned: bool = False, range_: int = 0, stream=None):
+    """Clips on the device -> their k best corpus matches on the device: Detective.fingerprint_clips_device, then
+    Corpus.query_packed_topk_keys_device on its output, on ONE stream with nothing in between (no handle, no copy to the host,
+    no synchronisation).  Returns the [n, k] int64 key tensor (decode rows with decode_topk_keys), and with aligned=True
+    (keys, lags int32 [n, k])."""
+    packed = det.fingerprint_clips_device(clips, stream=stream)
+    n, per = packed.shape[0], packed.shape[1]
+    return corpus.query_packed_topk_keys_device(packed, n, per, k, aligned=aligned, range_=range_, stream=stream)
+
+
+def debug_query_blocks(kind: int, n_queries: int, per_query: int, subfp_len: int, range_: int = 0, packed=None, bools=None) -> np.ndarray:
+    """LBAudioDetectiveDebugQueryBlocks (tests): the query blocks as uint32 [n_queries, words] -- built on the device from
+    `packed` (device tensor or address) or on the host from `bools` ([n_queries, per_query, subfp_len]).  kind 0: specialised
+    uniform scan, 1: ragged scan, 2 / 3: alignment words of a ragged / uniform corpus."""
+    count = N.UInt64(0)
+    b = _u8(bools) if bools is not None else None
+    if b is not None and b.size != n_queries * per_query * subfp_len:
+        raise ValueError("bools must hold n_queries x per_query x subfp_len Booleans")
+    src = (_dev_ptr(packed) if packed is not None else None, b.ctypes.data if b is not None else None)
+    L = N.lib()
+    L.LBAudioDetectiveDebugQueryBlocks(kind, src[0], src[1], n_queries, per_query, subfp_len, range_, None, 0, C.byref(count))
+    out = np.zeros(max(1, count.value), np.uint32)
+    _check(L.LBAudioDetectiveDebugQueryBlocks(kind, src[0], src[1], n_queries, per_query, subfp_len, range_, out.ctypes.data, out.size,
+                                              C.byref(count)), "DebugQueryBlocks")
+    return out[:count.value].reshape(n_queries, -1)
 
 
 class Comm:

@@ -98,6 +98,18 @@ OSStatus stage_queries(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerpr
     return noErr;
 }
 
+// the launch alone: queries whose words and table are on the device, max_off a bound of n1 - n2 + 1 over the pairs
+OSStatus align_launch(LBAudioDetectiveCorpus* c, const uint2* d_desc, const uint32_t* d_words, uint32_t n, uint64_t max_off, uint32_t range,
+                      uint32_t k, const unsigned long long* keys, uint64_t index_base, int32_t* lags, float* scores, hipStream_t stream) {
+    const uint64_t pairs = (uint64_t)n * k;
+    if (align_parts(pairs, max_off) > 1) {
+        OSStatus st = grow(reinterpret_cast<void**>(&c->d_align_best), &c->align_best_cap, pairs * sizeof(unsigned long long));
+        if (st != noErr) return st;
+    }
+    LBAD_HIP(launch_align_keys(source(c, range), d_words, d_desc, n, k, keys, index_base, max_off, c->d_align_best, lags, scores, stream));
+    return noErr;
+}
+
 // lags (and scores) of n x k keys on `stream`; the caller has waited for align_ev and records it afterwards
 OSStatus align_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range, uint32_t k,
                          const unsigned long long* keys, uint64_t index_base, int32_t* lags, float* scores, hipStream_t stream) {
@@ -110,16 +122,22 @@ OSStatus align_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFinger
         const uint64_t m = max_offsets(c, qs[i]->count);
         max_off = m > max_off ? m : max_off;
     }
-    const uint64_t pairs = (uint64_t)n * k;
-    if (align_parts(pairs, max_off) > 1) {
-        st = grow(reinterpret_cast<void**>(&c->d_align_best), &c->align_best_cap, pairs * sizeof(unsigned long long));
-        if (st != noErr) return st;
-    }
-    LBAD_HIP(launch_align_keys(source(c, range), d_words, d_desc, n, k, keys, index_base, max_off, c->d_align_best, lags, scores, stream));
-    return noErr;
+    return align_launch(c, d_desc, d_words, n, max_off, range, k, keys, index_base, lags, scores, stream);
 }
 
 }  // namespace
+
+OSStatus align_keys_built(LBAudioDetectiveCorpus* c, const uint2* d_desc, const uint32_t* d_words, uint32_t n, uint32_t per,
+                          uint32_t range, uint32_t k, const unsigned long long* keys, uint64_t index_base, int32_t* lags,
+                          hipStream_t stream) {
+    if (!c || per == 0 || per > 0x7FFFFFFFu || (c->ragged && c->ne_max > 0x7FFFFFFFu)) return kLBAudioDetectiveArgumentInvalid;
+    OSStatus st = wait_align(c);       // (the per-pair maxima of a split launch are the previous alignment's until then)
+    if (st == noErr) st = align_launch(c, d_desc, d_words, n, max_offsets(c, per), range, k, keys, index_base, lags, nullptr, stream);
+    if (st != noErr) return st;
+    LBAD_HIP(hipEventRecord(c->align_ev, stream));
+    return noErr;
+}
+
 }  // namespace lbad
 
 extern "C" {

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 
 namespace lbad {
 namespace {
@@ -65,21 +66,18 @@ uint32_t ragged_split(const LBAudioDetectiveCorpus* c, uint64_t nq) {
     return slots > 2 * c->n_pos * nq + 20000000ull ? kSlideSplitBelow : 0;     // (+ 10 us of slots: a second launch is not free)
 }
 
-// ONE launch: the n_q queries qs[0..n_q) (all of qs[0]->count sub-fingerprints), their keys to keys + pos[i]
-OSStatus launch_ragged(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, const uint32_t* pos, uint32_t n_q,
-                       uint32_t range, uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
-    const uint32_t nq = qs[0]->count;
-    const size_t block_words = ((size_t)nq + 1u) * 16u;
-    std::vector<uint32_t> block, all;
-    all.reserve(block_words * n_q);
-    for (uint32_t i = 0; i < n_q; ++i) {
-        build_sliding_query(qs[i]->data.data(), nq, c->subfp_len, range, block);
-        all.insert(all.end(), block.begin() + (block.size() - block_words), block.end());      // (without the header)
-    }
+// ONE launch: n_q queries of nq sub-fingerprints, their keys to keys + pos[i].  Their blocks ((nq + 1) * 16 words each, one
+// after the other) come either from the host -- h_blocks: staged through the launch's ring slot, or sent in the kernel's
+// arguments -- or are on the device already -- d_blocks: what a builder of k_query.hip wrote; nothing is staged then and the
+// argument shortcut is never taken.  Either way the launch owns a ring slot's result words and leaves its event behind.
+OSStatus launch_ragged_blocks(LBAudioDetectiveCorpus* c, uint32_t nq, const uint32_t* h_blocks, const uint32_t* d_blocks,
+                              const uint32_t* pos, uint32_t n_q, uint32_t range, uint64_t index_base, float* d_scores,
+                              unsigned long long* keys, hipStream_t stream) {
+    const size_t all_words = ((size_t)nq + 1u) * 16u * n_q;
     const uint32_t b_min = ragged_split(c, nq);
-    const bool in_args = n_q == 1 && nq <= kSlideQueryArgSubs && !sliding_short(nq, c->ne_max) && b_min == 0;   // (the systolic scan reads d_query)
-    const size_t slot_words = (all.size() + 63) & ~(size_t)63;
-    if (c->query_slot_words < slot_words) {               // (re)size the ring: everything that used it must be done
+    const bool in_args = h_blocks && n_q == 1 && nq <= kSlideQueryArgSubs && !sliding_short(nq, c->ne_max) && b_min == 0;   // (the systolic scan reads d_query)
+    const size_t slot_words = (all_words + 63) & ~(size_t)63;
+    if (h_blocks && c->query_slot_words < slot_words) {   // (re)size the ring: everything that used it must be done
         for (hipEvent_t e : c->query_ev)
             if (e) LBAD_HIP(hipEventSynchronize(e));
         c->query_slot_words = 0;
@@ -105,17 +103,24 @@ OSStatus launch_ragged(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerpr
     const uint32_t slot = (uint32_t)(c->query_seq++ % kQuerySlots);
     if (!c->query_ev[slot]) LBAD_HIP(hipEventCreateWithFlags(&c->query_ev[slot], hipEventDisableTiming));
     else LBAD_HIP(hipEventSynchronize(c->query_ev[slot]));
-    uint32_t* h = c->h_query + (size_t)slot * c->query_slot_words;
-    uint32_t* dq = c->d_query + (size_t)slot * c->query_slot_words;
-    std::memcpy(h, all.data(), all.size() * sizeof(uint32_t));
-    if (!in_args) LBAD_HIP(hipMemcpyAsync(dq, h, all.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    const uint32_t* h = nullptr;
+    const uint32_t* dq = d_blocks;
+    if (h_blocks) {
+        uint32_t* h_slot = c->h_query + (size_t)slot * c->query_slot_words;
+        uint32_t* d_slot = c->d_query + (size_t)slot * c->query_slot_words;
+        std::memcpy(h_slot, h_blocks, all_words * sizeof(uint32_t));
+        if (!in_args) LBAD_HIP(hipMemcpyAsync(d_slot, h_slot, all_words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        h = h_slot;
+        dq = d_slot;
+    }
     if (d_scores) LBAD_HIP(hipMemsetAsync(d_scores, 0, c->count * sizeof(float), stream));
     uint64_t tasks_a = 0, tasks_b = 0;
     ragged_tasks(c, nq, b_min, tasks_a, tasks_b);
     if (tasks_a > 0xFFFFFFFFull || tasks_b > 0xFFFFFFFFull) return kLBAudioDetectiveArgumentInvalid;   // the plan counts in 32 bits
     const SlideShape sh = sliding_shape(tasks_a, tasks_b, n_q);
-    // the plan of this query length: kept while the length and the entries stay (queries of one length are the rule)
-    if (!sliding_short(nq, c->ne_max) && (c->plan_nq != nq || c->plan_count != c->count || c->plan_grid != sh.grid || c->plan_bmin != b_min)) {
+    // the plan of this query length: kept while the length and the entries stay (queries of one length are the rule).  Only
+    // the task kernel reads it: a batch of short queries on compare_short_multi_kernel leaves the plan alone
+    if (sliding_needs_plan(nq, c->ne_max, n_q, tasks_a, d_scores != nullptr) && (c->plan_nq != nq || c->plan_count != c->count || c->plan_grid != sh.grid || c->plan_bmin != b_min)) {
         // scans on other streams may still read the old plan: every scan leaves its slot's event behind, and a slot is
         // reused only after its event -- the eight events cover everything that can still be running
         for (hipEvent_t e : c->query_ev)
@@ -148,6 +153,42 @@ OSStatus launch_ragged(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerpr
     // behind the SCAN, not just the copy: the slot's device half and its result words are the kernel's, and the launch
     // that reuses the slot eight launches later may arrive on another stream
     LBAD_HIP(hipEventRecord(c->query_ev[slot], stream));
+    return noErr;
+}
+
+// ONE launch: the n_q queries qs[0..n_q) (all of qs[0]->count sub-fingerprints), their keys to keys + pos[i]
+OSStatus launch_ragged(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, const uint32_t* pos, uint32_t n_q,
+                       uint32_t range, uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
+    const uint32_t nq = qs[0]->count;
+    const size_t block_words = ((size_t)nq + 1u) * 16u;
+    std::vector<uint32_t> block, all;
+    all.reserve(block_words * n_q);
+    for (uint32_t i = 0; i < n_q; ++i) {
+        build_sliding_query(qs[i]->data.data(), nq, c->subfp_len, range, block);
+        all.insert(all.end(), block.begin() + (block.size() - block_words), block.end());      // (without the header)
+    }
+    return launch_ragged_blocks(c, nq, all.data(), nullptr, pos, n_q, range, index_base, d_scores, keys, stream);
+}
+
+// n queries of `per` sub-fingerprints whose blocks a builder wrote to d_blocks, key i to keys[i] (d_scores: n == 1)
+OSStatus run_built_ragged(LBAudioDetectiveCorpus* c, const uint32_t* d_blocks, uint32_t n, uint32_t per, uint32_t range,
+                          uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
+    if (c->count == 0) {                                   // nothing to scan: every key is "no match"
+        LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream));
+        return noErr;
+    }
+    // the systolic scans max their keys in place
+    if (sliding_short(per, c->ne_max) || (n > 1 && sliding_multi(per, c->ne_max)))
+        LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream));
+    const size_t block_words = ((size_t)per + 1u) * 16u;
+    for (uint32_t at = 0; at < n;) {
+        const uint32_t g = d_scores ? 1u : sliding_queries_per_launch(per, c->ne_max, n - at);
+        uint32_t pos[8];
+        for (uint32_t i = 0; i < g; ++i) pos[i] = at + i;
+        OSStatus st = launch_ragged_blocks(c, per, nullptr, d_blocks + (size_t)at * block_words, pos, g, range, index_base, d_scores, keys, stream);
+        if (st != noErr) return st;
+        at += g;
+    }
     return noErr;
 }
 
@@ -445,6 +486,8 @@ void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
     if (c->d_topk_scan_keys) (void)hipFree(c->d_topk_scan_keys);
     if (c->d_topk_keys) (void)hipFree(c->d_topk_keys);
     if (c->align_ev) { (void)hipEventSynchronize(c->align_ev); (void)hipEventDestroy(c->align_ev); }
+    if (c->pq_ev) { (void)hipEventSynchronize(c->pq_ev); (void)hipEventDestroy(c->pq_ev); }
+    if (c->d_pq) (void)hipFree(c->d_pq);
     if (c->d_align_q) (void)hipFree(c->d_align_q);
     if (c->h_align_q) (void)hipHostFree(c->h_align_q);
     if (c->d_align_best) (void)hipFree(c->d_align_best);
@@ -618,9 +661,50 @@ OSStatus grow_topk(void** ptr, size_t* cap, size_t bytes) {
     return noErr;
 }
 
-// inCount queries, their keys to keys (device, inCount x k): groups of up to kQueryBatchMax queries write their score rows
-// (uniform corpus, the specialised shape: ONE pass of the batch scan; otherwise one scores scan per query), then one
-// selection over the group's rows
+// one query's per-entry scores (count floats) to d_scores and the scan's own key word to d_key, on the call's stream
+using ScoreScan = std::function<OSStatus(uint32_t q, float* d_scores, unsigned long long* d_key)>;
+
+// the previous top-K call's scans and selection may still read / write the scratch (on whatever stream it ran)
+OSStatus wait_topk(LBAudioDetectiveCorpus* c) {
+    if (c->topk_ev) LBAD_HIP(hipEventSynchronize(c->topk_ev));
+    else LBAD_HIP(hipEventCreateWithFlags(&c->topk_ev, hipEventDisableTiming));
+    return noErr;
+}
+
+// score rows, selection scratch and the scans' key words for a call of n queries
+OSStatus reserve_topk(LBAudioDetectiveCorpus* c, uint32_t n) {
+    const uint32_t rows = n < kQueryBatchMax ? n : kQueryBatchMax;
+    OSStatus st = grow_topk(reinterpret_cast<void**>(&c->d_topk_scores), &c->topk_scores_cap, (size_t)rows * c->count * sizeof(float));
+    if (st == noErr) st = grow_topk(&c->d_topk_scratch, &c->topk_scratch_cap, topk_scratch_bytes(rows));
+    if (st != noErr) return st;
+    if (!c->d_topk_scan_keys) LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_topk_scan_keys), kQueryBatchMax * sizeof(unsigned long long)));
+    return noErr;
+}
+
+// The scans and the selection of n staged queries, their keys to keys (device, n x k): groups of up to kQueryBatchMax queries
+// write their score rows -- d_qblocks given (the batch scan's blocks of all n queries, on the device): ONE pass of the batch
+// scan; otherwise scan_one per query -- then one selection over the group's rows.
+OSStatus topk_scan_select(LBAudioDetectiveCorpus* c, uint32_t n, uint32_t k, uint64_t index_base, unsigned long long* keys,
+                          hipStream_t stream, const uint32_t* d_qblocks, const ScoreScan& scan_one) {
+    const uint32_t kw = plane_query_words();
+    for (uint32_t q0 = 0; q0 < n; q0 += kQueryBatchMax) {
+        const uint32_t g = n - q0 < kQueryBatchMax ? n - q0 : kQueryBatchMax;
+        if (d_qblocks) {
+            LBAD_HIP(launch_compare_planes_batch_scores(c->d_planes, c->capacity, c->count, c->n_sub, d_qblocks + (size_t)q0 * kw, g,
+                                                        c->d_topk_scores, stream));
+        } else {
+            for (uint32_t i = 0; i < g; ++i) {
+                OSStatus st = scan_one(q0 + i, c->d_topk_scores + (size_t)i * c->count, c->d_topk_scan_keys + i);
+                if (st != noErr) return st;
+            }
+        }
+        LBAD_HIP(launch_topk_keys(c->d_topk_scores, c->count, g, k, index_base, c->d_topk_scratch, keys + (size_t)q0 * k, stream));
+    }
+    return noErr;
+}
+
+// inCount queries, their keys to keys (device, inCount x k): the queries staged from their handles (uniform corpus, the
+// specialised shape: the batch scan's blocks; otherwise each scores scan stages its own), then topk_scan_select
 OSStatus topk_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range, uint32_t k,
                         uint64_t index_base, unsigned long long* keys, hipStream_t stream) {
     if (!c || !qs || !keys || n == 0 || k == 0 || k > kTopKMax) return kLBAudioDetectiveArgumentInvalid;
@@ -630,19 +714,15 @@ OSStatus topk_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerp
     if (range == 0) range = c->subfp_len;   // LBAudioDetective.m:443-445
     bool batch_scan = !c->ragged && c->variant != 1;
     for (uint32_t i = 0; i < n && batch_scan; ++i) batch_scan = planes_fast_supported(c->subfp_len, c->n_sub, qs[i]->count);
-    // the previous call's scans and selection may still read / write the scratch (on whatever stream it ran)
-    if (c->topk_ev) LBAD_HIP(hipEventSynchronize(c->topk_ev));
-    else LBAD_HIP(hipEventCreateWithFlags(&c->topk_ev, hipEventDisableTiming));
+    OSStatus st = wait_topk(c);
+    if (st != noErr) return st;
     if (c->count == 0) {
         LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * k * sizeof(unsigned long long), stream));
         LBAD_HIP(hipEventRecord(c->topk_ev, stream));
         return noErr;
     }
-    const uint32_t rows = n < kQueryBatchMax ? n : kQueryBatchMax;
-    OSStatus st = grow_topk(reinterpret_cast<void**>(&c->d_topk_scores), &c->topk_scores_cap, (size_t)rows * c->count * sizeof(float));
-    if (st == noErr) st = grow_topk(&c->d_topk_scratch, &c->topk_scratch_cap, topk_scratch_bytes(rows));
+    st = reserve_topk(c, n);
     if (st != noErr) return st;
-    if (!c->d_topk_scan_keys) LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_topk_scan_keys), kQueryBatchMax * sizeof(unsigned long long)));
     const uint32_t kw = plane_query_words();
     if (batch_scan) {
         const size_t bytes = (size_t)n * kw * sizeof(uint32_t);   // every group's blocks at once: the copies are asynchronous
@@ -665,21 +745,126 @@ OSStatus topk_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerp
         }
         LBAD_HIP(hipMemcpyAsync(c->d_topk_q, c->h_topk_q, bytes, hipMemcpyHostToDevice, stream));
     }
-    for (uint32_t q0 = 0; q0 < n; q0 += kQueryBatchMax) {
-        const uint32_t g = n - q0 < kQueryBatchMax ? n - q0 : kQueryBatchMax;
-        if (batch_scan) {
-            LBAD_HIP(launch_compare_planes_batch_scores(c->d_planes, c->capacity, c->count, c->n_sub, c->d_topk_q + (size_t)q0 * kw, g,
-                                                        c->d_topk_scores, stream));
-        } else {
-            for (uint32_t i = 0; i < g; ++i) {
-                st = run_query(c, qs[q0 + i], range, 0, c->d_topk_scores + (size_t)i * c->count, c->d_topk_scan_keys + i, stream);
-                if (st != noErr) return st;
-            }
-        }
-        LBAD_HIP(launch_topk_keys(c->d_topk_scores, c->count, g, k, index_base, c->d_topk_scratch, keys + (size_t)q0 * k, stream));
-    }
+    st = topk_scan_select(c, n, k, index_base, keys, stream, batch_scan ? c->d_topk_q : nullptr,
+                          [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
+                              return run_query(c, qs[q], range, 0, d_scores, d_key, stream);
+                          });
+    if (st != noErr) return st;
     LBAD_HIP(hipEventRecord(c->topk_ev, stream));
     return noErr;
+}
+
+// ---- packed queries: the blocks come from the builders of k_query.hip instead of the handles' Booleans ---------------------
+struct BuiltQueries {
+    const uint32_t* scan = nullptr;      // ragged: sliding blocks; uniform: plane blocks (fast) or the rows cleared from the length on
+    bool fast = false;
+    const uint2* desc = nullptr;         // with lags: launch_align_keys' table and words
+    const uint32_t* words = nullptr;
+};
+
+// n queries of `per` packed sub-fingerprints at d_rows (device) -> their blocks in the corpus' scratch, on `stream`.  Waits
+// (on the host, as the top-K scratch does) for the previous packed call's event; the caller records pq_ev behind its last kernel.
+OSStatus build_packed(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t n, uint32_t per, uint32_t range, bool lags,
+                      hipStream_t stream, BuiltQueries& out) {
+    if ((uint64_t)n * per > 0xFFFFFFFFull) return kLBAudioDetectiveArgumentInvalid;      // (the tables count sub-fingerprints in 32 bits)
+    if (lags && (per > 0x7FFFFFFFu || (c->ragged && c->ne_max > 0x7FFFFFFFu))) return kLBAudioDetectiveArgumentInvalid;   // (a lag is a signed 32-bit offset)
+    out.fast = !c->ragged && c->variant != 1 && planes_fast_supported(c->subfp_len, c->n_sub, per);
+    if (!c->ragged) {
+        if (c->variant == 2 && !out.fast) return kLBAudioDetectiveArgumentInvalid;
+        if (!out.fast && (size_t)per * kPackedWords * 4 > 48 * 1024) return kLBAudioDetectiveArgumentInvalid;     // (the generic scan keeps the query in LDS)
+    }
+    const size_t row_words = (size_t)n * per * kPackedWords;
+    const size_t scan_words = c->ragged ? (size_t)n * ((size_t)per + 1u) * 16u : (out.fast ? (size_t)n * plane_query_words() : row_words);
+    const bool rows_serve_both = !c->ragged && !out.fast;         // the generic scan and the uniform alignment read the same words
+    // (every part starts on a 256-byte boundary, as the staging slots of the handle path do)
+    const size_t desc_words = lags ? (((size_t)2 * n + 63) & ~(size_t)63) : 0;
+    const size_t align_words = lags && !rows_serve_both ? ((row_words + 63) & ~(size_t)63) : 0;
+    const size_t bytes = (desc_words + align_words + scan_words) * sizeof(uint32_t);
+    if (c->pq_ev) LBAD_HIP(hipEventSynchronize(c->pq_ev));
+    else LBAD_HIP(hipEventCreateWithFlags(&c->pq_ev, hipEventDisableTiming));
+    OSStatus st = grow_topk(reinterpret_cast<void**>(&c->d_pq), &c->pq_cap, bytes);
+    if (st != noErr) return st;
+    uint2* desc = lags ? reinterpret_cast<uint2*>(c->d_pq) : nullptr;
+    uint32_t* words = c->d_pq + desc_words;
+    uint32_t* scan = words + align_words;
+    if (c->ragged) {
+        LBAD_HIP(launch_build_sliding_queries(d_rows, n, per, c->subfp_len, range, scan, stream));
+        if (lags) LBAD_HIP(launch_build_query_rows(d_rows, n, per, c->subfp_len, true, words, desc, stream));
+    } else if (out.fast) {
+        LBAD_HIP(launch_build_plane_queries(d_rows, n, c->n_sub, range, scan, stream));
+        if (lags) LBAD_HIP(launch_build_query_rows(d_rows, n, per, c->subfp_len, false, words, desc, stream));
+    } else {
+        LBAD_HIP(launch_build_query_rows(d_rows, n, per, c->subfp_len, false, scan, desc, stream));
+        words = scan;
+    }
+    out.scan = scan;
+    out.desc = desc;
+    out.words = lags ? words : nullptr;
+    return noErr;
+}
+
+// one built query's scan with per-entry scores (top-K) or without (d_scores null; uniform generic shapes, top-1)
+OSStatus scan_built_one(LBAudioDetectiveCorpus* c, const BuiltQueries& b, uint32_t q, uint32_t per, uint32_t range, uint64_t index_base,
+                        float* d_scores, unsigned long long* d_key, hipStream_t stream) {
+    if (c->ragged)
+        return run_built_ragged(c, b.scan + (size_t)q * ((size_t)per + 1u) * 16u, 1, per, range, index_base, d_scores, d_key, stream);
+    LBAD_HIP(hipMemsetAsync(d_key, 0, sizeof(unsigned long long), stream));
+    LBAD_HIP(launch_compare_planes_generic(c->d_planes, c->capacity, c->count, c->n_sub, c->subfp_len, b.scan + (size_t)q * per * kPackedWords,
+                                           per, range, index_base, d_scores, d_key, stream));
+    return noErr;
+}
+
+OSStatus packed_keys_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t n, uint32_t per, uint32_t range,
+                          uint64_t index_base, unsigned long long* keys, hipStream_t stream) {
+    if (!c || !d_rows || !keys || n == 0 || per == 0) return kLBAudioDetectiveArgumentInvalid;
+    if (index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
+    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
+    if (range == 0) range = c->subfp_len;   // LBAudioDetective.m:443-445
+    BuiltQueries b;
+    OSStatus st = build_packed(c, d_rows, n, per, range, false, stream, b);
+    if (st != noErr) return st;
+    if (c->ragged) {
+        st = run_built_ragged(c, b.scan, n, per, range, index_base, nullptr, keys, stream);
+    } else if (b.fast) {
+        // the batch scan even for one query: it equals the single-query scan bit for bit
+        st = hip_status(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream), "keys", __LINE__);
+        if (st == noErr)
+            st = hip_status(launch_compare_planes_batch(c->d_planes, c->capacity, c->count, c->n_sub, b.scan, n, index_base, keys, stream),
+                            "batch scan", __LINE__);
+    } else {
+        for (uint32_t q = 0; q < n && st == noErr; ++q) st = scan_built_one(c, b, q, per, range, index_base, nullptr, keys + q, stream);
+    }
+    const OSStatus rec = hip_status(hipEventRecord(c->pq_ev, stream), "event", __LINE__);     // (also behind what a failed call did launch)
+    return st != noErr ? st : rec;
+}
+
+OSStatus packed_topk_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t n, uint32_t per, uint32_t range, uint32_t k,
+                          uint64_t index_base, unsigned long long* keys, int32_t* lags, hipStream_t stream) {
+    if (!c || !d_rows || !keys || n == 0 || per == 0 || k == 0 || k > kTopKMax) return kLBAudioDetectiveArgumentInvalid;
+    if (index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
+    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
+    if (range == 0) range = c->subfp_len;
+    OSStatus st = wait_topk(c);
+    if (st != noErr) return st;
+    BuiltQueries b;
+    st = build_packed(c, d_rows, n, per, range, lags != nullptr, stream, b);
+    if (st != noErr) return st;
+    if (c->count == 0) {                                   // nothing to select from: zero keys, zero lags
+        st = hip_status(hipMemsetAsync(keys, 0, (size_t)n * k * sizeof(unsigned long long), stream), "keys", __LINE__);
+        if (st == noErr && lags) st = hip_status(hipMemsetAsync(lags, 0, (size_t)n * k * sizeof(int32_t), stream), "lags", __LINE__);
+    } else {
+        st = reserve_topk(c, n);
+        if (st == noErr)
+            st = topk_scan_select(c, n, k, index_base, keys, stream, b.fast ? b.scan : nullptr,
+                                  [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
+                                      return scan_built_one(c, b, q, per, range, 0, d_scores, d_key, stream);
+                                  });
+    }
+    OSStatus rec = hip_status(hipEventRecord(c->topk_ev, stream), "event", __LINE__);
+    if (st == noErr && rec == noErr && lags && c->count != 0)
+        st = align_keys_built(c, b.desc, b.words, n, per, range, k, keys, index_base, lags, stream);
+    const OSStatus rec2 = hip_status(hipEventRecord(c->pq_ev, stream), "event", __LINE__);
+    return st != noErr ? st : (rec != noErr ? rec : rec2);
 }
 
 // host-returning form: keys through the corpus' own buffer on the null stream, then decoded
@@ -731,6 +916,81 @@ OSStatus LBAudioDetectiveCorpusQueryTopK(LBAudioDetectiveCorpusRef c, LBAudioDet
     LBAD_GUARD_BEGIN
     if (!inQuery) return kLBAudioDetectiveArgumentInvalid;
     return lbad::topk_host_impl(c, &inQuery, 1, inRange, inK, outIndices, outScores, outCount);
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusQueryPackedKeysDevice(LBAudioDetectiveCorpusRef c, const void* inPackedQueries, UInt32 inCount,
+                                                     UInt32 inSubfingerprintsPerQuery, UInt32 inRange, UInt64 inIndexBase, void* outKeys,
+                                                     void* inStream) {
+    LBAD_GUARD_BEGIN
+    return lbad::packed_keys_impl(c, static_cast<const uint32_t*>(inPackedQueries), inCount, inSubfingerprintsPerQuery, inRange,
+                                  inIndexBase, static_cast<unsigned long long*>(outKeys), static_cast<hipStream_t>(inStream));
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusQueryPackedTopKKeysDevice(LBAudioDetectiveCorpusRef c, const void* inPackedQueries, UInt32 inCount,
+                                                         UInt32 inSubfingerprintsPerQuery, UInt32 inRange, UInt32 inK,
+                                                         UInt64 inIndexBase, void* outKeys, void* outLags, void* inStream) {
+    LBAD_GUARD_BEGIN
+    return lbad::packed_topk_impl(c, static_cast<const uint32_t*>(inPackedQueries), inCount, inSubfingerprintsPerQuery, inRange, inK,
+                                  inIndexBase, static_cast<unsigned long long*>(outKeys), static_cast<int32_t*>(outLags),
+                                  static_cast<hipStream_t>(inStream));
+    LBAD_GUARD_END
+}
+
+// Debug / tests: the blocks a builder makes of inCount x inPer sub-fingerprints -- from packed rows on the device (the kernels
+// of k_query.hip) or from Booleans on the host (the builders behind the handle-taking calls) -- copied to a host buffer
+OSStatus LBAudioDetectiveDebugQueryBlocks(UInt32 inKind, const void* inPackedQueries, const Boolean* inBooleans, UInt32 inCount,
+                                          UInt32 inPer, UInt32 inSubfingerprintLength, UInt32 inRange, UInt32* outWords,
+                                          UInt64 inCapacity, UInt64* outCount) {
+    LBAD_GUARD_BEGIN
+    const uint32_t L = inSubfingerprintLength;
+    if (inKind > 3 || (!inPackedQueries) == (!inBooleans) || inCount == 0 || inPer == 0 || !outCount || L == 0 ||
+        (uint64_t)inCount * inPer > 0xFFFFFFFFull)
+        return kLBAudioDetectiveArgumentInvalid;
+    if (inKind == 0 ? !lbad::planes_fast_supported(L, inPer, inPer) : (inKind == 3 ? L > 32u * lbad::kPackedWords : !lbad::sliding_supported(L)))
+        return kLBAudioDetectiveArgumentInvalid;
+    const uint32_t range = inRange ? inRange : L;
+    const size_t per_query = inKind == 0 ? lbad::plane_query_words() : (inKind == 1 ? ((size_t)inPer + 1u) * 16u : (size_t)inPer * lbad::kPackedWords);
+    const size_t words = per_query * inCount;
+    *outCount = words;
+    if (!outWords || inCapacity < words) return kLBAudioDetectiveArgumentInvalid;
+    if (inBooleans) {
+        std::vector<uint32_t> slots, block;
+        LBAudioDetectiveFingerprint fp;
+        fp.length = L;
+        fp.count = inPer;
+        for (UInt32 q = 0; q < inCount; ++q) {
+            const Boolean* b = inBooleans + (size_t)q * inPer * L;
+            uint32_t* o = outWords + (size_t)q * per_query;
+            std::memset(o, 0, per_query * sizeof(uint32_t));
+            if (inKind == 1) {
+                lbad::build_sliding_query(b, inPer, L, range, block);
+                std::memcpy(o, block.data() + (block.size() - per_query), per_query * sizeof(uint32_t));     // (without the header)
+                continue;
+            }
+            fp.data.assign(b, b + (size_t)inPer * L);
+            block.clear();
+            if (inKind == 0) {
+                lbad::pack_fingerprint(&fp, slots);
+                lbad::build_plane_query(slots.data(), inPer, range, block);
+            } else {
+                lbad::build_align_query(&fp, inKind == 2, block);
+            }
+            std::memcpy(o, block.data(), block.size() * sizeof(uint32_t));
+        }
+        return noErr;
+    }
+    if (!lbad::device_ready()) return kLBAudioDetectiveDeviceUnavailable;
+    uint32_t* d = nullptr;
+    LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&d), words * sizeof(uint32_t)));
+    const uint32_t* rows = static_cast<const uint32_t*>(inPackedQueries);
+    hipError_t e = inKind == 0   ? lbad::launch_build_plane_queries(rows, inCount, inPer, range, d, nullptr)
+                   : inKind == 1 ? lbad::launch_build_sliding_queries(rows, inCount, inPer, L, range, d, nullptr)
+                                 : lbad::launch_build_query_rows(rows, inCount, inPer, L, inKind == 2, d, nullptr, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(outWords, d, words * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    return lbad::hip_status(e, "query blocks", __LINE__);
     LBAD_GUARD_END
 }
 

@@ -342,6 +342,10 @@ hipError_t launch_sliding_plan(const uint32_t* d_off, uint64_t n_entries, uint32
 // tasks_a / tasks_b: groups of four sliding offsets over the entries longer / not longer than the query; d_query: the
 // block build_sliding_query made; zero_rec: index of an all-zero record
 bool sliding_short(uint32_t n_query, uint32_t ne_max);    // the systolic scan of short queries applies (no plan needed)
+// does ONE launch of n_q queries read the plan?  (launch_compare_sliding's own choice of kernel: only the task kernel does;
+// tasks_a as handed to it, scores: per-entry scores are asked for)
+bool sliding_needs_plan(uint32_t n_query, uint32_t ne_max, uint32_t n_q, uint64_t tasks_a, bool scores);
+uint4 sliding_range_mask(uint32_t subfp_len, uint32_t range);    // pairs inside min(range, length), one bit each
 hipError_t launch_compare_sliding(const uint4* d_recs, uint64_t n_pos, const uint32_t* d_off, uint64_t n_entries, uint32_t ne_max,
                                   uint32_t zero_rec, uint64_t tasks_a, uint64_t tasks_b, const SlideShape& sh, const uint32_t* d_plan,
                                   uint32_t subfp_len, const SlideScan& scan, uint32_t n_query, uint32_t range,
@@ -355,6 +359,20 @@ constexpr uint32_t kSlideSplitBelow = 16;
 constexpr uint64_t kMaxRaggedEntries = 0xFFFF0000ull;
 constexpr uint64_t kMaxRaggedRecords = 0xFFFFFF00ull;
 constexpr uint32_t kRecordSlack = 8;   // records allocated behind a ragged corpus' capacity (zero: over-read + the zero record)
+
+// query blocks built on the device (k_query.hip) from n_queries x per packed sub-fingerprints at d_rows (8 words each, 4-byte
+// aligned), bit for bit what the host builders make from the same Booleans; bits at or above the length are ignored.
+// plane blocks: plane_query_words() words per query (build_plane_query, zero padded), per == n_sub, length 200
+hipError_t launch_build_plane_queries(const uint32_t* d_rows, uint32_t n_queries, uint32_t n_sub, uint32_t range,
+                                      uint32_t* d_blocks, hipStream_t stream);
+// sliding blocks: (per + 1) * 16 words per query (build_sliding_query without its header); d_blocks 16-byte aligned
+hipError_t launch_build_sliding_queries(const uint32_t* d_rows, uint32_t n_queries, uint32_t per, uint32_t subfp_len, uint32_t range,
+                                        uint32_t* d_blocks, hipStream_t stream);
+// 8 words per sub-fingerprint to d_words (16-byte aligned): the slot words cleared from the length on (the generic uniform
+// scan's query, build_align_query's uniform form), or with `pairs` build_align_query's ragged form; d_desc (optional):
+// launch_align_keys' table, query q = (q * per, per)
+hipError_t launch_build_query_rows(const uint32_t* d_rows, uint32_t n_queries, uint32_t per, uint32_t subfp_len, bool pairs,
+                                   uint32_t* d_words, uint2* d_desc, hipStream_t stream);
 
 // measurement: ticks of the shader clock and of the constant 100 MHz clock over ~usec microseconds (2 words)
 hipError_t launch_clock_probe(uint32_t usec, unsigned long long* d_out, hipStream_t stream);
@@ -372,6 +390,11 @@ OSStatus grow_device(void** ptr, size_t* cap, size_t bytes);
 OSStatus fingerprint_clips_device(struct ::LBAudioDetective* d, const void* d_pcm, uint32_t fmt, uint64_t n_clips,
                                   uint64_t samples_per_clip, uint32_t* d_packed, float* d_raw, float* d_haar,
                                   hipStream_t stream, const FileTail* tails = nullptr, size_t n_tails = 0);
+// api_align.cpp: the lags of n x k keys for n queries of `per` sub-fingerprints each whose alignment words and table a builder
+// wrote to the device; waits for / records the alignment scratch's event itself
+OSStatus align_keys_built(struct ::LBAudioDetectiveCorpus* c, const uint2* d_desc, const uint32_t* d_words, uint32_t n, uint32_t per,
+                          uint32_t range, uint32_t k, const unsigned long long* keys, uint64_t index_base, int32_t* lags,
+                          hipStream_t stream);
 ::LBAudioDetectiveFingerprintRef fingerprint_from_bools(const struct ::LBAudioDetective* d, const Boolean* bools, uint64_t per);
 // the file entry points (api_files.cpp): decode, conversion and the window loop of n files in one launch chain per
 // hop value; statuses (optional) receives every file's status
@@ -548,4 +571,9 @@ struct LBAudioDetectiveCorpus {
     void* d_align_out = nullptr;
     size_t align_out_cap = 0;
     hipEvent_t align_ev = nullptr;
+    // packed queries (the ...QueryPacked...Device calls): what the builders of k_query.hip write -- the scan's blocks, then the
+    // alignment's table and words.  Grown on demand; a call reuses it only after pq_ev, recorded behind its last kernel.
+    uint32_t* d_pq = nullptr;
+    size_t pq_cap = 0;                           // bytes
+    hipEvent_t pq_ev = nullptr;
 };

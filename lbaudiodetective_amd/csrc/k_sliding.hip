@@ -1703,11 +1703,11 @@ uint4 pair_mask(uint32_t limit) {
     return make_uint4(m[0], m[1], m[2], m[3]);
 }
 
+}  // namespace
+
 uint4 sliding_range_mask(uint32_t subfp_len, uint32_t range) {
     return pair_mask(range < subfp_len ? range : subfp_len);      // Fp.m:155
 }
-
-}  // namespace
 
 bool sliding_supported(uint32_t subfp_len) { return subfp_len >= 1 && subfp_len <= 2 * kTriPairs; }
 
@@ -1805,6 +1805,15 @@ constexpr uint32_t kShortEntries = 15;
 bool sliding_short(uint32_t n_query, uint32_t ne_max) { return n_query <= LBAD_SHORT_QUERY || ne_max <= kShortEntries; }
 // A BATCH of such queries goes through compare_short_multi_kernel (defined above; needs an entry longer than the query)
 bool sliding_multi(uint32_t n_query, uint32_t ne_max) { return n_query <= LBAD_SHORT_MULTI_MAX && ne_max > n_query; }
+// several queries per launch, an entry longer than them, keys only: compare_short_multi_kernel
+static bool sliding_takes_multi(uint32_t n_query, uint32_t ne_max, uint32_t n_q, uint64_t tasks_a, bool scores) {
+    return n_q > 1 && sliding_multi(n_query, ne_max) && tasks_a != 0 && !scores;
+}
+// Which kernel a launch of n_q queries takes (launch_compare_sliding's choice, and the caller's "does this launch read the
+// plan?"): only the task kernel walks the plan's runs of entries, the two systolic scans walk the records
+bool sliding_needs_plan(uint32_t n_query, uint32_t ne_max, uint32_t n_q, uint64_t tasks_a, bool scores) {
+    return !sliding_takes_multi(n_query, ne_max, n_q, tasks_a, scores) && !sliding_short(n_query, ne_max);
+}
 
 static void sliding_variant(uint32_t subfp_len, uint32_t n_query, uint32_t range, uint32_t n_q, bool& full, bool& qlds, uint32_t& dyn_lds) {
     const uint4 rm = sliding_range_mask(subfp_len, range);
@@ -1932,7 +1941,7 @@ hipError_t launch_compare_sliding(const uint4* d_recs, uint64_t n_pos, const uin
 #undef LBAD_SHORT
         return hipGetLastError();
     };
-    // several queries of up to seven sub-fingerprints: the entries longer than the query through compare_short_multi_kernel
+    // several queries of up to LBAD_SHORT_MULTI_MAX (12) sub-fingerprints: the entries longer than the query through compare_short_multi_kernel
     // (four records per lane, query words in vector registers), the others -- where the corpus has any (tasks_b counts their
     // offsets) -- through the systolic scan above in its only_upto mode, which maxes into the same keys
     auto run_short_multi = [&]() -> hipError_t {
@@ -1982,8 +1991,8 @@ hipError_t launch_compare_sliding(const uint4* d_recs, uint64_t n_pos, const uin
         if (launched != hipSuccess || tasks_b == 0) return launched;
         return run_short(look, n_query);
     };
-    if (n_q > 1 && sliding_multi(n_query, ne_max) && tasks_a != 0 && !d_score_bits) return run_short_multi();
-    if (sliding_short(n_query, ne_max)) return run_short((n_query < ne_max ? n_query : ne_max) - 1u, 0u);
+    if (sliding_takes_multi(n_query, ne_max, n_q, tasks_a, d_score_bits != nullptr)) return run_short_multi();
+    if (!sliding_needs_plan(n_query, ne_max, n_q, tasks_a, d_score_bits != nullptr)) return run_short((n_query < ne_max ? n_query : ne_max) - 1u, 0u);
     SlideArgs a;
     a.index_base = index_base; a.n_entries = n_entries; a.nq = n_query; a.zero_rec = zero_rec;
     const uint4 rm = sliding_range_mask(subfp_len, range);

@@ -178,7 +178,11 @@ def make_comm(rank: int = 0, world_size: int = 1, group=None):
 class ShardedCorpus:
     """This rank's shard of a global corpus plus the collective top-1 query.  With `comm` (make_comm) the
     exchange step runs inside the library (ncclAllReduce of the uint64 keys, LBAudioDetectiveCorpusQuerySharded);
-    without it the keys are reduced through torch.distributed (the CPU tests use gloo)."""
+    without it the keys are reduced through torch.distributed (the CPU tests use gloo).
+
+    Packed queries (fingerprints already on the device) need nothing here: `local.query_packed_keys_device` /
+    `local.query_packed_topk_keys_device` with index_base = `begin` write the very keys (and lags) that a max-reduction,
+    gather_topk_keys and gather_topk_aligned take."""
 
     def __init__(self, subfingerprint_length: int, subfingerprints_per_entry: int, n_entries_global: int,
                  rank: int = 0, world_size: int = 1, group=None, comm=None):

@@ -601,6 +601,10 @@ OSStatus LBAudioDetectiveCorpusQueryPackedTopKKeysDevice(LBAudioDetectiveCorpusR
 OSStatus LBAudioDetectiveDebugQueryBlocks(UInt32 inKind, const void* inPackedQueries, const Boolean* inBooleans, UInt32 inCount,
                                           UInt32 inPer, UInt32 inSubfingerprintLength, UInt32 inRange, UInt32* outWords,
                                           UInt64 inCapacity, UInt64* outCount);
+/* Debug / tests: bytes of device and of pinned host memory that detectives and corpora of this process hold right now, scratch of
+ * single calls included.  The process-wide contexts of the pair compare, the Frame API and the sharded query, and what
+ * LBAudioDetectiveDeviceMalloc hands out, are not counted.  Needs no device. */
+OSStatus LBAudioDetectiveDebugLiveBytes(UInt64* outDevice, UInt64* outPinned);
 /* Binary corpus file ("LBADCRP1" header + the stored entries' planes; a ragged corpus: "LBADCRP2" header + the
  * entries' sub-fingerprint counts + the records); Load recognises both, reserves max(inCapacity, stored count)
  * entries and, for a ragged corpus, records in proportion. */

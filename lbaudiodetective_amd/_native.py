@@ -179,6 +179,7 @@ _SIGNATURES = {
                                                                    C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveDebugQueryBlocks": (OSStatus, [UInt32, C.c_void_p, C.c_void_p, UInt32, UInt32, UInt32, UInt32, C.c_void_p, UInt64,
                                                     _P(UInt64)]),
+    "LBAudioDetectiveDebugLiveBytes": (OSStatus, [_P(UInt64), _P(UInt64)]),
     "LBAudioDetectiveCorpusSetKernelVariant": (OSStatus, [Ref, UInt32]),
     "LBAudioDetectiveCorpusSave": (OSStatus, [Ref, C.c_char_p]),
     "LBAudioDetectiveCorpusLoad": (Ref, [C.c_char_p, UInt64]),

@@ -814,6 +814,13 @@ def debug_query_blocks(kind: int, n_queries: int, per_query: int, subfp_len: int
     return out[:count.value].reshape(n_queries, -1)
 
 
+def debug_live_bytes():
+    """LBAudioDetectiveDebugLiveBytes (tests): (device, pinned) bytes that detectives and corpora hold right now."""
+    dev, pinned = N.UInt64(0), N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveDebugLiveBytes(C.byref(dev), C.byref(pinned)), "DebugLiveBytes")
+    return dev.value, pinned.value
+
+
 class Comm:
     """An RCCL communicator made through the library's helpers (ncclCommInitRank with the current device).
     `unique_id()` on rank 0, the 128 bytes travel to the other ranks by whatever means the host has, then every

@@ -7,22 +7,8 @@
 namespace lbad {
 namespace {
 
-OSStatus grow(void** ptr, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return noErr;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *cap = 0;
-    LBAD_HIP(hipMalloc(ptr, bytes));
-    *cap = bytes;
-    return noErr;
-}
-
-// the previous alignment's kernels may still read / write the scratch (on whatever stream they ran)
-OSStatus wait_align(LBAudioDetectiveCorpus* c) {
-    if (c->align_ev) LBAD_HIP(hipEventSynchronize(c->align_ev));
-    else LBAD_HIP(hipEventCreateWithFlags(&c->align_ev, hipEventDisableTiming));
-    return noErr;
-}
+// (every entry point first waits for align_ev: the previous alignment's kernels may still read / write the scratch, on
+// whatever stream they ran)
 
 AlignSource source(const LBAudioDetectiveCorpus* c, uint32_t range) {
     AlignSource s;
@@ -81,20 +67,12 @@ OSStatus stage_queries(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerpr
     if (first > 0xFFFFFFFFull) return kLBAudioDetectiveArgumentInvalid;
     for (uint32_t i = 0; i < n; ++i) build_align_query(qs[i], c->ragged, all);
     const size_t bytes = all.size() * sizeof(uint32_t);
-    if (c->align_q_cap < bytes) {
-        if (c->d_align_q) (void)hipFree(c->d_align_q);
-        if (c->h_align_q) (void)hipHostFree(c->h_align_q);
-        c->d_align_q = nullptr;
-        c->h_align_q = nullptr;
-        c->align_q_cap = 0;
-        LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_align_q), bytes));
-        LBAD_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_align_q), bytes, hipHostMallocDefault));
-        c->align_q_cap = bytes;
-    }
-    std::memcpy(c->h_align_q, all.data(), bytes);
-    LBAD_HIP(hipMemcpyAsync(c->d_align_q, c->h_align_q, bytes, hipMemcpyHostToDevice, stream));
-    *d_desc = reinterpret_cast<const uint2*>(c->d_align_q);
-    *d_words = c->d_align_q + desc_words;
+    OSStatus st = c->align_q.reserve(all.size());
+    if (st != noErr) return st;
+    std::memcpy(c->align_q.host, all.data(), bytes);
+    LBAD_HIP(hipMemcpyAsync(c->align_q.dev, c->align_q.host, bytes, hipMemcpyHostToDevice, stream));
+    *d_desc = reinterpret_cast<const uint2*>(c->align_q.dev.get());
+    *d_words = c->align_q.dev + desc_words;
     return noErr;
 }
 
@@ -103,7 +81,7 @@ OSStatus align_launch(LBAudioDetectiveCorpus* c, const uint2* d_desc, const uint
                       uint32_t k, const unsigned long long* keys, uint64_t index_base, int32_t* lags, float* scores, hipStream_t stream) {
     const uint64_t pairs = (uint64_t)n * k;
     if (align_parts(pairs, max_off) > 1) {
-        OSStatus st = grow(reinterpret_cast<void**>(&c->d_align_best), &c->align_best_cap, pairs * sizeof(unsigned long long));
+        OSStatus st = c->d_align_best.reserve(pairs);
         if (st != noErr) return st;
     }
     LBAD_HIP(launch_align_keys(source(c, range), d_words, d_desc, n, k, keys, index_base, max_off, c->d_align_best, lags, scores, stream));
@@ -131,11 +109,10 @@ OSStatus align_keys_built(LBAudioDetectiveCorpus* c, const uint2* d_desc, const 
                           uint32_t range, uint32_t k, const unsigned long long* keys, uint64_t index_base, int32_t* lags,
                           hipStream_t stream) {
     if (!c || per == 0 || per > 0x7FFFFFFFu || (c->ragged && c->ne_max > 0x7FFFFFFFu)) return kLBAudioDetectiveArgumentInvalid;
-    OSStatus st = wait_align(c);       // (the per-pair maxima of a split launch are the previous alignment's until then)
+    OSStatus st = c->align_ev.wait_or_create();       // (the per-pair maxima of a split launch are the previous alignment's until then)
     if (st == noErr) st = align_launch(c, d_desc, d_words, n, max_offsets(c, per), range, k, keys, index_base, lags, nullptr, stream);
     if (st != noErr) return st;
-    LBAD_HIP(hipEventRecord(c->align_ev, stream));
-    return noErr;
+    return c->align_ev.record(stream);
 }
 
 }  // namespace lbad
@@ -151,13 +128,12 @@ OSStatus LBAudioDetectiveCorpusAlignKeysDevice(LBAudioDetectiveCorpusRef c, cons
     if (!lbad::device_ready()) return kLBAudioDetectiveDeviceUnavailable;
     if (!lbad::corpus_ok(c, inQueries, inCount) || inIndexBase + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
     hipStream_t stream = static_cast<hipStream_t>(inStream);
-    OSStatus st = lbad::wait_align(c);
+    OSStatus st = c->align_ev.wait_or_create();
     if (st == noErr)
         st = lbad::align_keys_impl(c, inQueries, inCount, inRange, inK, static_cast<const unsigned long long*>(inKeys), inIndexBase,
                                    static_cast<int32_t*>(outLags), static_cast<float*>(outScores), stream);
     if (st != noErr) return st;
-    LBAD_HIP(hipEventRecord(c->align_ev, stream));
-    return noErr;
+    return c->align_ev.record(stream);
     LBAD_GUARD_END
 }
 
@@ -170,19 +146,20 @@ OSStatus LBAudioDetectiveCorpusQueryBatchTopKAligned(LBAudioDetectiveCorpusRef c
         return kLBAudioDetectiveArgumentInvalid;
     if (!lbad::device_ready()) return kLBAudioDetectiveDeviceUnavailable;
     if (!lbad::corpus_ok(c, inQueries, inCount)) return kLBAudioDetectiveArgumentInvalid;
-    OSStatus st = lbad::wait_align(c);
+    OSStatus st = c->align_ev.wait_or_create();
     if (st != noErr) return st;
     // keys, then lags, in one block: one read-back
     const size_t words = (size_t)inCount * inK;
     const size_t bytes = words * (sizeof(unsigned long long) + sizeof(int32_t));
-    st = lbad::grow(&c->d_align_out, &c->align_out_cap, bytes);
+    st = c->d_align_out.reserve(bytes);
     if (st != noErr) return st;
-    unsigned long long* d_keys = static_cast<unsigned long long*>(c->d_align_out);
+    unsigned long long* d_keys = static_cast<unsigned long long*>(c->d_align_out.get());
     int32_t* d_lags = reinterpret_cast<int32_t*>(d_keys + words);
     st = LBAudioDetectiveCorpusQueryBatchTopKKeysDevice(c, inQueries, inCount, inRange, inK, 0, d_keys, NULL);
     if (st == noErr) st = lbad::align_keys_impl(c, inQueries, inCount, inRange, inK, d_keys, 0, d_lags, nullptr, nullptr);
     if (st != noErr) return st;
-    LBAD_HIP(hipEventRecord(c->align_ev, nullptr));
+    st = c->align_ev.record(nullptr);
+    if (st != noErr) return st;
     std::vector<unsigned char> host(bytes);
     LBAD_HIP(hipMemcpy(host.data(), d_keys, bytes, hipMemcpyDeviceToHost));
     const unsigned long long* keys = reinterpret_cast<const unsigned long long*>(host.data());
@@ -207,16 +184,17 @@ OSStatus LBAudioDetectiveCorpusQueryAligned(LBAudioDetectiveCorpusRef c, LBAudio
     if (!lbad::queries_ok(&inQuery, 1) || !outIndex || !outScore || !outLag) return kLBAudioDetectiveArgumentInvalid;
     if (!lbad::device_ready()) return kLBAudioDetectiveDeviceUnavailable;
     if (!lbad::corpus_ok(c, &inQuery, 1)) return kLBAudioDetectiveArgumentInvalid;
-    OSStatus st = lbad::wait_align(c);
-    if (st == noErr) st = lbad::grow(&c->d_align_out, &c->align_out_cap, 16);
+    OSStatus st = c->align_ev.wait_or_create();
+    if (st == noErr) st = c->d_align_out.reserve(16);
     if (st != noErr) return st;
     // the top-1 scan's key (LBAudioDetectiveCorpusQuery's, which the polled form returns as well), then its pair aligned
-    unsigned long long* d_key = static_cast<unsigned long long*>(c->d_align_out);
+    unsigned long long* d_key = static_cast<unsigned long long*>(c->d_align_out.get());
     int32_t* d_lag = reinterpret_cast<int32_t*>(d_key + 1);
     st = LBAudioDetectiveCorpusQueryKeyDevice(c, inQuery, inRange, 0, d_key, NULL);
     if (st == noErr) st = lbad::align_keys_impl(c, &inQuery, 1, inRange, 1, d_key, 0, d_lag, nullptr, nullptr);
     if (st != noErr) return st;
-    LBAD_HIP(hipEventRecord(c->align_ev, nullptr));
+    st = c->align_ev.record(nullptr);
+    if (st != noErr) return st;
     unsigned long long out[2] = {0ull, 0ull};
     LBAD_HIP(hipMemcpy(out, d_key, 16, hipMemcpyDeviceToHost));
     LBAudioDetectiveCorpusDecodeKey(out[0], outIndex, outScore);
@@ -240,15 +218,16 @@ OSStatus LBAudioDetectiveCorpusMatchProfile(LBAudioDetectiveCorpusRef c, LBAudio
     *outCount = n_off;
     *outFirstLag = 0;
     if (inCapacity < n_off || !outScores) return kLBAudioDetectiveArgumentInvalid;
-    OSStatus st = lbad::wait_align(c);
-    if (st == noErr) st = lbad::grow(&c->d_align_out, &c->align_out_cap, n_off * sizeof(float));
+    OSStatus st = c->align_ev.wait_or_create();
+    if (st == noErr) st = c->d_align_out.reserve(n_off * sizeof(float));
     const uint2* d_desc = nullptr;
     const uint32_t* d_words = nullptr;
     if (st == noErr) st = lbad::stage_queries(c, &inQuery, 1, &d_desc, &d_words, nullptr);
     if (st != noErr) return st;
-    float* d_out = static_cast<float*>(c->d_align_out);
+    float* d_out = static_cast<float*>(c->d_align_out.get());
     LBAD_HIP(lbad::launch_align_profile(lbad::source(c, inRange), d_words, inQuery->count, inEntry, n_off, d_out, nullptr));
-    LBAD_HIP(hipEventRecord(c->align_ev, nullptr));
+    st = c->align_ev.record(nullptr);
+    if (st != noErr) return st;
     LBAD_HIP(hipMemcpy(outScores, d_out, n_off * sizeof(float), hipMemcpyDeviceToHost));
     return noErr;
     LBAD_GUARD_END

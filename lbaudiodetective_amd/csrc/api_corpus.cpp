@@ -12,20 +12,6 @@
 namespace lbad {
 namespace {
 
-// make room for `words` words in the corpus' query staging pair (device + pinned)
-OSStatus reserve_query(LBAudioDetectiveCorpus* c, size_t words) {
-    if (c->query_cap >= words) return noErr;
-    if (c->d_query) (void)hipFree(c->d_query);
-    if (c->h_query) (void)hipHostFree(c->h_query);
-    c->d_query = nullptr;
-    c->h_query = nullptr;
-    c->query_cap = 0;
-    LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_query), words * sizeof(uint32_t)));
-    LBAD_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_query), words * sizeof(uint32_t), hipHostMallocDefault));
-    c->query_cap = (uint32_t)words;
-    return noErr;
-}
-
 // ragged corpus: the sliding scan of k_sliding.hip (any query length, any entry lengths).  A launch's query blocks travel
 // through a ring of kQuerySlots pinned + device slots, one event per slot: a call waits only for the scan that used
 // its slot kQuerySlots launches ago (long done), not for the stream -- back-to-back queries leave no gap on the GPU.
@@ -34,6 +20,15 @@ OSStatus reserve_query(LBAudioDetectiveCorpus* c, size_t words) {
 // ONE length share a pass over the corpus (eight in the systolic scan of short queries).
 constexpr uint32_t kQuerySlots = 8;
 constexpr uint32_t kScanOutWords = 16;      // per slot: 8 running maxima, the ticket, padding
+
+// every scan that used the ring (or, uniform corpus, the staging pair) is done
+OSStatus wait_scans(const LBAudioDetectiveCorpus* c) {
+    for (const Event& e : c->query_ev) {
+        OSStatus st = e.wait();
+        if (st != noErr) return st;
+    }
+    return noErr;
+}
 
 // tasks of either kind for queries of nq sub-fingerprints, from the histogram of entry lengths (Fp.m:123-136: an entry
 // longer than the query slides the query along itself, any other entry slides along the query)
@@ -78,22 +73,22 @@ OSStatus launch_ragged_blocks(LBAudioDetectiveCorpus* c, uint32_t nq, const uint
     const bool in_args = h_blocks && n_q == 1 && nq <= kSlideQueryArgSubs && !sliding_short(nq, c->ne_max) && b_min == 0;   // (the systolic scan reads d_query)
     const size_t slot_words = (all_words + 63) & ~(size_t)63;
     if (h_blocks && c->query_slot_words < slot_words) {   // (re)size the ring: everything that used it must be done
-        for (hipEvent_t e : c->query_ev)
-            if (e) LBAD_HIP(hipEventSynchronize(e));
-        c->query_slot_words = 0;
-        OSStatus st = reserve_query(c, slot_words * kQuerySlots);
+        OSStatus st = wait_scans(c);
+        if (st != noErr) return st;
+        c->query_slot_words = 0;                          // (a failed resize leaves no ring, not a ring of the old size)
+        st = c->query.reserve(slot_words * kQuerySlots);
         if (st != noErr) return st;
         c->query_slot_words = slot_words;
     }
     if (!c->d_scan_out) {
-        LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_scan_out), (size_t)kQuerySlots * kScanOutWords * 8));
+        OSStatus st = c->d_scan_out.reserve((size_t)kQuerySlots * kScanOutWords);
+        if (st != noErr) return st;
         c->scan_out_dirty = true;
     }
     if (c->scan_out_dirty) {
         // the result words must be zero between scans: the scans themselves leave them so, but a launch that failed may not
         // have -- nothing is trusted after one: everything that may still touch the words finishes, then they are cleared
-        for (hipEvent_t e : c->query_ev)
-            if (e) (void)hipEventSynchronize(e);
+        (void)wait_scans(c);
         // on the scan's own stream and awaited: the scan may run on a non-blocking stream, which a null-stream memset does
         // not order itself against (round-5 advice)
         LBAD_HIP(hipMemsetAsync(c->d_scan_out, 0, (size_t)kQuerySlots * kScanOutWords * 8, stream));
@@ -101,13 +96,13 @@ OSStatus launch_ragged_blocks(LBAudioDetectiveCorpus* c, uint32_t nq, const uint
         c->scan_out_dirty = false;
     }
     const uint32_t slot = (uint32_t)(c->query_seq++ % kQuerySlots);
-    if (!c->query_ev[slot]) LBAD_HIP(hipEventCreateWithFlags(&c->query_ev[slot], hipEventDisableTiming));
-    else LBAD_HIP(hipEventSynchronize(c->query_ev[slot]));
+    OSStatus st = c->query_ev[slot].wait_or_create();
+    if (st != noErr) return st;
     const uint32_t* h = nullptr;
     const uint32_t* dq = d_blocks;
     if (h_blocks) {
-        uint32_t* h_slot = c->h_query + (size_t)slot * c->query_slot_words;
-        uint32_t* d_slot = c->d_query + (size_t)slot * c->query_slot_words;
+        uint32_t* h_slot = c->query.host + (size_t)slot * c->query_slot_words;
+        uint32_t* d_slot = c->query.dev + (size_t)slot * c->query_slot_words;
         std::memcpy(h_slot, h_blocks, all_words * sizeof(uint32_t));
         if (!in_args) LBAD_HIP(hipMemcpyAsync(d_slot, h_slot, all_words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         h = h_slot;
@@ -123,12 +118,13 @@ OSStatus launch_ragged_blocks(LBAudioDetectiveCorpus* c, uint32_t nq, const uint
     if (sliding_needs_plan(nq, c->ne_max, n_q, tasks_a, d_scores != nullptr) && (c->plan_nq != nq || c->plan_count != c->count || c->plan_grid != sh.grid || c->plan_bmin != b_min)) {
         // scans on other streams may still read the old plan: every scan leaves its slot's event behind, and a slot is
         // reused only after its event -- the eight events cover everything that can still be running
-        for (hipEvent_t e : c->query_ev)
-            if (e) LBAD_HIP(hipEventSynchronize(e));
-        if (!c->plan_built) LBAD_HIP(hipEventCreateWithFlags(&c->plan_built, hipEventDisableTiming));
+        st = wait_scans(c);
+        if (st == noErr) st = c->plan_built.create();
+        if (st != noErr) return st;
         c->plan_nq = 0;
         LBAD_HIP(launch_sliding_plan(c->d_off, c->count, nq, b_min, sh, c->d_plan, stream));
-        LBAD_HIP(hipEventRecord(c->plan_built, stream));
+        st = c->plan_built.record(stream);
+        if (st != noErr) return st;
         c->plan_stream = stream;
         c->plan_nq = nq; c->plan_count = c->count; c->plan_grid = sh.grid; c->plan_bmin = b_min;
     } else if (c->plan_built && c->plan_stream != stream) {
@@ -152,8 +148,7 @@ OSStatus launch_ragged_blocks(LBAudioDetectiveCorpus* c, uint32_t nq, const uint
     }
     // behind the SCAN, not just the copy: the slot's device half and its result words are the kernel's, and the launch
     // that reuses the slot eight launches later may arrive on another stream
-    LBAD_HIP(hipEventRecord(c->query_ev[slot], stream));
-    return noErr;
+    return c->query_ev[slot].record(stream);
 }
 
 // ONE launch: the n_q queries qs[0..n_q) (all of qs[0]->count sub-fingerprints), their keys to keys + pos[i]
@@ -250,27 +245,16 @@ OSStatus run_query_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerp
                                             d_scores, key_dst, stream));
         return noErr;
     }
-    if (c->query_cap < slots.size()) {
-        if (c->query_ev[0]) LBAD_HIP(hipEventSynchronize(c->query_ev[0]));
-        if (c->d_query) (void)hipFree(c->d_query);
-        if (c->h_query) (void)hipHostFree(c->h_query);
-        c->d_query = nullptr;
-        c->h_query = nullptr;
-        c->query_cap = 0;
-        LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_query), slots.size() * sizeof(uint32_t)));
-        LBAD_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_query), slots.size() * sizeof(uint32_t), hipHostMallocDefault));
-        c->query_cap = (uint32_t)slots.size();
-    }
-    // the staging block and its device copy are reused by every query: wait for the previous one's SCAN (whatever
-    // stream it ran on; slot 0 of the ragged ring's events serves this path, a corpus is either ragged or not)
-    if (!c->query_ev[0]) LBAD_HIP(hipEventCreateWithFlags(&c->query_ev[0], hipEventDisableTiming));
-    else LBAD_HIP(hipEventSynchronize(c->query_ev[0]));
-    std::memcpy(c->h_query, slots.data(), slots.size() * sizeof(uint32_t));
-    LBAD_HIP(hipMemcpyAsync(c->d_query, c->h_query, slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    LBAD_HIP(launch_compare_planes_generic(c->d_planes, c->capacity, c->count, c->n_sub, c->subfp_len, c->d_query,
+    // the staging block and its device copy are reused (and regrown) by every query: wait for the previous one's SCAN
+    // (whatever stream it ran on; slot 0 of the ragged ring's events serves this path, a corpus is either ragged or not)
+    OSStatus st = c->query_ev[0].wait_or_create();
+    if (st == noErr) st = c->query.reserve(slots.size());
+    if (st != noErr) return st;
+    std::memcpy(c->query.host, slots.data(), slots.size() * sizeof(uint32_t));
+    LBAD_HIP(hipMemcpyAsync(c->query.dev, c->query.host, slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    LBAD_HIP(launch_compare_planes_generic(c->d_planes, c->capacity, c->count, c->n_sub, c->subfp_len, c->query.dev,
                                            q->count, range, index_base, d_scores, key_dst, stream));
-    LBAD_HIP(hipEventRecord(c->query_ev[0], stream));
-    return noErr;
+    return c->query_ev[0].record(stream);
 }
 
 // (host allocations -- the packed query, its constant block -- can fail: nothing may unwind through the C boundary)
@@ -285,24 +269,22 @@ OSStatus run_query(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprint*
 OSStatus query_fast_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprint* q, uint32_t range, unsigned long long* key) {
     if (!c->h_out) {
         // built in locals and committed only when everything exists: a failure leaves the corpus as it was
-        unsigned long long *d_fast = nullptr, *h_out = nullptr, *h_out_dev = nullptr;
+        DeviceBuffer<unsigned long long> d_fast;
+        PinnedBuffer<unsigned long long> h_out;
+        unsigned long long* h_out_dev = nullptr;
         OSStatus st = c->stream ? noErr : kLBAudioDetectiveDeviceError;     // created with the corpus
-        if (st == noErr) st = hip_status(hipMalloc(reinterpret_cast<void**>(&d_fast), (kScanSlots + 1) * sizeof(unsigned long long)), "hipMalloc", __LINE__);
+        if (st == noErr) st = d_fast.reserve(kScanSlots + 1);
         if (st == noErr) st = hip_status(hipMemset(d_fast, 0, (kScanSlots + 1) * sizeof(unsigned long long)), "memset", __LINE__);
-        if (st == noErr) st = hip_status(hipHostMalloc(reinterpret_cast<void**>(&h_out), 16, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc", __LINE__);
+        if (st == noErr) st = h_out.reserve(2, hipHostMallocMapped | hipHostMallocCoherent);
         if (st == noErr) {
             h_out[0] = h_out[1] = 0;
             st = hip_status(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_out_dev), h_out, 0), "device pointer", __LINE__);
         }
-        if (st != noErr || !h_out_dev) {
-            if (h_out) (void)hipHostFree(h_out);
-            if (d_fast) (void)hipFree(d_fast);
-            return st != noErr ? st : kLBAudioDetectiveDeviceError;
-        }
-        c->d_fast_key = d_fast;
+        if (st != noErr || !h_out_dev) return st != noErr ? st : kLBAudioDetectiveDeviceError;
         c->d_ticket = reinterpret_cast<unsigned int*>(d_fast + kScanSlots);
+        c->d_fast_key = std::move(d_fast);
         c->h_out_dev = h_out_dev;
-        c->h_out = h_out;
+        c->h_out = std::move(h_out);
     }
     if (range == 0) range = c->subfp_len;
     std::vector<uint32_t> slots, block;
@@ -311,7 +293,7 @@ OSStatus query_fast_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFinger
     const unsigned long long seq = ++c->seq;
     LBAD_HIP(launch_compare_planes_fast(c->d_planes, c->capacity, c->count, c->n_sub, block.data(), 0, nullptr,
                                         c->d_fast_key, c->stream, c->d_ticket, c->h_out_dev, seq));
-    volatile unsigned long long* out = c->h_out;
+    volatile unsigned long long* out = c->h_out.get();
     const auto t0 = std::chrono::steady_clock::now();
     for (uint64_t spins = 1; out[1] != seq; ++spins) {
         if ((spins & 0xFFFFF) == 0) {                       // every million polls: is the stream still alive?
@@ -359,13 +341,10 @@ LBAudioDetectiveCorpusRef LBAudioDetectiveCorpusNew(UInt32 inSubfingerprintLengt
     c->n_sub = inSubfingerprintsPerEntry;
     c->capacity = inCapacity;
     c->n_planes = lbad::planes_per_entry(inSubfingerprintLength, inSubfingerprintsPerEntry);
-    const size_t bytes = (size_t)c->n_planes * inCapacity * sizeof(uint4);
     // the polled query's own stream exists from the start, so that every append can order it behind itself
-    if (lbad::hip_status(hipMalloc(reinterpret_cast<void**>(&c->d_planes), bytes), "hipMalloc corpus", __LINE__) != noErr ||
-        lbad::hip_status(hipMalloc(reinterpret_cast<void**>(&c->d_key), 16), "hipMalloc key", __LINE__) != noErr ||
+    if (c->d_planes.reserve((size_t)c->n_planes * inCapacity) != noErr || c->d_key.reserve(2) != noErr ||
         lbad::hip_status(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "stream", __LINE__) != noErr ||
-        lbad::hip_status(hipMalloc(reinterpret_cast<void**>(&c->d_shard_keys), (size_t)LBAD_SHARD_KEYS * 8), "hipMalloc keys", __LINE__) != noErr ||
-        lbad::hip_status(hipHostMalloc(reinterpret_cast<void**>(&c->h_shard_keys), (size_t)LBAD_SHARD_KEYS * 8, hipHostMallocDefault), "keys", __LINE__) != noErr) {
+        c->d_shard_keys.reserve(LBAD_SHARD_KEYS) != noErr || c->h_shard_keys.reserve(LBAD_SHARD_KEYS) != noErr) {
         LBAudioDetectiveCorpusDispose(c);
         return NULL;
     }
@@ -395,14 +374,12 @@ LBAudioDetectiveCorpusRef LBAudioDetectiveCorpusNewRagged(UInt32 inSubfingerprin
     }
     // kRecordSlack zero records behind the capacity: the scan reads up to three records past an entry's end (offsets
     // that do not exist, never used) and takes its all-zero record from there
-    if (lbad::hip_status(hipMalloc(reinterpret_cast<void**>(&c->d_recs), ((size_t)inSubfingerprintCapacity + lbad::kRecordSlack) * 32), "hipMalloc corpus", __LINE__) != noErr ||
+    if (c->d_recs.reserve(2 * ((size_t)inSubfingerprintCapacity + lbad::kRecordSlack)) != noErr ||
         lbad::hip_status(hipMemset(c->d_recs + 2 * (size_t)inSubfingerprintCapacity, 0, (size_t)lbad::kRecordSlack * 32), "corpus slack", __LINE__) != noErr ||
-        lbad::hip_status(hipMalloc(reinterpret_cast<void**>(&c->d_off), (size_t)(inEntryCapacity + 1) * 4), "hipMalloc offsets", __LINE__) != noErr ||
+        c->d_off.reserve((size_t)inEntryCapacity + 1) != noErr ||
         lbad::hip_status(hipMemset(c->d_off, 0, 4), "offsets", __LINE__) != noErr ||
-        lbad::hip_status(hipMalloc(reinterpret_cast<void**>(&c->d_key), 16), "hipMalloc key", __LINE__) != noErr ||
-        lbad::hip_status(hipMalloc(reinterpret_cast<void**>(&c->d_plan), lbad::sliding_plan_words(inEntryCapacity) * 4), "hipMalloc plan", __LINE__) != noErr ||
-        lbad::hip_status(hipMalloc(reinterpret_cast<void**>(&c->d_shard_keys), (size_t)LBAD_SHARD_KEYS * 8), "hipMalloc keys", __LINE__) != noErr ||
-        lbad::hip_status(hipHostMalloc(reinterpret_cast<void**>(&c->h_shard_keys), (size_t)LBAD_SHARD_KEYS * 8, hipHostMallocDefault), "keys", __LINE__) != noErr) {
+        c->d_key.reserve(2) != noErr || c->d_plan.reserve(lbad::sliding_plan_words(inEntryCapacity)) != noErr ||
+        c->d_shard_keys.reserve(LBAD_SHARD_KEYS) != noErr || c->h_shard_keys.reserve(LBAD_SHARD_KEYS) != noErr) {
         LBAudioDetectiveCorpusDispose(c);
         return NULL;
     }
@@ -460,41 +437,17 @@ OSStatus LBAudioDetectiveCorpusAppendRaggedPackedDevice(LBAudioDetectiveCorpusRe
     LBAD_GUARD_END
 }
 
+// Everything that may still touch the corpus' memory is awaited first -- the plan, the scans, the top-K, alignment and packed
+// scratch, the polled query's stream -- and nothing else: NOT append_event or shard_stale_event (the latter may sit behind a
+// collective that never ends).  The members then release what they own.
 void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
     if (!c) return;
-    if (c->plan_built) { (void)hipEventSynchronize(c->plan_built); (void)hipEventDestroy(c->plan_built); }
-    if (c->d_plan) (void)hipFree(c->d_plan);
-    if (c->d_scan_out) (void)hipFree(c->d_scan_out);
-    if (c->d_shard_keys) (void)hipFree(c->d_shard_keys);
-    if (c->h_shard_keys) (void)hipHostFree(c->h_shard_keys);
-    if (c->d_recs) (void)hipFree(c->d_recs);
-    if (c->d_off) (void)hipFree(c->d_off);
-    if (c->d_planes) (void)hipFree(c->d_planes);
-    for (hipEvent_t e : c->query_ev)
-        if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
-    if (c->d_query) (void)hipFree(c->d_query);
-    if (c->h_query) (void)hipHostFree(c->h_query);
-    if (c->d_key) (void)hipFree(c->d_key);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->append_event) (void)hipEventDestroy(c->append_event);
-    if (c->shard_stale_event) (void)hipEventDestroy(c->shard_stale_event);
-    if (c->topk_ev) { (void)hipEventSynchronize(c->topk_ev); (void)hipEventDestroy(c->topk_ev); }
-    if (c->d_topk_scores) (void)hipFree(c->d_topk_scores);
-    if (c->d_topk_scratch) (void)hipFree(c->d_topk_scratch);
-    if (c->d_topk_q) (void)hipFree(c->d_topk_q);
-    if (c->h_topk_q) (void)hipHostFree(c->h_topk_q);
-    if (c->d_topk_scan_keys) (void)hipFree(c->d_topk_scan_keys);
-    if (c->d_topk_keys) (void)hipFree(c->d_topk_keys);
-    if (c->align_ev) { (void)hipEventSynchronize(c->align_ev); (void)hipEventDestroy(c->align_ev); }
-    if (c->pq_ev) { (void)hipEventSynchronize(c->pq_ev); (void)hipEventDestroy(c->pq_ev); }
-    if (c->d_pq) (void)hipFree(c->d_pq);
-    if (c->d_align_q) (void)hipFree(c->d_align_q);
-    if (c->h_align_q) (void)hipHostFree(c->h_align_q);
-    if (c->d_align_best) (void)hipFree(c->d_align_best);
-    if (c->d_align_out) (void)hipFree(c->d_align_out);
-    if (c->d_fast_key) (void)hipFree(c->d_fast_key);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    (void)c->plan_built.wait();
+    for (const lbad::Event& e : c->query_ev) (void)e.wait();
+    (void)c->topk_ev.wait();
+    (void)c->align_ev.wait();
+    (void)c->pq_ev.wait();
+    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     delete c;
 }
 
@@ -521,8 +474,9 @@ OSStatus LBAudioDetectiveCorpusAppendPackedDevice(LBAudioDetectiveCorpusRef c, c
                                       c->d_planes, c->capacity, c->count, static_cast<hipStream_t>(inStream)));
     // the polled query runs on the corpus's own stream: it waits for this event instead of keeping the caller's
     // stream handle (which may be gone by then); appends on several streams each leave their event behind
-    if (!c->append_event) LBAD_HIP(hipEventCreateWithFlags(&c->append_event, hipEventDisableTiming));
-    LBAD_HIP(hipEventRecord(c->append_event, static_cast<hipStream_t>(inStream)));
+    OSStatus st = c->append_event.create();
+    if (st == noErr) st = c->append_event.record(static_cast<hipStream_t>(inStream));
+    if (st != noErr) return st;
     if (c->stream) LBAD_HIP(hipStreamWaitEvent(c->stream, c->append_event, 0));
     c->appended = true;
     c->count += inNumberOfEntries;
@@ -535,14 +489,13 @@ OSStatus LBAudioDetectiveCorpusAppendFingerprint(LBAudioDetectiveCorpusRef c, LB
     if (c->ragged ? fp->count == 0 : fp->count != c->n_sub) return kLBAudioDetectiveArgumentInvalid;
     std::vector<uint32_t> slots;
     lbad::pack_fingerprint(fp, slots);
-    uint32_t* d = nullptr;
-    LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&d), slots.size() * 4));
-    OSStatus st = lbad::hip_status(hipMemcpy(d, slots.data(), slots.size() * 4, hipMemcpyHostToDevice), "copy", __LINE__);
+    lbad::DeviceBuffer<uint32_t> d;
+    OSStatus st = d.reserve(slots.size());
+    if (st == noErr) st = lbad::hip_status(hipMemcpy(d, slots.data(), slots.size() * 4, hipMemcpyHostToDevice), "copy", __LINE__);
     const UInt32 n = fp->count;
     if (st == noErr) st = c->ragged ? LBAudioDetectiveCorpusAppendRaggedPackedDevice(c, d, &n, 1, NULL)
                                     : LBAudioDetectiveCorpusAppendPackedDevice(c, d, 1, NULL);
     if (st == noErr) st = lbad::hip_status(hipStreamSynchronize(nullptr), "sync", __LINE__);
-    (void)hipFree(d);
     return st;
     LBAD_GUARD_END
 }
@@ -599,32 +552,22 @@ OSStatus LBAudioDetectiveCorpusQueryBatchKeysDevice(LBAudioDetectiveCorpusRef c,
     const size_t words = (size_t)inCount * kw;
     // the staging pair is shared with the single-query generic scan, which may still be running on ANOTHER stream:
     // its event (slot 0) orders every reuse, this path's too (round-3 advice)
-    if (c->query_ev[0]) LBAD_HIP(hipEventSynchronize(c->query_ev[0]));
-    if (c->query_cap < words) {
-        if (c->d_query) (void)hipFree(c->d_query);
-        if (c->h_query) (void)hipHostFree(c->h_query);
-        c->d_query = nullptr;
-        c->h_query = nullptr;
-        c->query_cap = 0;
-        LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_query), words * sizeof(uint32_t)));
-        LBAD_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_query), words * sizeof(uint32_t), hipHostMallocDefault));
-        c->query_cap = (uint32_t)words;
-    }
+    OSStatus st = c->query_ev[0].wait_or_create();
+    if (st == noErr) st = c->query.reserve(words);
+    if (st != noErr) return st;
     LBAD_HIP(hipStreamSynchronize(stream));   // the pinned staging block is reused by every call
-    std::memset(c->h_query, 0, words * sizeof(uint32_t));
+    std::memset(c->query.host, 0, words * sizeof(uint32_t));
     std::vector<uint32_t> slots, block;
     for (UInt32 i = 0; i < inCount; ++i) {
         lbad::pack_fingerprint(inQueries[i], slots);
         lbad::build_plane_query(slots.data(), c->n_sub, range, block);
-        std::memcpy(c->h_query + (size_t)i * kw, block.data(), block.size() * sizeof(uint32_t));
+        std::memcpy(c->query.host + (size_t)i * kw, block.data(), block.size() * sizeof(uint32_t));
     }
-    LBAD_HIP(hipMemcpyAsync(c->d_query, c->h_query, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    LBAD_HIP(hipMemcpyAsync(c->query.dev, c->query.host, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)inCount * sizeof(unsigned long long), stream));
-    LBAD_HIP(lbad::launch_compare_planes_batch(c->d_planes, c->capacity, c->count, c->n_sub, c->d_query, inCount,
+    LBAD_HIP(lbad::launch_compare_planes_batch(c->d_planes, c->capacity, c->count, c->n_sub, c->query.dev, inCount,
                                                inIndexBase, keys, stream));
-    if (!c->query_ev[0]) LBAD_HIP(hipEventCreateWithFlags(&c->query_ev[0], hipEventDisableTiming));
-    LBAD_HIP(hipEventRecord(c->query_ev[0], stream));
-    return noErr;
+    return c->query_ev[0].record(stream);
     LBAD_GUARD_END
 }
 
@@ -633,13 +576,12 @@ OSStatus LBAudioDetectiveCorpusQueryBatch(LBAudioDetectiveCorpusRef c, const LBA
     LBAD_GUARD_BEGIN
     if (!c || inCount == 0) return kLBAudioDetectiveArgumentInvalid;
     std::vector<unsigned long long> keys(inCount);
-    unsigned long long* d_keys = nullptr;
-    LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&d_keys), (size_t)inCount * sizeof(unsigned long long)));
-    OSStatus st = LBAudioDetectiveCorpusQueryBatchKeysDevice(c, inQueries, inCount, inRange, 0, d_keys, NULL);
+    lbad::DeviceBuffer<unsigned long long> d_keys;
+    OSStatus st = d_keys.reserve(inCount);
+    if (st == noErr) st = LBAudioDetectiveCorpusQueryBatchKeysDevice(c, inQueries, inCount, inRange, 0, d_keys, NULL);
     if (st == noErr)
         st = lbad::hip_status(hipMemcpy(keys.data(), d_keys, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost),
                               "copy keys", __LINE__);
-    (void)hipFree(d_keys);
     if (st != noErr) return st;
     for (UInt32 i = 0; i < inCount; ++i)
         LBAudioDetectiveCorpusDecodeKey(keys[i], outIndices ? outIndices + i : NULL, outScores ? outScores + i : NULL);
@@ -651,34 +593,18 @@ OSStatus LBAudioDetectiveCorpusQueryBatch(LBAudioDetectiveCorpusRef c, const LBA
 namespace lbad {
 namespace {
 
-OSStatus grow_topk(void** ptr, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return noErr;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *cap = 0;
-    LBAD_HIP(hipMalloc(ptr, bytes));
-    *cap = bytes;
-    return noErr;
-}
-
 // one query's per-entry scores (count floats) to d_scores and the scan's own key word to d_key, on the call's stream
 using ScoreScan = std::function<OSStatus(uint32_t q, float* d_scores, unsigned long long* d_key)>;
 
-// the previous top-K call's scans and selection may still read / write the scratch (on whatever stream it ran)
-OSStatus wait_topk(LBAudioDetectiveCorpus* c) {
-    if (c->topk_ev) LBAD_HIP(hipEventSynchronize(c->topk_ev));
-    else LBAD_HIP(hipEventCreateWithFlags(&c->topk_ev, hipEventDisableTiming));
-    return noErr;
-}
-
-// score rows, selection scratch and the scans' key words for a call of n queries
+// score rows, selection scratch and the scans' key words for a call of n queries (allocated exactly: the score rows are the
+// size of the corpus).  The caller has waited for topk_ev: the previous top-K call's scans and selection may still read /
+// write the scratch, on whatever stream it ran.
 OSStatus reserve_topk(LBAudioDetectiveCorpus* c, uint32_t n) {
     const uint32_t rows = n < kQueryBatchMax ? n : kQueryBatchMax;
-    OSStatus st = grow_topk(reinterpret_cast<void**>(&c->d_topk_scores), &c->topk_scores_cap, (size_t)rows * c->count * sizeof(float));
-    if (st == noErr) st = grow_topk(&c->d_topk_scratch, &c->topk_scratch_cap, topk_scratch_bytes(rows));
-    if (st != noErr) return st;
-    if (!c->d_topk_scan_keys) LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_topk_scan_keys), kQueryBatchMax * sizeof(unsigned long long)));
-    return noErr;
+    OSStatus st = c->d_topk_scores.reserve((size_t)rows * c->count);
+    if (st == noErr) st = c->d_topk_scratch.reserve(topk_scratch_bytes(rows));
+    if (st == noErr) st = c->d_topk_scan_keys.reserve(kQueryBatchMax);
+    return st;
 }
 
 // The scans and the selection of n staged queries, their keys to keys (device, n x k): groups of up to kQueryBatchMax queries
@@ -714,44 +640,34 @@ OSStatus topk_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerp
     if (range == 0) range = c->subfp_len;   // LBAudioDetective.m:443-445
     bool batch_scan = !c->ragged && c->variant != 1;
     for (uint32_t i = 0; i < n && batch_scan; ++i) batch_scan = planes_fast_supported(c->subfp_len, c->n_sub, qs[i]->count);
-    OSStatus st = wait_topk(c);
+    OSStatus st = c->topk_ev.wait_or_create();
     if (st != noErr) return st;
     if (c->count == 0) {
         LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * k * sizeof(unsigned long long), stream));
-        LBAD_HIP(hipEventRecord(c->topk_ev, stream));
-        return noErr;
+        return c->topk_ev.record(stream);
     }
     st = reserve_topk(c, n);
     if (st != noErr) return st;
     const uint32_t kw = plane_query_words();
     if (batch_scan) {
         const size_t bytes = (size_t)n * kw * sizeof(uint32_t);   // every group's blocks at once: the copies are asynchronous
-        if (c->topk_q_cap < bytes) {
-            if (c->d_topk_q) (void)hipFree(c->d_topk_q);
-            if (c->h_topk_q) (void)hipHostFree(c->h_topk_q);
-            c->d_topk_q = nullptr;
-            c->h_topk_q = nullptr;
-            c->topk_q_cap = 0;
-            LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_topk_q), bytes));
-            LBAD_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->h_topk_q), bytes, hipHostMallocDefault));
-            c->topk_q_cap = bytes;
-        }
-        std::memset(c->h_topk_q, 0, bytes);
+        st = c->topk_q.reserve((size_t)n * kw);
+        if (st != noErr) return st;
+        std::memset(c->topk_q.host, 0, bytes);
         std::vector<uint32_t> slots, block;
         for (uint32_t i = 0; i < n; ++i) {
             pack_fingerprint(qs[i], slots);
             build_plane_query(slots.data(), c->n_sub, range, block);
-            std::memcpy(c->h_topk_q + (size_t)i * kw, block.data(), block.size() * sizeof(uint32_t));
+            std::memcpy(c->topk_q.host + (size_t)i * kw, block.data(), block.size() * sizeof(uint32_t));
         }
-        LBAD_HIP(hipMemcpyAsync(c->d_topk_q, c->h_topk_q, bytes, hipMemcpyHostToDevice, stream));
+        LBAD_HIP(hipMemcpyAsync(c->topk_q.dev, c->topk_q.host, bytes, hipMemcpyHostToDevice, stream));
     }
-    st = topk_scan_select(c, n, k, index_base, keys, stream, batch_scan ? c->d_topk_q : nullptr,
+    st = topk_scan_select(c, n, k, index_base, keys, stream, batch_scan ? c->topk_q.dev.get() : nullptr,
                           [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
                               return run_query(c, qs[q], range, 0, d_scores, d_key, stream);
                           });
     if (st != noErr) return st;
-    LBAD_HIP(hipEventRecord(c->topk_ev, stream));
-    return noErr;
+    return c->topk_ev.record(stream);
 }
 
 // ---- packed queries: the blocks come from the builders of k_query.hip instead of the handles' Booleans ---------------------
@@ -779,12 +695,10 @@ OSStatus build_packed(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_
     // (every part starts on a 256-byte boundary, as the staging slots of the handle path do)
     const size_t desc_words = lags ? (((size_t)2 * n + 63) & ~(size_t)63) : 0;
     const size_t align_words = lags && !rows_serve_both ? ((row_words + 63) & ~(size_t)63) : 0;
-    const size_t bytes = (desc_words + align_words + scan_words) * sizeof(uint32_t);
-    if (c->pq_ev) LBAD_HIP(hipEventSynchronize(c->pq_ev));
-    else LBAD_HIP(hipEventCreateWithFlags(&c->pq_ev, hipEventDisableTiming));
-    OSStatus st = grow_topk(reinterpret_cast<void**>(&c->d_pq), &c->pq_cap, bytes);
+    OSStatus st = c->pq_ev.wait_or_create();
+    if (st == noErr) st = c->d_pq.reserve(desc_words + align_words + scan_words);
     if (st != noErr) return st;
-    uint2* desc = lags ? reinterpret_cast<uint2*>(c->d_pq) : nullptr;
+    uint2* desc = lags ? reinterpret_cast<uint2*>(c->d_pq.get()) : nullptr;
     uint32_t* words = c->d_pq + desc_words;
     uint32_t* scan = words + align_words;
     if (c->ragged) {
@@ -834,7 +748,7 @@ OSStatus packed_keys_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uin
     } else {
         for (uint32_t q = 0; q < n && st == noErr; ++q) st = scan_built_one(c, b, q, per, range, index_base, nullptr, keys + q, stream);
     }
-    const OSStatus rec = hip_status(hipEventRecord(c->pq_ev, stream), "event", __LINE__);     // (also behind what a failed call did launch)
+    const OSStatus rec = c->pq_ev.record(stream);     // (also behind what a failed call did launch)
     return st != noErr ? st : rec;
 }
 
@@ -844,7 +758,7 @@ OSStatus packed_topk_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uin
     if (index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
     if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
     if (range == 0) range = c->subfp_len;
-    OSStatus st = wait_topk(c);
+    OSStatus st = c->topk_ev.wait_or_create();
     if (st != noErr) return st;
     BuiltQueries b;
     st = build_packed(c, d_rows, n, per, range, lags != nullptr, stream, b);
@@ -860,10 +774,10 @@ OSStatus packed_topk_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uin
                                       return scan_built_one(c, b, q, per, range, 0, d_scores, d_key, stream);
                                   });
     }
-    OSStatus rec = hip_status(hipEventRecord(c->topk_ev, stream), "event", __LINE__);
+    OSStatus rec = c->topk_ev.record(stream);
     if (st == noErr && rec == noErr && lags && c->count != 0)
         st = align_keys_built(c, b.desc, b.words, n, per, range, k, keys, index_base, lags, stream);
-    const OSStatus rec2 = hip_status(hipEventRecord(c->pq_ev, stream), "event", __LINE__);
+    const OSStatus rec2 = c->pq_ev.record(stream);
     return st != noErr ? st : (rec != noErr ? rec : rec2);
 }
 
@@ -871,9 +785,9 @@ OSStatus packed_topk_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uin
 OSStatus topk_host_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range, uint32_t k,
                         SInt64* out_idx, Float32* out_scores, UInt32* out_counts) {
     if (!c || !qs || n == 0 || k == 0 || k > kTopKMax || !out_idx || !out_scores || !out_counts) return kLBAudioDetectiveArgumentInvalid;
-    if (c->topk_ev) LBAD_HIP(hipEventSynchronize(c->topk_ev));    // (the key buffer is the previous call's until then)
+    OSStatus st = c->topk_ev.wait();    // (the key buffer is the previous call's until then)
     const size_t words = (size_t)n * k;
-    OSStatus st = grow_topk(reinterpret_cast<void**>(&c->d_topk_keys), &c->topk_keys_cap, words * sizeof(unsigned long long));
+    if (st == noErr) st = c->d_topk_keys.reserve(words);
     if (st == noErr) st = topk_keys_impl(c, qs, n, range, k, 0, c->d_topk_keys, nullptr);
     if (st != noErr) return st;
     std::vector<unsigned long long> keys(words);
@@ -982,14 +896,14 @@ OSStatus LBAudioDetectiveDebugQueryBlocks(UInt32 inKind, const void* inPackedQue
         return noErr;
     }
     if (!lbad::device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    uint32_t* d = nullptr;
-    LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&d), words * sizeof(uint32_t)));
+    lbad::DeviceBuffer<uint32_t> d;
+    OSStatus st = d.reserve(words);
+    if (st != noErr) return st;
     const uint32_t* rows = static_cast<const uint32_t*>(inPackedQueries);
     hipError_t e = inKind == 0   ? lbad::launch_build_plane_queries(rows, inCount, inPer, range, d, nullptr)
                    : inKind == 1 ? lbad::launch_build_sliding_queries(rows, inCount, inPer, L, range, d, nullptr)
                                  : lbad::launch_build_query_rows(rows, inCount, inPer, L, inKind == 2, d, nullptr, nullptr);
     if (e == hipSuccess) e = hipMemcpy(outWords, d, words * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     return lbad::hip_status(e, "query blocks", __LINE__);
     LBAD_GUARD_END
 }
@@ -1003,16 +917,15 @@ OSStatus LBAudioDetectiveTopKKeysFromScoresDevice(const Float32* inScores, UInt6
     unsigned long long* keys = static_cast<unsigned long long*>(outKeys);
     constexpr uint32_t kRowsPerLaunch = 64;                // bounds the scratch (about 11 MiB)
     const uint32_t rows = inRows < kRowsPerLaunch ? inRows : kRowsPerLaunch;
-    void* scratch = nullptr;
-    LBAD_HIP(hipMalloc(&scratch, lbad::topk_scratch_bytes(rows)));
-    OSStatus st = noErr;
+    lbad::DeviceBuffer<void> scratch;
+    OSStatus st = scratch.reserve(lbad::topk_scratch_bytes(rows));
+    if (st != noErr) return st;
     for (uint32_t r0 = 0; r0 < inRows && st == noErr; r0 += rows) {
         const uint32_t g = inRows - r0 < rows ? inRows - r0 : rows;
         st = lbad::hip_status(lbad::launch_topk_keys(inScores + (size_t)r0 * inCount, inCount, g, inK, inIndexBase, scratch,
                                                      keys + (size_t)r0 * inK, stream), "top-K selection", __LINE__);
     }
     const OSStatus done = lbad::hip_status(hipStreamSynchronize(stream), "top-K selection", __LINE__);
-    (void)hipFree(scratch);
     return st != noErr ? st : done;
     LBAD_GUARD_END
 }

@@ -20,13 +20,7 @@ uint64_t subfingerprint_count(uint64_t n_samples, uint32_t window, uint32_t stri
 
 static bool valid_window(uint32_t w) { return w >= kMinWindow && w <= kMaxWindow && (w & (w - 1)) == 0; }
 
-static void free_plan(Plan& p) {
-    if (p.d_tw) (void)hipFree(p.d_tw);
-    if (p.d_bands) (void)hipFree(p.d_bands);
-    if (p.d_bin_const) (void)hipFree(p.d_bin_const);
-    if (p.d_claim) (void)hipFree(p.d_claim);
-    p = Plan();
-}
+static void free_plan(Plan& p) { p = Plan(); }
 
 // stride-dependent part of a plan: which specialised stage-1 kernels apply, and their tables
 static OSStatus plan_kernels(Plan& p) {
@@ -34,14 +28,14 @@ static OSStatus plan_kernels(Plan& p) {
     if (p.pruned_ok && !p.d_bin_const) {
         std::vector<float> bc;
         rows_pruned_constants(bc);
-        LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&p.d_bin_const), bc.size() * sizeof(float)));
+        OSStatus st = p.d_bin_const.reserve(bc.size());
+        if (st != noErr) return st;
         LBAD_HIP(hipMemcpy(p.d_bin_const, bc.data(), bc.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     p.full_ok = rows_full_supported(p);
     p.stream_ok = rows_stream_supported(p);
     p.stream2_ok = rows_stream2_supported(p);
-    if ((p.full_ok || p.stream_ok || p.stream2_ok) && !p.d_claim) LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&p.d_claim), 8 * sizeof(uint32_t)));
-    return noErr;
+    return p.full_ok || p.stream_ok || p.stream2_ok ? p.d_claim.reserve(8) : noErr;
 }
 
 // (re)build the device tables when the configuration changed since the last call
@@ -81,7 +75,8 @@ OSStatus ensure_plan(LBAudioDetective* d) {
     std::vector<float> re, im;
     make_twiddles(p.window, re, im);
     const size_t half = p.window / 2;
-    LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&p.d_tw), 2 * half * sizeof(float)));
+    OSStatus st = p.d_tw.reserve(2 * half);
+    if (st != noErr) return st;
     LBAD_HIP(hipMemcpy(p.d_tw, re.data(), half * sizeof(float), hipMemcpyHostToDevice));
     LBAD_HIP(hipMemcpy(p.d_tw + half, im.data(), half * sizeof(float), hipMemcpyHostToDevice));
     plan_sparse(p);
@@ -111,21 +106,12 @@ OSStatus ensure_plan(LBAudioDetective* d) {
         tbl[10 * p.bands + b] = band_div_proven(div) ? 1u : 0u;
     }
     tbl[8 * (size_t)p.bands] = p.table.term_end;
-    LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&p.d_bands), tbl.size() * sizeof(uint32_t)));
+    st = p.d_bands.reserve(tbl.size());
+    if (st != noErr) return st;
     LBAD_HIP(hipMemcpy(p.d_bands, tbl.data(), tbl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    OSStatus st = plan_kernels(p);
+    st = plan_kernels(p);
     if (st != noErr) return st;
     p.valid = true;
-    return noErr;
-}
-
-static OSStatus ensure_scratch(LBAudioDetective* d, uint64_t floats) {
-    if (d->d_frames_cap >= floats) return noErr;
-    if (d->d_frames) (void)hipFree(d->d_frames);
-    d->d_frames = nullptr;
-    d->d_frames_cap = 0;
-    LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_frames), floats * sizeof(float)));
-    d->d_frames_cap = floats;
     return noErr;
 }
 
@@ -228,7 +214,7 @@ OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, ui
     uint64_t chunk = (d->scratch_limit / sizeof(float)) / (per * frame_floats);
     if (chunk == 0) chunk = 1;
     if (chunk > n_clips) chunk = n_clips;
-    st = ensure_scratch(d, chunk * per * frame_floats);
+    st = d->d_frames.reserve(chunk * per * frame_floats);
     if (st != noErr) return st;
     auto mark = [&]() -> hipError_t {   // events accumulate over calls until SetStageTiming resets them
         if (!d->timing) return hipSuccess;
@@ -260,33 +246,13 @@ OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, ui
 // allocation per call.
 constexpr size_t kPinnedLimit = 512u << 10;  // larger transfers go straight from the caller's memory (measured: staging 1.6 MB costs more than it saves)
 
-OSStatus grow_device(void** ptr, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return noErr;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 4;
-    LBAD_HIP(hipMalloc(ptr, want));
-    *cap = want;
-    return noErr;
-}
-
 static OSStatus ensure_io(LBAudioDetective* d, size_t pcm_bytes, size_t packed_bytes, size_t extra_bytes) {
-    OSStatus st = grow_device(&d->d_io_pcm, &d->d_io_pcm_cap, pcm_bytes + extra_bytes + 256);
-    if (st != noErr) return st;
-    st = grow_device(reinterpret_cast<void**>(&d->d_io_packed), &d->d_io_packed_cap, packed_bytes);
+    OSStatus st = d->d_io_pcm.reserve_slack(pcm_bytes + extra_bytes + 256);
+    if (st == noErr) st = d->d_io_packed.reserve_slack(packed_bytes / sizeof(uint32_t));
     if (st != noErr) return st;
     if (!d->io_stream) LBAD_HIP(hipStreamCreateWithFlags(&d->io_stream, hipStreamNonBlocking));
     const size_t stage = pcm_bytes + packed_bytes + extra_bytes;
-    if (stage <= kPinnedLimit && d->h_io_cap < stage) {
-        if (d->h_io) (void)hipHostFree(d->h_io);
-        d->h_io = nullptr;
-        d->h_io_cap = 0;
-        const size_t want = stage + stage / 4;
-        LBAD_HIP(hipHostMalloc(&d->h_io, want, hipHostMallocDefault));
-        d->h_io_cap = want;
-    }
-    return noErr;
+    return stage <= kPinnedLimit ? d->h_io.reserve_slack(stage) : noErr;
 }
 
 // host clips -> Booleans through the persistent buffers.  `tail`/`tbl_words` describe the end-of-file
@@ -305,9 +271,9 @@ static OSStatus fingerprint_clips_host(LBAudioDetective* d, const void* clips, u
     st = ensure_io(d, pcm_pad, packed_bytes, tbl_bytes);
     if (st != noErr) return st;
     hipStream_t stream = d->io_stream;
-    char* dev = static_cast<char*>(d->d_io_pcm);
+    char* dev = static_cast<char*>(d->d_io_pcm.get());
     const bool pinned = pcm_pad + packed_bytes + tbl_bytes <= kPinnedLimit;
-    char* stage = static_cast<char*>(d->h_io);
+    char* stage = static_cast<char*>(d->h_io.get());
     std::vector<uint32_t> packed_big;
     uint32_t* packed_host;
     if (pinned) {
@@ -342,22 +308,16 @@ OSStatus device_phase(LBAudioDetective* d, const PhaseTable* host, hipStream_t s
         DevPhase e;
         e.host = host;
         const size_t q = (size_t)host->q;
-        OSStatus st = hip_status(hipMalloc(reinterpret_cast<void**>(&e.first), q * 4), "phase table", __LINE__);
-        if (st == noErr) st = hip_status(hipMalloc(reinterpret_cast<void**>(&e.count), q * 4), "phase table", __LINE__);
-        if (st == noErr) st = hip_status(hipMalloc(reinterpret_cast<void**>(&e.wsum), q * 8), "phase table", __LINE__);
-        if (st == noErr) st = hip_status(hipMalloc(reinterpret_cast<void**>(&e.w), host->w.size() * 8), "phase table", __LINE__);
+        OSStatus st = e.first.reserve(q);
+        if (st == noErr) st = e.count.reserve(q);
+        if (st == noErr) st = e.wsum.reserve(q);
+        if (st == noErr) st = e.w.reserve(host->w.size());
         if (st == noErr) st = hip_status(hipMemcpyAsync(e.first, host->first.data(), q * 4, hipMemcpyHostToDevice, stream), "phase table", __LINE__);
         if (st == noErr) st = hip_status(hipMemcpyAsync(e.count, host->count.data(), q * 4, hipMemcpyHostToDevice, stream), "phase table", __LINE__);
         if (st == noErr) st = hip_status(hipMemcpyAsync(e.wsum, host->wsum.data(), q * 8, hipMemcpyHostToDevice, stream), "phase table", __LINE__);
         if (st == noErr) st = hip_status(hipMemcpyAsync(e.w, host->w.data(), host->w.size() * 8, hipMemcpyHostToDevice, stream), "phase table", __LINE__);
-        if (st != noErr) {
-            if (e.first) (void)hipFree(e.first);
-            if (e.count) (void)hipFree(e.count);
-            if (e.wsum) (void)hipFree(e.wsum);
-            if (e.w) (void)hipFree(e.w);
-            return st;
-        }
-        d->d_phases.push_back(e);           // (the host table lives for the life of the process: pageable copies may finish late)
+        if (st != noErr) return st;
+        d->d_phases.push_back(std::move(e));           // (the host table lives for the life of the process: pageable copies may finish late)
         found = &d->d_phases.back();
     }
     f.ph_p = host->p; f.ph_q = host->q; f.ph_m_min = host->m_min; f.ph_m_span = host->m_span;
@@ -376,13 +336,10 @@ static OSStatus convert_file_on_device(LBAudioDetective* d, const AudioPayload& 
     if (a.count == 0) return noErr;
     out.resize(rp.n_out);
     if (rp.n_out == 0) return noErr;
-    OSStatus st = grow_device(&d->d_rs_bytes, &d->d_rs_bytes_cap, a.len);
-    if (st != noErr) return st;
-    st = grow_device(&d->d_rs_in, &d->d_rs_in_cap, a.total_frames * sizeof(float));
-    if (st != noErr) return st;
-    st = grow_device(&d->d_rs_out, &d->d_rs_out_cap, rp.n_out * sizeof(float));
-    if (st != noErr) return st;
-    st = grow_device(&d->d_rs_desc, &d->d_rs_desc_cap, sizeof(FileDesc));
+    OSStatus st = d->d_rs_bytes[0].reserve_slack(a.len);
+    if (st == noErr) st = d->d_rs_in.reserve_slack(a.total_frames);
+    if (st == noErr) st = d->d_rs_out.reserve_slack(rp.n_out);
+    if (st == noErr) st = d->d_rs_desc.reserve_slack(1);
     if (st != noErr) return st;
     if (!d->io_stream) LBAD_HIP(hipStreamCreateWithFlags(&d->io_stream, hipStreamNonBlocking));
     hipStream_t stream = d->io_stream;
@@ -395,23 +352,23 @@ static OSStatus convert_file_on_device(LBAudioDetective* d, const AudioPayload& 
     f.ratio = rp.ratio; f.scale = rp.scale; f.half = rp.half;
     st = device_phase(d, rp.copy ? nullptr : rp.phases, stream, f);
     if (st != noErr) return st;
-    LBAD_HIP(hipMemcpyAsync(d->d_rs_bytes, a.bytes + a.off, a.len, hipMemcpyHostToDevice, stream));
+    LBAD_HIP(hipMemcpyAsync(d->d_rs_bytes[0], a.bytes + a.off, a.len, hipMemcpyHostToDevice, stream));
     LBAD_HIP(hipMemcpyAsync(d->d_rs_desc, &f, sizeof(f), hipMemcpyHostToDevice, stream));
     const double* d_table = nullptr;
     uint64_t table_n = 0;
     if (!rp.copy && mode < 2) {
         table_n = rp.table->size();
         if (!d->d_rs_table[mode]) {
-            LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_rs_table[mode]), table_n * sizeof(double)));
+            st = d->d_rs_table[mode].reserve(table_n);
+            if (st != noErr) return st;
             LBAD_HIP(hipMemcpyAsync(d->d_rs_table[mode], rp.table->data(), table_n * sizeof(double), hipMemcpyHostToDevice, stream));
         }
         d_table = d->d_rs_table[mode];
     }
-    const FileDesc* d_files = static_cast<const FileDesc*>(d->d_rs_desc);
+    const FileDesc* d_files = d->d_rs_desc;
     const uint64_t units = a.kind == AudioPayload::Ima4 ? a.total_frames / 64 : a.total_frames;
-    LBAD_HIP(launch_decode_batch(d_files, 1, units, static_cast<const uint8_t*>(d->d_rs_bytes), static_cast<float*>(d->d_rs_in), stream));
-    LBAD_HIP(launch_resample_batch(d_files, 1, rp.n_out, static_cast<const float*>(d->d_rs_in), rp.table_res, d_table, table_n,
-                                   static_cast<float*>(d->d_rs_out), stream));
+    LBAD_HIP(launch_decode_batch(d_files, 1, units, d->d_rs_bytes[0], d->d_rs_in, stream));
+    LBAD_HIP(launch_resample_batch(d_files, 1, rp.n_out, d->d_rs_in, rp.table_res, d_table, table_n, d->d_rs_out, stream));
     LBAD_HIP(hipMemcpyAsync(out.data(), d->d_rs_out, rp.n_out * sizeof(float), hipMemcpyDeviceToHost, stream));
     LBAD_HIP(hipStreamSynchronize(stream));
     return noErr;
@@ -446,32 +403,13 @@ LBAudioDetectiveRef LBAudioDetectiveNew(void) {  // :77-90
     return d;
 }
 
+// The uploads of a file batch are awaited (as they always were), the streams and events go, and the members release the memory.
 OSStatus LBAudioDetectiveDispose(LBAudioDetectiveRef inDetective) {  // :92-111
     if (inDetective == NULL) return kLBAudioDetectiveArgumentInvalid;
-    lbad::free_plan(inDetective->plan);
-    if (inDetective->d_frames) (void)hipFree(inDetective->d_frames);
-    if (inDetective->d_io_pcm) (void)hipFree(inDetective->d_io_pcm);
-    if (inDetective->d_io_packed) (void)hipFree(inDetective->d_io_packed);
-    if (inDetective->h_io) (void)hipHostFree(inDetective->h_io);
-    if (inDetective->d_rs_bytes) (void)hipFree(inDetective->d_rs_bytes);
-    if (inDetective->d_rs_bytes_b) (void)hipFree(inDetective->d_rs_bytes_b);
     if (inDetective->up_stream) { (void)hipStreamSynchronize(inDetective->up_stream); (void)hipStreamDestroy(inDetective->up_stream); }
     for (hipEvent_t e : inDetective->up_done) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : inDetective->bytes_free) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : inDetective->packed_done) if (e) (void)hipEventDestroy(e);
-    if (inDetective->h_files_b) (void)hipHostFree(inDetective->h_files_b);
-    if (inDetective->h_packed_b) (void)hipHostFree(inDetective->h_packed_b);
-    if (inDetective->d_rs_in) (void)hipFree(inDetective->d_rs_in);
-    if (inDetective->d_rs_out) (void)hipFree(inDetective->d_rs_out);
-    if (inDetective->d_rs_tail) (void)hipFree(inDetective->d_rs_tail);
-    if (inDetective->d_rs_desc) (void)hipFree(inDetective->d_rs_desc);
-    if (inDetective->h_files) (void)hipHostFree(inDetective->h_files);
-    if (inDetective->h_packed) (void)hipHostFree(inDetective->h_packed);
-    for (double* t : inDetective->d_rs_table)
-        if (t) (void)hipFree(t);
-    for (lbad::DevPhase& e : inDetective->d_phases) {
-        (void)hipFree(e.first); (void)hipFree(e.count); (void)hipFree(e.wsum); (void)hipFree(e.w);
-    }
     if (inDetective->io_stream) (void)hipStreamDestroy(inDetective->io_stream);
     for (hipEvent_t e : inDetective->ev) (void)hipEventDestroy(e);
     if (inDetective->done) (void)hipEventDestroy(inDetective->done);
@@ -1012,13 +950,12 @@ OSStatus LBAudioDetectiveProbeShaderClock(void* inStream, UInt32 inMicroseconds,
     if (!outMegahertz || inMicroseconds == 0 || inMicroseconds > 1000000u) return kLBAudioDetectiveArgumentInvalid;
     if (!lbad::device_ready()) return kLBAudioDetectiveDeviceUnavailable;
     hipStream_t stream = static_cast<hipStream_t>(inStream);
-    unsigned long long* d = nullptr;
+    lbad::DeviceBuffer<unsigned long long> d;
     unsigned long long h[2] = {0, 0};
-    LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&d), sizeof(h)));
-    OSStatus st = lbad::hip_status(lbad::launch_clock_probe(inMicroseconds, d, stream), "clock probe", __LINE__);
+    OSStatus st = d.reserve(2);
+    if (st == noErr) st = lbad::hip_status(lbad::launch_clock_probe(inMicroseconds, d, stream), "clock probe", __LINE__);
     if (st == noErr) st = lbad::hip_status(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, stream), "copy", __LINE__);
     if (st == noErr) st = lbad::hip_status(hipStreamSynchronize(stream), "sync", __LINE__);
-    (void)hipFree(d);
     if (st != noErr) return st;
     *outMegahertz = h[1] ? 100.0 * (double)h[0] / (double)h[1] : 0.0;
     return noErr;
@@ -1044,6 +981,12 @@ OSStatus LBAudioDetectiveDeviceCopyIn(void* inDevice, const void* inHost, UInt64
 }
 OSStatus LBAudioDetectiveDeviceCopyOut(void* inHost, const void* inDevice, UInt64 inBytes) {
     LBAD_HIP(hipMemcpy(inHost, inDevice, inBytes, hipMemcpyDeviceToHost));
+    return noErr;
+}
+OSStatus LBAudioDetectiveDebugLiveBytes(UInt64* outDevice, UInt64* outPinned) {
+    if (!outDevice || !outPinned) return kLBAudioDetectiveArgumentInvalid;
+    *outDevice = lbad::g_live_bytes[0].load();
+    *outPinned = lbad::g_live_bytes[1].load();
     return noErr;
 }
 OSStatus LBAudioDetectiveDeviceSynchronize(void) {

@@ -60,17 +60,6 @@ struct StrideGuard {
     ~StrideGuard() { d->stride = saved; }
 };
 
-OSStatus grow_pinned(void** ptr, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return noErr;
-    if (*ptr) (void)hipHostFree(*ptr);
-    *ptr = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 4;
-    LBAD_HIP(hipHostMalloc(ptr, want, hipHostMallocDefault));
-    *cap = want;
-    return noErr;
-}
-
 // The threads that read and parse the files of a batch: started once (a std::thread costs ~20 us to create, sixteen of them
 // were a third of the read phase), parked on a condition variable between calls, shared by every detective of the process.
 class ReadPool {
@@ -231,17 +220,15 @@ OSStatus enqueue_group(LBAudioDetective* d, std::vector<Job>& jobs, std::vector<
     const uint64_t T = total_frames * G + W;                       // samples of the clip: exactly total_frames frames
     const size_t packed_bytes = (size_t)total_frames * LBAD_PACKED_BYTES;
 
-    OSStatus st = grow_device(&d->d_rs_in, &d->d_rs_in_cap, dec_total * sizeof(float));
-    if (st == noErr) st = grow_device(&d->d_rs_out, &d->d_rs_out_cap, T * sizeof(float));
-    if (st == noErr) st = grow_device(reinterpret_cast<void**>(&d->d_io_packed), &d->d_io_packed_cap, packed_bytes);
-    if (st == noErr && tbl_words) st = grow_device(&d->d_rs_tail, &d->d_rs_tail_cap, tbl_words * sizeof(uint32_t));
-    void** h_packed = slot ? &d->h_packed_b : &d->h_packed;
-    size_t* h_packed_cap = slot ? &d->h_packed_b_cap : &d->h_packed_cap;
-    if (st == noErr) st = grow_pinned(h_packed, h_packed_cap, packed_bytes);
+    OSStatus st = d->d_rs_in.reserve_slack(dec_total);
+    if (st == noErr) st = d->d_rs_out.reserve_slack(T);
+    if (st == noErr) st = d->d_io_packed.reserve_slack(packed_bytes / sizeof(uint32_t));
+    if (st == noErr) st = d->d_rs_tail.reserve_slack(tbl_words);
+    if (st == noErr) st = d->h_packed[slot].reserve_slack(packed_bytes / sizeof(uint32_t));
     if (st != noErr) return st;
     LBAD_T(g0);
     hipStream_t stream = d->io_stream;                             // the payload bytes are on their way on this stream
-    float* pcm = static_cast<float*>(d->d_rs_out);
+    float* pcm = d->d_rs_out;
     LBAD_HIP(hipMemsetAsync(pcm, 0, T * sizeof(float), stream));   // the slots' zero padding
 
     // tail mode 2: nRead shrinks monotonically over the short windows (:252,275: in/out argument)
@@ -296,7 +283,7 @@ OSStatus enqueue_group(LBAudioDetective* d, std::vector<Job>& jobs, std::vector<
             t.mode = 2;
             t.first_short = j.first_short;
             t.n_client = j.n_client;
-            t.d_tbl = j.tbl_n ? static_cast<const uint32_t*>(d->d_rs_tail) + j.tbl0 : nullptr;
+            t.d_tbl = j.tbl_n ? d->d_rs_tail + j.tbl0 : nullptr;
             t.row_begin = f.row_begin;
             t.rows = f.rows;
             t.pcm_begin = f.out_off;
@@ -304,9 +291,9 @@ OSStatus enqueue_group(LBAudioDetective* d, std::vector<Job>& jobs, std::vector<
         }
     }
     const size_t desc_bytes = descs.size() * sizeof(FileDesc);
-    st = grow_device(&d->d_rs_desc, &d->d_rs_desc_cap, desc_bytes);
+    st = d->d_rs_desc.reserve_slack(descs.size());
     if (st != noErr) return st;
-    const FileDesc* d_files = static_cast<const FileDesc*>(d->d_rs_desc);
+    const FileDesc* d_files = d->d_rs_desc;
     LBAD_HIP(hipMemcpyAsync(d->d_rs_desc, descs.data(), desc_bytes, hipMemcpyHostToDevice, stream));
     const double* d_table = nullptr;
     uint64_t table_n = 0;
@@ -318,16 +305,15 @@ OSStatus enqueue_group(LBAudioDetective* d, std::vector<Job>& jobs, std::vector<
         table_n = rp->table->size();
         table_res = rp->table_res;
         if (!d->d_rs_table[mode]) {
-            LBAD_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_rs_table[mode]), table_n * sizeof(double)));
+            st = d->d_rs_table[mode].reserve(table_n);
+            if (st != noErr) return st;
             LBAD_HIP(hipMemcpyAsync(d->d_rs_table[mode], rp->table->data(), table_n * sizeof(double), hipMemcpyHostToDevice, stream));
         }
         d_table = d->d_rs_table[mode];
     }
-    LBAD_HIP(launch_decode_batch(d_files, (uint32_t)descs.size(), max_units,
-                                 static_cast<const uint8_t*>(slot ? d->d_rs_bytes_b : d->d_rs_bytes), static_cast<float*>(d->d_rs_in), stream));
+    LBAD_HIP(launch_decode_batch(d_files, (uint32_t)descs.size(), max_units, d->d_rs_bytes[slot], d->d_rs_in, stream));
     if (d->bytes_free[slot]) LBAD_HIP(hipEventRecord(d->bytes_free[slot], stream));   // the slot's payloads may be replaced from here on
-    LBAD_HIP(launch_resample_batch(d_files, (uint32_t)descs.size(), max_out, static_cast<const float*>(d->d_rs_in), table_res,
-                                   d_table, table_n, pcm, stream));
+    LBAD_HIP(launch_resample_batch(d_files, (uint32_t)descs.size(), max_out, d->d_rs_in, table_res, d_table, table_n, pcm, stream));
     if (d->hop_mode == 1 && d->tail_mode == 1 && max_short) {
         FileTail t;
         t.mode = 3;
@@ -346,7 +332,7 @@ OSStatus enqueue_group(LBAudioDetective* d, std::vector<Job>& jobs, std::vector<
                                           tails.empty() ? nullptr : tails.data(), tails.size());
     }
     if (st != noErr) return st;
-    p.packed = static_cast<uint32_t*>(*h_packed);
+    p.packed = d->h_packed[slot];
     LBAD_HIP(hipMemcpyAsync(p.packed, d->d_io_packed, packed_bytes, hipMemcpyDeviceToHost, stream));
     if (!d->packed_done[slot]) LBAD_HIP(hipEventCreateWithFlags(&d->packed_done[slot], hipEventDisableTiming));
     LBAD_HIP(hipEventRecord(d->packed_done[slot], stream));
@@ -555,15 +541,11 @@ OSStatus process_audio_files(LBAudioDetective* d, const char* const* paths, size
             }
             ++run_e;
         }
-        void** h_files = slot ? &d->h_files_b : &d->h_files;
-        size_t* h_files_cap = slot ? &d->h_files_b_cap : &d->h_files_cap;
         // (sized for the call's largest run at once: the short first runs must not make the later ones re-allocate)
         const uint64_t largest = all_bytes < kRunBytes ? all_bytes : kRunBytes;
         const uint64_t block = d->file_pipeline && total < largest ? largest : total;
-        st = total ? grow_pinned(h_files, h_files_cap, block) : noErr;
-        void** d_bytes = slot ? &d->d_rs_bytes_b : &d->d_rs_bytes;
-        size_t* d_bytes_cap = slot ? &d->d_rs_bytes_b_cap : &d->d_rs_bytes_cap;
-        if (st == noErr && total) st = grow_device(d_bytes, d_bytes_cap, block);
+        st = total ? d->h_files[slot].reserve_slack(block) : noErr;
+        if (st == noErr && total) st = d->d_rs_bytes[slot].reserve_slack(block);
         // the run's payloads go up on their own stream, beside the previous run's kernels: they wait for the decode kernel
         // that read this slot two runs ago, and this run's kernels wait for them
         if (st == noErr && !d->up_stream) st = hip_status(hipStreamCreateWithFlags(&d->up_stream, hipStreamNonBlocking), "stream", __LINE__);
@@ -581,7 +563,8 @@ OSStatus process_audio_files(LBAudioDetective* d, const char* const* paths, size
             run_b = run_e;
             continue;
         }
-        uint8_t* stage = static_cast<uint8_t*>(*h_files);
+        uint8_t* stage = d->h_files[slot];
+        uint8_t* d_bytes = d->d_rs_bytes[slot];
         int device = 0;
         (void)hipGetDevice(&device);
         std::atomic<int> upload_error{0};
@@ -611,7 +594,7 @@ OSStatus process_audio_files(LBAudioDetective* d, const char* const* paths, size
                 j.bytes0 = j.file_off + j.a.off;
             }
             if (hi > lo) {
-                const hipError_t err = hipMemcpyAsync(static_cast<uint8_t*>(*d_bytes) + lo, stage + lo, hi - lo, hipMemcpyHostToDevice, d->up_stream);
+                const hipError_t err = hipMemcpyAsync(d_bytes + lo, stage + lo, hi - lo, hipMemcpyHostToDevice, d->up_stream);
                 if (err != hipSuccess) upload_error.store((int)err);
             }
         };

@@ -202,8 +202,7 @@ OSStatus LBAudioDetectiveCorpusQueryBatchShardedWith(LBAudioDetectiveCorpusRef i
             if (st != noErr && inCorpus && !block_busy) {
                 // remember WHERE the stuck work ends, not the stream it sits on
                 inCorpus->shard_stale = true;
-                if (!inCorpus->shard_stale_event &&
-                    hipEventCreateWithFlags(&inCorpus->shard_stale_event, hipEventDisableTiming) != hipSuccess) inCorpus->shard_stale_event = nullptr;
+                if (inCorpus->shard_stale_event.create() != noErr) inCorpus->shard_stale_event.ev = nullptr;
                 if (inCorpus->shard_stale_event) (void)hipEventRecord(inCorpus->shard_stale_event, stream);
             }
         }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/lbaudiodetective.h"
+#include "buffers.hpp"   // hip_status / LBAD_HIP and the owning types
 
 namespace lbad {
 
@@ -22,13 +23,6 @@ constexpr uint32_t kMaxBands = 64;
 constexpr uint32_t kSparseFrameDwMax = 128 * 17;       // the largest compact frame (Plan::Sparse): 128 rows of at most 16 + 1 stored bands
 constexpr uint32_t kMinWindow = 16;
 constexpr uint32_t kMaxWindow = 8192;
-
-OSStatus hip_status(hipError_t e, const char* what, int line);
-#define LBAD_HIP(expr)                                                   \
-    do {                                                                 \
-        OSStatus st__ = ::lbad::hip_status((expr), #expr, __LINE__);     \
-        if (st__ != noErr) return st__;                                  \
-    } while (0)
 
 // Host allocations sized by caller or file data (decoded audio, resampler output, zero padding) can fail:
 // nothing may unwind through the C boundary.  memFullErr is MacErrors.h's -108.
@@ -90,14 +84,14 @@ struct Plan {
     uint32_t keep = 0;  // wavelets whose sign pair survives the truncation to subfp_len Booleans
     BandTable table;
     // device copies
-    float* d_tw = nullptr;        // [W/2] re then [W/2] im
-    uint32_t* d_bands = nullptr;  // [bands] lo, [bands] hi, [bands] divisor as float bits, ... (api_detective.cpp: eight rows + 1 word, then RN(1 / divisor) and "short division proven" from word 9 * bands)
-    float* d_bin_const = nullptr; // per-bin twiddles of the pruned kernel (only when pruned_ok)
+    DeviceBuffer<float> d_tw;     // [W/2] re then [W/2] im
+    DeviceBuffer<uint32_t> d_bands;  // [bands] lo, [bands] hi, [bands] divisor as float bits, ... (api_detective.cpp: eight rows + 1 word, then RN(1 / divisor) and "short division proven" from word 9 * bands)
+    DeviceBuffer<float> d_bin_const; // per-bin twiddles of the pruned kernel (only when pruned_ok)
     bool pruned_ok = false;
     bool full_ok = false;         // k_rows_full.hip applies
     bool stream_ok = false;       // k_rows_stream.hip applies (also uses d_claim)
     bool stream2_ok = false;      // k_rows_stream2.hip applies (preferred over k_rows_full.hip when the clip length is even)
-    uint32_t* d_claim = nullptr;  // its per-XCD claim counters (8 words)
+    DeviceBuffer<uint32_t> d_claim;  // its per-XCD claim counters (8 words)
     // Structurally empty bands (round 4): a band whose bin range is empty is +0.0 in every window (17 of the 32
     // bands at 44.1 kHz / 1024).  `sparse.ok`: 32 bands and at most ONE live band among the left sixteen -- stage 1 then
     // writes compact frames (128 rows of the `n_stored` bands that can be non-zero: the live ones of the right sixteen in
@@ -209,10 +203,9 @@ struct PhaseTable;
 // the device copy of a phase table, made on first use and kept by the detective
 struct DevPhase {
     const PhaseTable* host = nullptr;
-    int32_t* first = nullptr;
-    uint32_t* count = nullptr;
-    double* wsum = nullptr;
-    double* w = nullptr;
+    DeviceBuffer<int32_t> first;
+    DeviceBuffer<uint32_t> count;
+    DeviceBuffer<double> wsum, w;
 };
 OSStatus device_phase(struct ::LBAudioDetective* d, const PhaseTable* host, hipStream_t stream, FileDesc& f);
 hipError_t launch_decode_batch(const FileDesc* d_files, uint32_t n_files, uint64_t max_units, const uint8_t* d_bytes,
@@ -385,7 +378,6 @@ hipError_t launch_synth_corpus(uint32_t seed, uint64_t first, uint64_t n_entries
 // ---- shared between the api_*.cpp files ------------------------------------------------------------------
 uint64_t subfingerprint_count(uint64_t n_samples, uint32_t window, uint32_t stride);
 OSStatus ensure_plan(struct ::LBAudioDetective* d);
-OSStatus grow_device(void** ptr, size_t* cap, size_t bytes);
 // the batch hot path on device memory; tails: end-of-file treatment of files laid out inside ONE float32 clip
 OSStatus fingerprint_clips_device(struct ::LBAudioDetective* d, const void* d_pcm, uint32_t fmt, uint64_t n_clips,
                                   uint64_t samples_per_clip, uint32_t* d_packed, float* d_raw, float* d_haar,
@@ -430,49 +422,32 @@ struct LBAudioDetective {
     uint32_t tail_mode = 1;  // hop mode 1, windows past the end of the file: 0 zero-filled, 1 nothing read, 2 stale spectrum
     uint32_t resampler = 0;  // 0 long Kaiser sinc, 1 short sinc, 2 linear interpolation
     lbad::Plan plan;         // lazily rebuilt when the configuration changes
-    float* d_frames = nullptr;  // frame rows between stage 1 and stage 2
-    uint64_t d_frames_cap = 0;  // in floats
+    lbad::DeviceBuffer<float> d_frames;  // frame rows between stage 1 and stage 2
     // bytes of HBM the inter-stage buffer may take.  512 MiB = 32 768 frames per chunk: the configs[1] pass of 500 000
     // frames runs as 16 chunks and is 2.5 % FASTER than as one (20.05 against 20.57 ms; 16 GiB was the default until
     // round 3), below 128 MiB the launches start to cost (tools/exp/scratch_chunks.py)
     uint64_t scratch_limit = 512ull << 20;
-    // persistent buffers of the one-off (host in, host out) entry points; they only grow
-    void* d_io_pcm = nullptr;
-    size_t d_io_pcm_cap = 0;
-    uint32_t* d_io_packed = nullptr;
-    size_t d_io_packed_cap = 0;
-    void* h_io = nullptr;        // pinned staging for small calls
-    size_t h_io_cap = 0;
+    // persistent buffers of the one-off (host in, host out) entry points; they only grow (a quarter more than asked for)
+    lbad::DeviceBuffer<void> d_io_pcm;
+    lbad::DeviceBuffer<uint32_t> d_io_packed;
+    lbad::PinnedBuffer<void> h_io;   // pinned staging for small calls
     hipStream_t io_stream = nullptr;
     // converter state of the file entry points: input / output samples and the two kernel tables, grown on demand
-    void* d_rs_bytes = nullptr;       // the file's payload as read (file batches: slot 0)
-    size_t d_rs_bytes_cap = 0;
-    void* d_rs_bytes_b = nullptr;     // file batches, slot 1: run i + 1's payloads go up while run i is decoded
-    size_t d_rs_bytes_b_cap = 0;
+    lbad::DeviceBuffer<uint8_t> d_rs_bytes[2];   // the files' payloads as read; file batches, slot 1: run i + 1's payloads go up while run i is decoded
     hipStream_t up_stream = nullptr;  // the uploads of a file batch (beside io_stream, which runs the kernels)
     hipEvent_t up_done[2] = {nullptr, nullptr};      // behind a run's uploads, on up_stream
     hipEvent_t bytes_free[2] = {nullptr, nullptr};   // behind the decode kernel that read the slot's payloads, on io_stream
     hipEvent_t packed_done[2] = {nullptr, nullptr};  // behind the copy of a group's packed results into the slot's pinned block
-    void* d_rs_in = nullptr;          // decoded mono samples at the file's rate
-    size_t d_rs_in_cap = 0;
-    void* d_rs_out = nullptr;
-    size_t d_rs_out_cap = 0;
-    double* d_rs_table[2] = {nullptr, nullptr};
+    lbad::DeviceBuffer<float> d_rs_in;           // decoded mono samples at the file's rate
+    lbad::DeviceBuffer<float> d_rs_out;
+    lbad::DeviceBuffer<double> d_rs_table[2];
     std::vector<lbad::DevPhase> d_phases;   // phase tables of the rational rate pairs met so far
-    void* d_rs_desc = nullptr;        // per-file descriptors of a file batch
-    size_t d_rs_desc_cap = 0;
-    void* d_rs_tail = nullptr;        // tail-mode-2 tables of a file batch
-    size_t d_rs_tail_cap = 0;
+    lbad::DeviceBuffer<lbad::FileDesc> d_rs_desc;   // per-file descriptors of a file batch
+    lbad::DeviceBuffer<uint32_t> d_rs_tail;      // tail-mode-2 tables of a file batch
     // a file batch goes through in runs, two in flight (api_files.cpp): while the device works on run i the host reads
     // run i + 1 into the other pinned block, and run i's results are unpacked while the device works on run i + 1
-    void* h_files = nullptr;          // pinned block a run of files is read into (slot 0)
-    size_t h_files_cap = 0;
-    void* h_packed = nullptr;         // pinned landing area of a run's packed results (slot 0)
-    size_t h_packed_cap = 0;
-    void* h_files_b = nullptr;        // slot 1
-    size_t h_files_b_cap = 0;
-    void* h_packed_b = nullptr;
-    size_t h_packed_b_cap = 0;
+    lbad::PinnedBuffer<uint8_t> h_files[2];      // per slot: pinned block a run of files is read into
+    lbad::PinnedBuffer<uint32_t> h_packed[2];    // ... and the pinned landing area of a run's packed results
     bool file_pipeline = true;        // LBAudioDetectiveSetFilePipeline(…, 0): one run at a time (measurement)
     // optional per-stage timing (hipEvents on the caller's stream)
     bool timing = false;
@@ -499,81 +474,70 @@ struct LBAudioDetectiveCorpus {
     uint64_t capacity = 0;
     uint64_t count = 0;
     uint32_t variant = 0;
-    uint4* d_planes = nullptr;    // plane layout [n_planes][capacity]
+    // The blocks made with the corpus (planes or records, offsets, plan, keys) keep their addresses for its lifetime.
+    lbad::DeviceBuffer<uint4> d_planes;          // plane layout [n_planes][capacity]
     uint32_t n_planes = 0;
-    uint32_t* d_query = nullptr;  // query block on the device
-    uint32_t* h_query = nullptr;  // pinned staging copy of it
-    uint32_t query_cap = 0;       // in words
-    unsigned long long* d_key = nullptr;
+    lbad::StagingPair<uint32_t> query;           // query block on the device and the pinned staging copy of it
+    lbad::DeviceBuffer<unsigned long long> d_key;
     // host-synchronous query without memset / copy / stream synchronisation (api_corpus.cpp)
-    unsigned long long* d_fast_key = nullptr;    // zero between queries
-    unsigned int* d_ticket = nullptr;
-    unsigned long long* h_out = nullptr;         // pinned, host-coherent: [0] key, [1] sequence number
-    unsigned long long* h_out_dev = nullptr;     // its device address
+    lbad::DeviceBuffer<unsigned long long> d_fast_key;   // zero between queries
+    unsigned int* d_ticket = nullptr;            // (inside d_fast_key, behind the scan's slots)
+    lbad::PinnedBuffer<unsigned long long> h_out;        // pinned, host-coherent: [0] key, [1] sequence number
+    unsigned long long* h_out_dev = nullptr;     // its device address (an alias, like d_ticket)
     unsigned long long seq = 0;
     hipStream_t stream = nullptr;
     bool appended = false;                       // entries were appended since the last polled query
-    hipEvent_t append_event = nullptr;           // recorded behind the latest append on ITS stream
+    lbad::Event append_event;                    // recorded behind the latest append on ITS stream
     // ragged form (LBAudioDetectiveCorpusNewRagged): entries of any length as a stream of 32-byte records
     bool ragged = false;
-    uint4* d_recs = nullptr;                     // 2 x uint4 per record
+    lbad::DeviceBuffer<uint4> d_recs;            // 2 x uint4 per record
     uint64_t rec_capacity = 0;                   // records
     uint64_t n_pos = 0;                          // records stored
-    uint32_t* d_off = nullptr;                   // capacity + 1 record positions (entry e = [off[e], off[e + 1]))
+    lbad::DeviceBuffer<uint32_t> d_off;          // capacity + 1 record positions (entry e = [off[e], off[e + 1]))
     std::vector<uint32_t> h_off;                 // count + 1
     uint32_t ne_max = 0;                         // longest entry
     std::map<uint32_t, uint64_t> len_hist;       // entries per length: the scan's task totals for any query length
     // the scan's plan for ONE query length (k_sliding.hip): rebuilt when the length, the entries or the grid change
-    uint32_t* d_plan = nullptr;
+    lbad::DeviceBuffer<uint32_t> d_plan;
     uint32_t plan_nq = 0, plan_grid = 0, plan_bmin = 0;
     bool bound_pruning = true;     // top-1 scans of a ragged corpus may drop passes that cannot reach the best match so far (exact)
     float prune_from = 0.7f;       // ... once a match of at least this score is known (LBAudioDetectiveCorpusSetBoundPruningThreshold)
     uint64_t plan_count = 0;
-    hipEvent_t plan_built = nullptr;             // behind the plan's kernels, on plan_stream
+    lbad::Event plan_built;                      // behind the plan's kernels, on plan_stream
     hipStream_t plan_stream = nullptr;
     // key block of the sharded query (api_rccl.cpp), made with the corpus so that the collective call never allocates
-    unsigned long long* d_shard_keys = nullptr;
-    unsigned long long* h_shard_keys = nullptr;
-    // ring of query slots in h_query / d_query (ragged scan): slot size in words, one event per slot, queries so far
+    lbad::DeviceBuffer<unsigned long long> d_shard_keys;
+    lbad::PinnedBuffer<unsigned long long> h_shard_keys;
+    // ring of query slots in `query` (ragged scan): slot size in words, one event per slot, queries so far
     size_t query_slot_words = 0;
-    hipEvent_t query_ev[8] = {};
+    lbad::Event query_ev[8];
     // per ring slot: the scan's running maxima (8 words) and its ticket, ZERO between scans -- the scan's last workgroup
     // leaves them so (k_sliding.hip: ScanOut); 16 words per slot
-    unsigned long long* d_scan_out = nullptr;
+    lbad::DeviceBuffer<unsigned long long> d_scan_out;
     bool scan_out_dirty = false;                 // a scan's launch failed: clear the words before the next one
     std::mutex shard_lock;                       // the sharded query's key block is one per corpus (api_rccl.cpp)
     bool shard_stale = false;                    // a sharded query timed out: work may still be queued behind the key block
-    hipEvent_t shard_stale_event = nullptr;      // ... recorded behind that work when the call gave up (the stream may be gone by the next call)
+    lbad::Event shard_stale_event;               // ... recorded behind that work when the call gave up (the stream may be gone by the next call)
     uint64_t query_seq = 0;
     // top-K queries (api_corpus.cpp): score rows (up to kQueryBatchMax x count floats), the selection's scratch, the staged
     // query blocks of the batch scan, the scans' own key words (the top-1 state -- d_key, the polled slots -- stays
     // untouched) and the keys of the host-returning forms.  Grown on demand; a call reuses them only after topk_ev, recorded
     // behind the previous call's last kernel.
-    float* d_topk_scores = nullptr;
-    size_t topk_scores_cap = 0;                  // bytes, and so on below
-    void* d_topk_scratch = nullptr;
-    size_t topk_scratch_cap = 0;
-    uint32_t* d_topk_q = nullptr;
-    uint32_t* h_topk_q = nullptr;
-    size_t topk_q_cap = 0;
-    unsigned long long* d_topk_scan_keys = nullptr;   // kQueryBatchMax words
-    unsigned long long* d_topk_keys = nullptr;
-    size_t topk_keys_cap = 0;
-    hipEvent_t topk_ev = nullptr;
+    lbad::DeviceBuffer<float> d_topk_scores;
+    lbad::DeviceBuffer<void> d_topk_scratch;
+    lbad::StagingPair<uint32_t> topk_q;
+    lbad::DeviceBuffer<unsigned long long> d_topk_scan_keys;   // kQueryBatchMax words
+    lbad::DeviceBuffer<unsigned long long> d_topk_keys;
+    lbad::Event topk_ev;
     // alignment (api_align.cpp): the staged query words and their table (device + pinned), the per-pair maxima of a split
     // launch, and the results of the host-returning forms (keys, lags or a profile) on their way back.  Grown on demand; a
     // call reuses them only after align_ev, recorded behind the previous call's last kernel.
-    uint32_t* d_align_q = nullptr;
-    uint32_t* h_align_q = nullptr;
-    size_t align_q_cap = 0;                      // bytes, and so on below
-    unsigned long long* d_align_best = nullptr;
-    size_t align_best_cap = 0;
-    void* d_align_out = nullptr;
-    size_t align_out_cap = 0;
-    hipEvent_t align_ev = nullptr;
+    lbad::StagingPair<uint32_t> align_q;
+    lbad::DeviceBuffer<unsigned long long> d_align_best;
+    lbad::DeviceBuffer<void> d_align_out;
+    lbad::Event align_ev;
     // packed queries (the ...QueryPacked...Device calls): what the builders of k_query.hip write -- the scan's blocks, then the
     // alignment's table and words.  Grown on demand; a call reuses it only after pq_ev, recorded behind its last kernel.
-    uint32_t* d_pq = nullptr;
-    size_t pq_cap = 0;                           // bytes
-    hipEvent_t pq_ev = nullptr;
+    lbad::DeviceBuffer<uint32_t> d_pq;
+    lbad::Event pq_ev;
 };

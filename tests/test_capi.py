@@ -145,6 +145,24 @@ def test_compute_calls_fail_loudly_without_gpu(lb):
     assert L.LBAudioDetectiveGetCompactBands(None, None, C.byref(n)) != 0
 
 
+@pytest.mark.skipif(_has_gpu(), reason="checks the no-GPU behaviour")
+def test_handles_own_nothing_without_gpu(lb):
+    """The owners of device and pinned memory count what they hold (LBAudioDetectiveDebugLiveBytes): a detective that is made,
+    refused its work and disposed, and a corpus that cannot be made, leave both counters at 0 -- and get there without a device."""
+    assert lb.debug_live_bytes() == (0, 0)
+    d = lb.Detective().configure(sample_rate=44100, window=1024)
+    with pytest.raises(lb.LBAudioDetectiveError):
+        d.process_pcm(np.zeros(44100, np.float32))
+    assert lb.debug_live_bytes() == (0, 0)
+    d.dispose()
+    lb.Detective().dispose()
+    for make in (lambda: lb.Corpus(200, 5, 10), lambda: lb.Corpus.ragged(200, 10, 100)):
+        with pytest.raises(lb.LBAudioDetectiveError):
+            make()
+    assert lb.debug_live_bytes() == (0, 0)
+    assert lb.lib().LBAudioDetectiveDebugLiveBytes(None, None) == lb.constant("kLBAudioDetectiveArgumentInvalid")
+
+
 def test_missing_library_raises(lb, monkeypatch, tmp_path):
     from lbaudiodetective_amd import _native
     monkeypatch.setattr(_native, "_lib", None)

@@ -381,7 +381,7 @@ LBAudioDetectiveCorpusRef LBAudioDetectiveCorpusNew(UInt32 inSubfingerprintLengt
  * lengths; LBAudioDetectiveFingerprint.m:123-146 swaps the two sides and slides the shorter along the longer).
  * inSubfingerprintLength <= 200.  HBM for inSubfingerprintCapacity sub-fingerprints (32 bytes each) and
  * inEntryCapacity entries is reserved up front.  Every query entry point below accepts such a corpus and a query
- * of ANY number of sub-fingerprints; the scan is one launch (k_sliding.hip). */
+ * of ANY number of sub-fingerprints; the scan is one launch (k_sliding.hip, k_sliding_short.hip). */
 LBAudioDetectiveCorpusRef LBAudioDetectiveCorpusNewRagged(UInt32 inSubfingerprintLength, UInt64 inEntryCapacity,
                                                           UInt64 inSubfingerprintCapacity);
 /* Append inNumberOfEntries entries to a ragged corpus: inPacked = device pointer to the entries' sub-fingerprints
@@ -601,6 +601,21 @@ OSStatus LBAudioDetectiveCorpusQueryPackedTopKKeysDevice(LBAudioDetectiveCorpusR
 OSStatus LBAudioDetectiveDebugQueryBlocks(UInt32 inKind, const void* inPackedQueries, const Boolean* inBooleans, UInt32 inCount,
                                           UInt32 inPer, UInt32 inSubfingerprintLength, UInt32 inRange, UInt32* outWords,
                                           UInt64 inCapacity, UInt64* outCount);
+/* Debug / tests: which kernel ONE launch of a ragged-corpus scan takes and what it needs in front of it -- the scan's own
+ * decision (sliding.cpp: sliding_choose) as words; touches no device.  The corpus is described by a histogram of entry lengths
+ * (inLengthCount pairs of length and count), its record count, its longest entry and its kernel variant; the launch by the
+ * query length, the queries of that length still to go, the range (0: the whole length), whether per-entry scores are wanted,
+ * whether the query blocks are on the host, and the device's compute units.  outWords (inCapacity >= 21):
+ *   0 queries this launch takes (0: no such launch, every other word is 0)   1 family: 0 compare_sliding_kernel, 1
+ *   compare_short_kernel, 2 compare_short_multi_kernel   2..5 the instance's template arguments (FULL, QLDS, QN, THREADS | K, QN |
+ *   QN, NQ)   6 b_min   7..8 tasks_a   9..10 tasks_b (low, high)   11..13 grid, chunk_a, chunk_b   14 the plan is read   15 the
+ *   query travels in the kernel's arguments   16 the launch maxes its keys in place   17 a systolic launch follows, with 18 its
+ *   look and 19 its only_upto   20 look of a systolic first launch */
+OSStatus LBAudioDetectiveDebugSlidingChoice(const UInt32* inEntryLengths, const UInt64* inEntryCounts, UInt32 inLengthCount,
+                                            UInt64 inRecordCount, UInt32 inLongestEntry, UInt32 inKernelVariant,
+                                            UInt32 inSubfingerprintLength, UInt32 inQueryLength, UInt32 inQueriesLeft, UInt32 inRange,
+                                            UInt32 inScores, UInt32 inHostBlocks, UInt32 inComputeUnits, UInt32* outWords,
+                                            UInt32 inCapacity);
 /* Debug / tests: bytes of device and of pinned host memory that detectives and corpora of this process hold right now, scratch of
  * single calls included.  The process-wide contexts of the pair compare, the Frame API and the sharded query, and what
  * LBAudioDetectiveDeviceMalloc hands out, are not counted.  Needs no device. */

@@ -179,6 +179,8 @@ _SIGNATURES = {
                                                                    C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveDebugQueryBlocks": (OSStatus, [UInt32, C.c_void_p, C.c_void_p, UInt32, UInt32, UInt32, UInt32, C.c_void_p, UInt64,
                                                     _P(UInt64)]),
+    "LBAudioDetectiveDebugSlidingChoice": (OSStatus, [_P(UInt32), _P(UInt64), UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, UInt32, UInt32,
+                                                      UInt32, UInt32, UInt32, _P(UInt32), UInt32]),
     "LBAudioDetectiveDebugLiveBytes": (OSStatus, [_P(UInt64), _P(UInt64)]),
     "LBAudioDetectiveCorpusSetKernelVariant": (OSStatus, [Ref, UInt32]),
     "LBAudioDetectiveCorpusSave": (OSStatus, [Ref, C.c_char_p]),

@@ -814,6 +814,22 @@ def debug_query_blocks(kind: int, n_queries: int, per_query: int, subfp_len: int
     return out[:count.value].reshape(n_queries, -1)
 
 
+SLIDING_CHOICE_WORDS = 21
+
+
+def debug_sliding_choice(hist, n_pos: int, ne_max: int, variant: int, subfp_len: int, n_query: int, n_left: int, range_: int = 0,
+                         scores: bool = False, host_blocks: bool = True, cus: int = 256) -> list:
+    """LBAudioDetectiveDebugSlidingChoice (tests): the kernel one launch of a ragged scan takes, as the 21 words the header
+    describes.  hist: (entry length, count) pairs.  Needs no device."""
+    lengths = (N.UInt32 * max(1, len(hist)))(*[int(h[0]) for h in hist])
+    counts = (N.UInt64 * max(1, len(hist)))(*[int(h[1]) for h in hist])
+    out = (N.UInt32 * SLIDING_CHOICE_WORDS)()
+    _check(N.lib().LBAudioDetectiveDebugSlidingChoice(lengths, counts, len(hist), n_pos, ne_max, variant, subfp_len, n_query, n_left,
+                                                      range_, int(bool(scores)), int(bool(host_blocks)), cus, out, SLIDING_CHOICE_WORDS),
+           "DebugSlidingChoice")
+    return list(out)
+
+
 def debug_live_bytes():
     """LBAudioDetectiveDebugLiveBytes (tests): (device, pinned) bytes that detectives and corpora hold right now."""
     dev, pinned = N.UInt64(0), N.UInt64(0)

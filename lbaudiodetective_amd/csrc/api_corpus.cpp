@@ -12,7 +12,7 @@
 namespace lbad {
 namespace {
 
-// ragged corpus: the sliding scan of k_sliding.hip (any query length, any entry lengths).  A launch's query blocks travel
+// ragged corpus: the sliding scan (sliding.cpp decides and launches; any query length, any entry lengths).  A launch's query blocks travel
 // through a ring of kQuerySlots pinned + device slots, one event per slot: a call waits only for the scan that used
 // its slot kQuerySlots launches ago (long done), not for the stream -- back-to-back queries leave no gap on the GPU.
 // Round 5: a single query of up to kSlideQueryArgSubs sub-fingerprints travels in the kernel's argument segment (no copy
@@ -30,47 +30,22 @@ OSStatus wait_scans(const LBAudioDetectiveCorpus* c) {
     return noErr;
 }
 
-// tasks of either kind for queries of nq sub-fingerprints, from the histogram of entry lengths (Fp.m:123-136: an entry
-// longer than the query slides the query along itself, any other entry slides along the query)
-// (b_min: "B" entries shorter than this are left out -- they go through the systolic scan, ragged_split)
-void ragged_tasks(const LBAudioDetectiveCorpus* c, uint64_t nq, uint64_t b_min, uint64_t& tasks_a, uint64_t& tasks_b) {
-    tasks_a = tasks_b = 0;
-    for (const auto& kv : c->len_hist) {
-        const uint64_t ne = kv.first;
-        if (ne > nq) tasks_a += kv.second * ((ne - nq + 4) / 4);
-        else if (ne >= b_min) tasks_b += kv.second * ((nq - ne + 4) / 4);
-    }
+SlideCorpusStats ragged_stats(const LBAudioDetectiveCorpus* c) {
+    SlideCorpusStats s;
+    s.len_hist = &c->len_hist; s.n_pos = c->n_pos; s.ne_max = c->ne_max; s.variant = c->variant; s.subfp_len = c->subfp_len;
+    return s;
 }
 
-// Split the scan?  An entry of n <= 15 sub-fingerprints against a longer query of nq costs the task kernel a pass of nq steps
-// per four of its nq - n + 1 offsets, n of which meet the entry: measured 2 300 G (step, offset) slots per second whatever
-// n is.  The systolic scan spends nq steps on EVERY record of a chunk that holds such an entry (2 200 G record-steps per
-// second, and not less than reading the records once).  Worth a second launch when the short entries' slots are well above
-// the whole corpus' record-steps.  Kernel variant 3 forces the split (where one exists), 4 forbids it.
-uint32_t ragged_split(const LBAudioDetectiveCorpus* c, uint64_t nq) {
-    if (sliding_short((uint32_t)nq, c->ne_max) || nq < kSlideSplitBelow || c->variant == 4) return 0;
-    uint64_t slots = 0, entries = 0;
-    for (const auto& kv : c->len_hist) {
-        const uint64_t ne = kv.first;
-        if (ne >= kSlideSplitBelow || ne > nq) continue;
-        slots += kv.second * ((nq - ne + 4) / 4) * 4 * nq;
-        entries += kv.second;
-    }
-    if (entries == 0) return 0;
-    if (c->variant == 3) return kSlideSplitBelow;
-    return slots > 2 * c->n_pos * nq + 20000000ull ? kSlideSplitBelow : 0;     // (+ 10 us of slots: a second launch is not free)
-}
-
-// ONE launch: n_q queries of nq sub-fingerprints, their keys to keys + pos[i].  Their blocks ((nq + 1) * 16 words each, one
-// after the other) come either from the host -- h_blocks: staged through the launch's ring slot, or sent in the kernel's
-// arguments -- or are on the device already -- d_blocks: what a builder of k_query.hip wrote; nothing is staged then and the
-// argument shortcut is never taken.  Either way the launch owns a ring slot's result words and leaves its event behind.
-OSStatus launch_ragged_blocks(LBAudioDetectiveCorpus* c, uint32_t nq, const uint32_t* h_blocks, const uint32_t* d_blocks,
-                              const uint32_t* pos, uint32_t n_q, uint32_t range, uint64_t index_base, float* d_scores,
+// ONE launch, as `choice` (sliding_choose) has decided it: choice.n_take queries of nq sub-fingerprints, their keys to
+// keys + pos[i].  Their blocks (sliding_block_words(nq) words each, one after the other) come either from the host -- h_blocks:
+// staged through the launch's ring slot, or sent in the kernel's arguments -- or are on the device already -- d_blocks: what a
+// builder of k_query.hip wrote; nothing is staged then.  Either way the launch owns a ring slot's result words and leaves its
+// event behind.  What belongs to the corpus is managed here: the ring, the result words, the plan cache and the events.
+OSStatus launch_ragged_blocks(LBAudioDetectiveCorpus* c, uint32_t nq, const SlideChoice& choice, const uint32_t* h_blocks,
+                              const uint32_t* d_blocks, const uint32_t* pos, uint32_t range, uint64_t index_base, float* d_scores,
                               unsigned long long* keys, hipStream_t stream) {
-    const size_t all_words = ((size_t)nq + 1u) * 16u * n_q;
-    const uint32_t b_min = ragged_split(c, nq);
-    const bool in_args = h_blocks && n_q == 1 && nq <= kSlideQueryArgSubs && !sliding_short(nq, c->ne_max) && b_min == 0;   // (the systolic scan reads d_query)
+    if (choice.n_take == 0) return kLBAudioDetectiveArgumentInvalid;
+    const size_t all_words = sliding_block_words(nq) * choice.n_take;
     const size_t slot_words = (all_words + 63) & ~(size_t)63;
     if (h_blocks && c->query_slot_words < slot_words) {   // (re)size the ring: everything that used it must be done
         OSStatus st = wait_scans(c);
@@ -98,51 +73,47 @@ OSStatus launch_ragged_blocks(LBAudioDetectiveCorpus* c, uint32_t nq, const uint
     const uint32_t slot = (uint32_t)(c->query_seq++ % kQuerySlots);
     OSStatus st = c->query_ev[slot].wait_or_create();
     if (st != noErr) return st;
-    const uint32_t* h = nullptr;
-    const uint32_t* dq = d_blocks;
+    SlideScan scan;
+    scan.d_queries = d_blocks;
     if (h_blocks) {
         uint32_t* h_slot = c->query.host + (size_t)slot * c->query_slot_words;
         uint32_t* d_slot = c->query.dev + (size_t)slot * c->query_slot_words;
         std::memcpy(h_slot, h_blocks, all_words * sizeof(uint32_t));
-        if (!in_args) LBAD_HIP(hipMemcpyAsync(d_slot, h_slot, all_words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        h = h_slot;
-        dq = d_slot;
+        if (!choice.q_in_args) LBAD_HIP(hipMemcpyAsync(d_slot, h_slot, all_words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        scan.d_queries = choice.q_in_args ? nullptr : d_slot;
+        scan.h_query = choice.q_in_args ? h_slot : nullptr;
     }
     if (d_scores) LBAD_HIP(hipMemsetAsync(d_scores, 0, c->count * sizeof(float), stream));
-    uint64_t tasks_a = 0, tasks_b = 0;
-    ragged_tasks(c, nq, b_min, tasks_a, tasks_b);
-    if (tasks_a > 0xFFFFFFFFull || tasks_b > 0xFFFFFFFFull) return kLBAudioDetectiveArgumentInvalid;   // the plan counts in 32 bits
-    const SlideShape sh = sliding_shape(tasks_a, tasks_b, n_q);
     // the plan of this query length: kept while the length and the entries stay (queries of one length are the rule).  Only
     // the task kernel reads it: a batch of short queries on compare_short_multi_kernel leaves the plan alone
-    if (sliding_needs_plan(nq, c->ne_max, n_q, tasks_a, d_scores != nullptr) && (c->plan_nq != nq || c->plan_count != c->count || c->plan_grid != sh.grid || c->plan_bmin != b_min)) {
+    if (choice.reads_plan && (c->plan_nq != nq || c->plan_count != c->count || c->plan_grid != choice.shape.grid || c->plan_bmin != choice.b_min)) {
         // scans on other streams may still read the old plan: every scan leaves its slot's event behind, and a slot is
         // reused only after its event -- the eight events cover everything that can still be running
         st = wait_scans(c);
         if (st == noErr) st = c->plan_built.create();
         if (st != noErr) return st;
         c->plan_nq = 0;
-        LBAD_HIP(launch_sliding_plan(c->d_off, c->count, nq, b_min, sh, c->d_plan, stream));
+        LBAD_HIP(launch_sliding_plan(c->d_off, c->count, nq, choice.b_min, choice.shape, c->d_plan, stream));
         st = c->plan_built.record(stream);
         if (st != noErr) return st;
         c->plan_stream = stream;
-        c->plan_nq = nq; c->plan_count = c->count; c->plan_grid = sh.grid; c->plan_bmin = b_min;
+        c->plan_nq = nq; c->plan_count = c->count; c->plan_grid = choice.shape.grid; c->plan_bmin = choice.b_min;
     } else if (c->plan_built && c->plan_stream != stream) {
         LBAD_HIP(hipStreamWaitEvent(stream, c->plan_built, 0));
     }
-    SlideScan scan;
-    scan.d_queries = in_args ? nullptr : dq;
-    scan.h_query = in_args ? h : nullptr;
-    scan.n_q = n_q;
     scan.d_acc = c->d_scan_out + (size_t)slot * kScanOutWords;
     scan.d_ticket = reinterpret_cast<unsigned int*>(scan.d_acc + 8);
     scan.d_keys = keys;
-    for (uint32_t i = 0; i < 8; ++i) scan.key_pos[i] = i < n_q ? pos[i] : 0u;
+    for (uint32_t i = 0; i < 8; ++i) scan.key_pos[i] = i < choice.n_take ? pos[i] : 0u;
+    SlideCorpus src;
+    src.recs = c->d_recs; src.n_pos = c->n_pos; src.off = c->d_off; src.n_entries = c->count;
+    src.zero_rec = (uint32_t)(c->rec_capacity + kRecordSlack / 2); src.subfp_len = c->subfp_len; src.plan = c->d_plan;
+    SlideCall call;
+    call.n_query = nq; call.range = range; call.index_base = index_base;
+    call.d_score_bits = reinterpret_cast<unsigned int*>(d_scores);
+    call.bound_pruning = c->bound_pruning; call.prune_from = c->prune_from; call.stream = stream;
     {
-        const hipError_t launched = launch_compare_sliding(c->d_recs, c->n_pos, c->d_off, c->count, c->ne_max,
-                                                           (uint32_t)(c->rec_capacity + kRecordSlack / 2), tasks_a, tasks_b, sh, c->d_plan,
-                                                           c->subfp_len, scan, nq, range, index_base,
-                                                           reinterpret_cast<unsigned int*>(d_scores), stream, c->bound_pruning, c->prune_from, b_min);
+        const hipError_t launched = launch_compare_sliding(src, choice, scan, call);
         if (launched != hipSuccess) c->scan_out_dirty = true;
         LBAD_HIP(launched);
     }
@@ -151,70 +122,80 @@ OSStatus launch_ragged_blocks(LBAudioDetectiveCorpus* c, uint32_t nq, const uint
     return c->query_ev[slot].record(stream);
 }
 
-// ONE launch: the n_q queries qs[0..n_q) (all of qs[0]->count sub-fingerprints), their keys to keys + pos[i]
-OSStatus launch_ragged(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, const uint32_t* pos, uint32_t n_q,
-                       uint32_t range, uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
-    const uint32_t nq = qs[0]->count;
-    const size_t block_words = ((size_t)nq + 1u) * 16u;
-    std::vector<uint32_t> block, all;
-    all.reserve(block_words * n_q);
-    for (uint32_t i = 0; i < n_q; ++i) {
-        build_sliding_query(qs[i]->data.data(), nq, c->subfp_len, range, block);
-        all.insert(all.end(), block.begin() + (block.size() - block_words), block.end());      // (without the header)
+// Where the blocks of one launch come from: the g queries idx[0..g) (positions in the caller's order, all of `per`
+// sub-fingerprints) as host blocks to stage or as blocks that are on the device already -- exactly one of the two is set
+using RaggedBlocks = std::function<void(const uint32_t* idx, uint32_t g, uint32_t per, const uint32_t*& h_blocks, const uint32_t*& d_blocks)>;
+
+// n queries against the ragged corpus, query i of lengths[i] sub-fingerprints, key i to keys[i] (d_scores: n == 1).  Queries of
+// one length share launches: grouped by length, chunked by what sliding_choose lets a launch take; the keys are zeroed once up
+// front when some launch of the call maxes its keys in place.
+OSStatus run_ragged(LBAudioDetectiveCorpus* c, const std::vector<uint32_t>& lengths, bool host_blocks, const RaggedBlocks& blocks,
+                    uint32_t range, uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
+    const uint32_t n = (uint32_t)lengths.size();
+    if (c->count == 0) {                                   // nothing to scan: every key is "no match"
+        LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream));
+        return noErr;
     }
-    return launch_ragged_blocks(c, nq, all.data(), nullptr, pos, n_q, range, index_base, d_scores, keys, stream);
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return lengths[x] < lengths[y]; });
+    struct Launch {
+        uint32_t at;
+        SlideChoice choice;
+    };
+    std::vector<Launch> launches;
+    const SlideCorpusStats stats = ragged_stats(c);
+    const uint32_t cus = (uint32_t)device_cu_count();
+    bool zero_keys = false;
+    for (uint32_t at = 0; at < n;) {
+        SlideGroup group;
+        group.n_query = lengths[order[at]]; group.range = range; group.scores = d_scores != nullptr; group.host_blocks = host_blocks;
+        while (at + group.n_left < n && lengths[order[at + group.n_left]] == group.n_query) ++group.n_left;
+        while (group.n_left) {
+            const SlideChoice choice = sliding_choose(stats, group, cus);
+            if (choice.n_take == 0) return kLBAudioDetectiveArgumentInvalid;
+            zero_keys = zero_keys || choice.maxes_keys;
+            launches.push_back({at, choice});
+            at += choice.n_take;
+            group.n_left -= choice.n_take;
+        }
+    }
+    if (zero_keys) LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream));
+    for (const Launch& l : launches) {
+        const uint32_t* h_blocks = nullptr;
+        const uint32_t* d_blocks = nullptr;
+        blocks(order.data() + l.at, l.choice.n_take, lengths[order[l.at]], h_blocks, d_blocks);
+        OSStatus st = launch_ragged_blocks(c, lengths[order[l.at]], l.choice, h_blocks, d_blocks, order.data() + l.at, range, index_base,
+                                           d_scores, keys, stream);
+        if (st != noErr) return st;
+    }
+    return noErr;
 }
 
 // n queries of `per` sub-fingerprints whose blocks a builder wrote to d_blocks, key i to keys[i] (d_scores: n == 1)
 OSStatus run_built_ragged(LBAudioDetectiveCorpus* c, const uint32_t* d_blocks, uint32_t n, uint32_t per, uint32_t range,
                           uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
-    if (c->count == 0) {                                   // nothing to scan: every key is "no match"
-        LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream));
-        return noErr;
-    }
-    // the systolic scans max their keys in place
-    if (sliding_short(per, c->ne_max) || (n > 1 && sliding_multi(per, c->ne_max)))
-        LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream));
-    const size_t block_words = ((size_t)per + 1u) * 16u;
-    for (uint32_t at = 0; at < n;) {
-        const uint32_t g = d_scores ? 1u : sliding_queries_per_launch(per, c->ne_max, n - at);
-        uint32_t pos[8];
-        for (uint32_t i = 0; i < g; ++i) pos[i] = at + i;
-        OSStatus st = launch_ragged_blocks(c, per, nullptr, d_blocks + (size_t)at * block_words, pos, g, range, index_base, d_scores, keys, stream);
-        if (st != noErr) return st;
-        at += g;
-    }
-    return noErr;
+    // (one length: the order is the caller's, a launch's blocks lie one after the other)
+    auto built = [&](const uint32_t* idx, uint32_t, uint32_t, const uint32_t*&, const uint32_t*& d) {
+        d = d_blocks + (size_t)idx[0] * sliding_block_words(per);
+    };
+    return run_ragged(c, std::vector<uint32_t>(n, per), false, built, range, index_base, d_scores, keys, stream);
 }
 
-// n queries against the ragged corpus, key i to keys[i]: queries of one length share launches
+// n queries against the ragged corpus, key i to keys[i]
 OSStatus run_queries_ragged(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
                             uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
-    if (c->count == 0) {                                   // nothing to scan: every key is "no match"
-        LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream));
-        return noErr;
-    }
-    bool any_short = false;                                // the systolic scan of short queries max-es its keys in place
-    for (uint32_t i = 0; i < n; ++i) any_short = any_short || sliding_short(qs[i]->count, c->ne_max) || (n > 1 && sliding_multi(qs[i]->count, c->ne_max));
-    if (any_short) LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream));
-    std::vector<uint32_t> order(n);
-    for (uint32_t i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return qs[x]->count < qs[y]->count; });
-    for (uint32_t at = 0; at < n;) {
-        uint32_t same = 1;
-        while (at + same < n && qs[order[at + same]]->count == qs[order[at]]->count) ++same;
-        while (same) {
-            const uint32_t g = d_scores ? 1u : sliding_queries_per_launch(qs[order[at]]->count, c->ne_max, same);
-            LBAudioDetectiveFingerprintRef group[8];
-            uint32_t pos[8];
-            for (uint32_t i = 0; i < g; ++i) { group[i] = qs[order[at + i]]; pos[i] = order[at + i]; }
-            OSStatus st = launch_ragged(c, group, pos, g, range, index_base, d_scores, keys, stream);
-            if (st != noErr) return st;
-            at += g;
-            same -= g;
+    std::vector<uint32_t> lengths(n), block, all;
+    for (uint32_t i = 0; i < n; ++i) lengths[i] = qs[i]->count;
+    auto from_handles = [&](const uint32_t* idx, uint32_t g, uint32_t per, const uint32_t*& h, const uint32_t*&) {
+        all.clear();
+        for (uint32_t i = 0; i < g; ++i) {
+            build_sliding_query(qs[idx[i]]->data.data(), per, c->subfp_len, range, block);
+            all.insert(all.end(), block.begin(), block.end());
         }
-    }
-    return noErr;
+        h = all.data();
+    };
+    return run_ragged(c, lengths, true, from_handles, range, index_base, d_scores, keys, stream);
 }
 
 OSStatus run_query_ragged(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprint* q, uint32_t range,
@@ -535,7 +516,7 @@ OSStatus LBAudioDetectiveCorpusQueryBatchKeysDevice(LBAudioDetectiveCorpusRef c,
     for (UInt32 i = 0; i < inCount && all_fast; ++i)
         all_fast = inQueries[i] && lbad::planes_fast_supported(c->subfp_len, c->n_sub, inQueries[i]->count) &&
                    inQueries[i]->length == c->subfp_len;
-    if (c->ragged) {   // queries of one length share their passes over the records (k_sliding.hip)
+    if (c->ragged) {   // queries of one length share their passes over the records (sliding.cpp)
         for (UInt32 i = 0; i < inCount; ++i)
             if (!inQueries[i] || inQueries[i]->length != c->subfp_len || inQueries[i]->count == 0) return kLBAudioDetectiveArgumentInvalid;
         return lbad::run_queries_ragged(c, inQueries, inCount, inRange ? inRange : c->subfp_len, inIndexBase, nullptr, keys, stream);
@@ -690,7 +671,7 @@ OSStatus build_packed(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_
         if (!out.fast && (size_t)per * kPackedWords * 4 > 48 * 1024) return kLBAudioDetectiveArgumentInvalid;     // (the generic scan keeps the query in LDS)
     }
     const size_t row_words = (size_t)n * per * kPackedWords;
-    const size_t scan_words = c->ragged ? (size_t)n * ((size_t)per + 1u) * 16u : (out.fast ? (size_t)n * plane_query_words() : row_words);
+    const size_t scan_words = c->ragged ? (size_t)n * sliding_block_words(per) : (out.fast ? (size_t)n * plane_query_words() : row_words);
     const bool rows_serve_both = !c->ragged && !out.fast;         // the generic scan and the uniform alignment read the same words
     // (every part starts on a 256-byte boundary, as the staging slots of the handle path do)
     const size_t desc_words = lags ? (((size_t)2 * n + 63) & ~(size_t)63) : 0;
@@ -721,7 +702,7 @@ OSStatus build_packed(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_
 OSStatus scan_built_one(LBAudioDetectiveCorpus* c, const BuiltQueries& b, uint32_t q, uint32_t per, uint32_t range, uint64_t index_base,
                         float* d_scores, unsigned long long* d_key, hipStream_t stream) {
     if (c->ragged)
-        return run_built_ragged(c, b.scan + (size_t)q * ((size_t)per + 1u) * 16u, 1, per, range, index_base, d_scores, d_key, stream);
+        return run_built_ragged(c, b.scan + (size_t)q * sliding_block_words(per), 1, per, range, index_base, d_scores, d_key, stream);
     LBAD_HIP(hipMemsetAsync(d_key, 0, sizeof(unsigned long long), stream));
     LBAD_HIP(launch_compare_planes_generic(c->d_planes, c->capacity, c->count, c->n_sub, c->subfp_len, b.scan + (size_t)q * per * kPackedWords,
                                            per, range, index_base, d_scores, d_key, stream));
@@ -865,7 +846,7 @@ OSStatus LBAudioDetectiveDebugQueryBlocks(UInt32 inKind, const void* inPackedQue
     if (inKind == 0 ? !lbad::planes_fast_supported(L, inPer, inPer) : (inKind == 3 ? L > 32u * lbad::kPackedWords : !lbad::sliding_supported(L)))
         return kLBAudioDetectiveArgumentInvalid;
     const uint32_t range = inRange ? inRange : L;
-    const size_t per_query = inKind == 0 ? lbad::plane_query_words() : (inKind == 1 ? ((size_t)inPer + 1u) * 16u : (size_t)inPer * lbad::kPackedWords);
+    const size_t per_query = inKind == 0 ? lbad::plane_query_words() : (inKind == 1 ? lbad::sliding_block_words(inPer) : (size_t)inPer * lbad::kPackedWords);
     const size_t words = per_query * inCount;
     *outCount = words;
     if (!outWords || inCapacity < words) return kLBAudioDetectiveArgumentInvalid;
@@ -880,7 +861,7 @@ OSStatus LBAudioDetectiveDebugQueryBlocks(UInt32 inKind, const void* inPackedQue
             std::memset(o, 0, per_query * sizeof(uint32_t));
             if (inKind == 1) {
                 lbad::build_sliding_query(b, inPer, L, range, block);
-                std::memcpy(o, block.data() + (block.size() - per_query), per_query * sizeof(uint32_t));     // (without the header)
+                std::memcpy(o, block.data(), per_query * sizeof(uint32_t));
                 continue;
             }
             fp.data.assign(b, b + (size_t)inPer * L);
@@ -905,6 +886,29 @@ OSStatus LBAudioDetectiveDebugQueryBlocks(UInt32 inKind, const void* inPackedQue
                                  : lbad::launch_build_query_rows(rows, inCount, inPer, L, inKind == 2, d, nullptr, nullptr);
     if (e == hipSuccess) e = hipMemcpy(outWords, d, words * sizeof(uint32_t), hipMemcpyDeviceToHost);
     return lbad::hip_status(e, "query blocks", __LINE__);
+    LBAD_GUARD_END
+}
+
+// Debug / tests: the decision of one ragged launch (sliding_choose) as words; no device is touched
+OSStatus LBAudioDetectiveDebugSlidingChoice(const UInt32* inEntryLengths, const UInt64* inEntryCounts, UInt32 inLengthCount,
+                                            UInt64 inRecordCount, UInt32 inLongestEntry, UInt32 inKernelVariant,
+                                            UInt32 inSubfingerprintLength, UInt32 inQueryLength, UInt32 inQueriesLeft, UInt32 inRange,
+                                            UInt32 inScores, UInt32 inHostBlocks, UInt32 inComputeUnits, UInt32* outWords,
+                                            UInt32 inCapacity) {
+    LBAD_GUARD_BEGIN
+    if (!outWords || inCapacity < 21 || inQueryLength == 0 || inQueriesLeft == 0 || inComputeUnits == 0 ||
+        (inLengthCount && (!inEntryLengths || !inEntryCounts)) || !lbad::sliding_supported(inSubfingerprintLength))
+        return kLBAudioDetectiveArgumentInvalid;
+    std::map<uint32_t, uint64_t> hist;
+    for (UInt32 i = 0; i < inLengthCount; ++i) hist[inEntryLengths[i]] += inEntryCounts[i];
+    lbad::SlideCorpusStats stats;
+    stats.len_hist = &hist; stats.n_pos = inRecordCount; stats.ne_max = inLongestEntry; stats.variant = inKernelVariant;
+    stats.subfp_len = inSubfingerprintLength;
+    lbad::SlideGroup group;
+    group.n_query = inQueryLength; group.n_left = inQueriesLeft; group.range = inRange ? inRange : inSubfingerprintLength;
+    group.scores = inScores != 0; group.host_blocks = inHostBlocks != 0;
+    lbad::sliding_choice_words(lbad::sliding_choose(stats, group, inComputeUnits), inQueryLength, outWords);
+    return noErr;
     LBAD_GUARD_END
 }
 
@@ -944,7 +948,7 @@ struct CorpusFileHeader {
 // ragged corpus file: header, the entries' sub-fingerprint counts, the records
 namespace {
 struct RaggedFileHeader {
-    char magic[8];            // "LBADCRP3" (round-4 record layout, k_sliding.hip); "LBADCRP2" files (round 3) still load
+    char magic[8];            // "LBADCRP3" (round-4 record layout, sliding_common.hpp); "LBADCRP2" files (round 3) still load
     uint32_t subfp_len, reserved;
     uint64_t count, n_pos;
 };

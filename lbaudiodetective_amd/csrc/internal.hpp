@@ -291,11 +291,15 @@ hipError_t launch_align_keys(const AlignSource& src, const uint32_t* d_qwords, c
 hipError_t launch_align_profile(const AlignSource& src, const uint32_t* d_qwords, uint32_t n_query, uint64_t entry, uint64_t n_offsets,
                                 float* d_out, hipStream_t stream);
 
-// ragged corpus (k_sliding.hip): a stream of 32-byte sub-fingerprint records, entries of any length back to back
+// ragged corpus: a stream of 32-byte sub-fingerprint records, entries of any length back to back (sliding_common.hpp has the
+// layout).  sliding.cpp: the host side; k_records.hip, k_sliding.hip, k_sliding_short.hip: the kernels
 bool sliding_supported(uint32_t subfp_len);
-uint32_t sliding_query_words(uint32_t n_query);
+// words of the scan's block of a query of n_query sub-fingerprints: 16 per sub-fingerprint and one zero sub-fingerprint of slack
+constexpr size_t sliding_block_words(size_t n_query) { return (n_query + 1u) * 16u; }
+// the block of one query from unpacked Booleans (n_query x subfp_len)
 void build_sliding_query(const Boolean* bools, uint32_t n_query, uint32_t subfp_len, uint32_t range,
                          std::vector<uint32_t>& out);
+uint4 sliding_range_mask(uint32_t subfp_len, uint32_t range);    // pairs inside min(range, length), one bit each
 // d_off_new: ABSOLUTE record positions of the n_new new entries (n_new + 1 values, the first one = slot 0's position)
 hipError_t launch_pack_records(const uint32_t* d_slots, uint64_t n_new_pos, const uint32_t* d_off_new, uint64_t n_new,
                                uint32_t first_entry, uint4* d_recs, hipStream_t stream);
@@ -305,49 +309,90 @@ hipError_t launch_restamp_records(uint4* d_recs, const uint32_t* d_off, uint64_t
                                   bool old_layout, hipStream_t stream);
 hipError_t launch_synth_ragged(uint32_t seed, uint64_t first_entry, uint64_t n_entries, const uint32_t* d_off,
                                uint64_t n_pos, uint32_t subfp_len, uint32_t* d_out, hipStream_t stream);
-// shape of a scan: workgroups (one per CU) and the tasks of either kind each of them owns
+
+// ---- the scan of a ragged corpus: ONE decision per launch (sliding.cpp: sliding_choose), handed to the launcher ----------------
+// shape of a task scan: workgroups (one per CU) and the tasks of either kind each of them owns
 struct SlideShape {
     uint32_t grid = 0, chunk_a = 0, chunk_b = 0;
 };
-constexpr uint32_t kSlideMaxGrid = 1024;
-SlideShape sliding_shape(uint64_t tasks_a, uint64_t tasks_b, uint32_t n_q = 1);
-// how many of n_left queries of one length a single launch takes (1, 2, 4; 8 for the systolic scan of short queries)
-uint32_t sliding_queries_per_launch(uint32_t n_query, uint32_t ne_max, uint32_t n_left);
-bool sliding_multi(uint32_t n_query, uint32_t ne_max);    // a batch of such queries takes compare_short_multi_kernel (keys max-ed in place)
-// One launch of the scan: n_q queries of one length.  d_queries: their blocks (build_sliding_query without the header),
-// (n_query + 1) * 16 words each, on the device; h_query: the same block of a single query on the host -- short enough it
-// travels in the kernel's arguments and d_queries may be null.  d_acc (n_q words) and d_ticket are zero between scans
-// (the scan leaves them so); d_keys receives the n_q results.
+// what the decision looks at.  The corpus: its histogram of entry lengths, records stored, longest entry, kernel variant (3
+// forces the split of the scan where one exists, 4 forbids it)
+struct SlideCorpusStats {
+    const std::map<uint32_t, uint64_t>* len_hist = nullptr;
+    uint64_t n_pos = 0;
+    uint32_t ne_max = 0, variant = 0, subfp_len = 0;
+};
+// ... and the queries: their length, how many of that length are still to go, the range (>= 1), whether per-entry scores are
+// wanted (one query per launch then) and whether the blocks are on the host (a short single query can travel in the kernel's
+// arguments) or on the device already
+struct SlideGroup {
+    uint32_t n_query = 0, n_left = 0, range = 0;
+    bool scores = false, host_blocks = false;
+};
+enum class SlideKernel : uint32_t { Task = 0, Short = 1, ShortMulti = 2 };   // compare_sliding_ / compare_short_ / compare_short_multi_kernel
+// One launch of the scan, decided: everything the corpus' side (ring, plan cache, zeroing of keys) and the launcher need.
+struct SlideChoice {
+    uint32_t n_take = 0;               // queries this launch takes (0: there is no such launch -- a task count beyond 32 bits)
+    SlideKernel kernel = SlideKernel::Task;
+    // the instance: compare_sliding_kernel<full, false, qlds, n_take, threads>, compare_short_kernel<look <= 6 ? 1 : 4, n_take>,
+    // compare_short_multi_kernel<n_take, n_query>
+    bool full = false, qlds = false;
+    uint32_t threads = 0;
+    uint32_t look = 0;                 // Short: records a window reaches back
+    // b_min > 0: the scan is SPLIT -- "B" entries (not longer than the query) of fewer sub-fingerprints go through the systolic
+    // scan in a second launch, and tasks_b and the plan count only the others
+    uint32_t b_min = 0;
+    uint64_t tasks_a = 0, tasks_b = 0; // groups of four sliding offsets over the entries longer / not longer than the query
+    SlideShape shape;
+    bool reads_plan = false;           // only the task kernel walks the plan's runs of entries
+    bool q_in_args = false;            // the single query's block travels in the kernel's argument segment, nothing is copied
+    bool maxes_keys = false;           // the launch maxes its keys in place: they must be zero in front of it
+    // a systolic launch over the same keys follows (the short entries of a split scan, or what compare_short_multi_kernel
+    // leaves: the entries not longer than the query)
+    bool second = false;
+    uint32_t second_look = 0, second_only_upto = 0;
+    uint32_t cus = 0;                  // compute units the grids were sized for
+};
+SlideChoice sliding_choose(const SlideCorpusStats& corpus, const SlideGroup& group, uint32_t cus);
+void sliding_choice_words(const SlideChoice& ch, uint32_t n_query, uint32_t* out21);    // LBAudioDetectiveDebugSlidingChoice's words
+
+// The corpus as the scan's kernels read it (cf. AlignSource)
+struct SlideCorpus {
+    const uint4* recs = nullptr;
+    uint64_t n_pos = 0;                // records stored
+    const uint32_t* off = nullptr;     // n_entries + 1 record positions
+    uint64_t n_entries = 0;
+    uint32_t zero_rec = 0;             // index of an all-zero record behind the stored ones
+    uint32_t subfp_len = 0;
+    const uint32_t* plan = nullptr;    // launch_sliding_plan's output for this query length (read when choice.reads_plan)
+};
+// The queries of one launch and where their keys go.  d_queries: choice.n_take blocks of sliding_block_words(n_query) words, one
+// after the other, on the device; h_query: the same block of a single query on the host when choice.q_in_args (d_queries may
+// be null then).  d_acc (8 words) and d_ticket are zero between scans (the scan leaves them so); d_keys receives the results.
 struct SlideScan {
     const uint32_t* d_queries = nullptr;
     const uint32_t* h_query = nullptr;
-    uint32_t n_q = 1;
     unsigned long long* d_acc = nullptr;
     unsigned int* d_ticket = nullptr;
     unsigned long long* d_keys = nullptr;
     uint32_t key_pos[8] = {};     // query i's key goes to d_keys[key_pos[i]]
 };
-constexpr uint32_t kSlideQueryArgSubs = 47;   // longest query that travels as a kernel argument
+// the scalars of a call.  d_score_bits (optional, one query only; n_entries words) must be zero on entry and receives the
+// float bits of every entry's match
+struct SlideCall {
+    uint32_t n_query = 0, range = 0;
+    uint64_t index_base = 0;
+    unsigned int* d_score_bits = nullptr;
+    bool bound_pruning = true;
+    float prune_from = 0.7f;
+    hipStream_t stream = nullptr;
+};
 size_t sliding_plan_words(uint64_t capacity);
 // the plan of a query length (where every workgroup's run of entries starts) into d_plan
 hipError_t launch_sliding_plan(const uint32_t* d_off, uint64_t n_entries, uint32_t n_query, uint32_t b_min, const SlideShape& sh,
                                uint32_t* d_plan, hipStream_t stream);
-// tasks_a / tasks_b: groups of four sliding offsets over the entries longer / not longer than the query; d_query: the
-// block build_sliding_query made; zero_rec: index of an all-zero record
-bool sliding_short(uint32_t n_query, uint32_t ne_max);    // the systolic scan of short queries applies (no plan needed)
-// does ONE launch of n_q queries read the plan?  (launch_compare_sliding's own choice of kernel: only the task kernel does;
-// tasks_a as handed to it, scores: per-entry scores are asked for)
-bool sliding_needs_plan(uint32_t n_query, uint32_t ne_max, uint32_t n_q, uint64_t tasks_a, bool scores);
-uint4 sliding_range_mask(uint32_t subfp_len, uint32_t range);    // pairs inside min(range, length), one bit each
-hipError_t launch_compare_sliding(const uint4* d_recs, uint64_t n_pos, const uint32_t* d_off, uint64_t n_entries, uint32_t ne_max,
-                                  uint32_t zero_rec, uint64_t tasks_a, uint64_t tasks_b, const SlideShape& sh, const uint32_t* d_plan,
-                                  uint32_t subfp_len, const SlideScan& scan, uint32_t n_query, uint32_t range,
-                                  uint64_t index_base, unsigned int* d_score_bits, hipStream_t stream, bool bound_pruning = true,
-                                  float prune_from = 0.7f, uint32_t b_min = 0);
-// b_min > 0 (kSlideSplitBelow): the scan is SPLIT -- entries of fewer sub-fingerprints that are not longer than the query go
-// through the systolic scan (a second launch over the records), everything else through the task kernel; tasks_b and the
-// plan then count only the "B" entries of at least b_min sub-fingerprints
-constexpr uint32_t kSlideSplitBelow = 16;
+// performs the launches the choice names
+hipError_t launch_compare_sliding(const SlideCorpus& src, const SlideChoice& choice, const SlideScan& scan, const SlideCall& call);
 // limits of a ragged corpus (the key carries a 32-bit index, the scan's claim cursor and its record offsets want a little slack)
 constexpr uint64_t kMaxRaggedEntries = 0xFFFF0000ull;
 constexpr uint64_t kMaxRaggedRecords = 0xFFFFFF00ull;
@@ -358,7 +403,7 @@ constexpr uint32_t kRecordSlack = 8;   // records allocated behind a ragged corp
 // plane blocks: plane_query_words() words per query (build_plane_query, zero padded), per == n_sub, length 200
 hipError_t launch_build_plane_queries(const uint32_t* d_rows, uint32_t n_queries, uint32_t n_sub, uint32_t range,
                                       uint32_t* d_blocks, hipStream_t stream);
-// sliding blocks: (per + 1) * 16 words per query (build_sliding_query without its header); d_blocks 16-byte aligned
+// sliding blocks: sliding_block_words(per) words per query (build_sliding_query's); d_blocks 16-byte aligned
 hipError_t launch_build_sliding_queries(const uint32_t* d_rows, uint32_t n_queries, uint32_t per, uint32_t subfp_len, uint32_t range,
                                         uint32_t* d_blocks, hipStream_t stream);
 // 8 words per sub-fingerprint to d_words (16-byte aligned): the slot words cleared from the length on (the generic uniform
@@ -512,7 +557,7 @@ struct LBAudioDetectiveCorpus {
     size_t query_slot_words = 0;
     lbad::Event query_ev[8];
     // per ring slot: the scan's running maxima (8 words) and its ticket, ZERO between scans -- the scan's last workgroup
-    // leaves them so (k_sliding.hip: ScanOut); 16 words per slot
+    // leaves them so (sliding_common.hpp: ScanOut); 16 words per slot
     lbad::DeviceBuffer<unsigned long long> d_scan_out;
     bool scan_out_dirty = false;                 // a scan's launch failed: clear the words before the next one
     std::mutex shard_lock;                       // the sharded query's key block is one per corpus (api_rccl.cpp)

@@ -9,9 +9,9 @@
 //   score  = max_o q_o (never below 0: the reference's MAX starts from 0),  offset = the lowest o with q_o == score
 //   lag    = +offset in A (the query's sub-fingerprint 0 lies on the entry's sub-fingerprint lag),
 //            -offset in B (the entry's sub-fingerprint 0 lies on the query's sub-fingerprint -lag)
-// ratio is the compare of the scans (k_compare.hip, k_sliding.hip): `possible` counts fingerprint1's non-zero pairs inside the
+// ratio is the compare of the scans (k_compare.hip, k_sliding.hip, k_sliding_short.hip): `possible` counts fingerprint1's non-zero pairs inside the
 // range, hits the pairs where both Booleans agree, and the quotient is correctly rounded -- an IEEE division here, the same
-// values k_sliding.hip reads from its table.  score is therefore, bit for bit, what LBAudioDetectiveCorpusScoresDevice returns.
+// values the ragged scans read from their table (sliding.cpp: sliding_tri_table).  score is therefore, bit for bit, what LBAudioDetectiveCorpusScoresDevice returns.
 //
 // Alignment runs AFTER selection, on the pairs the top-1 / top-K paths hand over as 64-bit keys on the device
 // (score bits << 32 | 0xFFFFFFFF - global index), so the tuned scans stay as they are.  Lanes own offsets: a workgroup is one
@@ -21,7 +21,7 @@
 // turns them into lags.  With one part per pair the workgroup writes its result itself.  A key that is zero or whose index
 // lies outside [index_base, index_base + count) gives lag 0 and score 0; nothing outside the corpus or the queries is read.
 //
-// Both corpus layouts: the ragged records of k_sliding.hip (32 bytes, pairs de-interleaved: P in w0..w2 + w3 bits 0..3, N in
+// Both corpus layouts: the ragged records of sliding_common.hpp (32 bytes, pairs de-interleaved: P in w0..w2 + w3 bits 0..3, N in
 // w4..w6 + w7 bits 0..3; the derived bits above them never meet the range mask) and the uniform planes of k_compare.hip (a
 // tight bitstream of n_sub * Lp bits per entry, word w of entry e in plane w >> 2 at planes[(w >> 2) * stride + e]).  A query
 // sub-fingerprint is eight words in the layout of its corpus: P[4] N[4] (ragged) or the packed slot words (uniform).

@@ -1,6 +1,6 @@
 // k_query.hip -- the scans' query blocks built ON the device from packed sub-fingerprints (8 little-endian words each, the
 // layout LBAudioDetectiveFingerprintClipsDevice writes and LBAudioDetectiveCorpusAppendPackedDevice reads): what the host
-// builders build_plane_query (k_compare.hip), build_sliding_query (k_sliding.hip) and build_align_query (k_align.hip) make from
+// builders build_plane_query (k_compare.hip), build_sliding_query (sliding.cpp) and build_align_query (k_align.hip) make from
 // a fingerprint handle's Booleans, word for word, so that a query that is already in HBM never visits the host.  Every
 // builder first clears the bits at or above the sub-fingerprint length: the result depends on the first `length` Booleans only.
 // Not a hot loop -- a lane per output word or per sub-fingerprint, nothing kept in indexed arrays (no scratch memory).
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(kQbThreads) void build_plane_queries_kernel(const u
     blocks[t] = v;
 }
 
-// ---- ragged corpus: build_sliding_query without its header -- one lane per sub-fingerprint (and per block's zero slack) -----
+// ---- ragged corpus: build_sliding_query's block -- one lane per sub-fingerprint (and per block's zero slack) -----
 __global__ __launch_bounds__(kQbThreads) void build_sliding_queries_kernel(const uint32_t* __restrict__ rows, uint64_t n_queries,
                                                                            uint32_t per, uint32_t subfp_len, uint4 rm,
                                                                            uint4* __restrict__ blocks) {

@@ -204,7 +204,7 @@ def test_ragged_save_load(lb, gpu, oracle, tmp_path):
 
 
 def _record_words(row, L, old_layout):
-    """One sub-fingerprint of L Booleans as the eight words of a corpus-file record (k_sliding.hip): round-4 layout
+    """One sub-fingerprint of L Booleans as the eight words of a corpus-file record (sliding_common.hpp): round-4 layout
     or the round-3 one ("LBADCRP2": P at bits 0..99, N at bits 100..199, place fields above)."""
     pairs = (L + 1) // 2
     P = sum(int(row[2 * p]) << p for p in range(pairs))
@@ -764,3 +764,78 @@ def test_pass_of_a_scan_never_spans_more_than_its_offsets_can_address(lb, gpu, o
             idx, score = corpus.query(fq)
             assert (idx, _bits(score)) == (want_index, _bits(bs)), (pruning, idx, score, want_index, bs)
     corpus.dispose()
+
+
+def _launched_instances(lb, entries, L, nq, n, rg, cus):
+    """The kernel instances a call with n queries of nq sub-fingerprints launches, from the scan's own decision
+    (LBAudioDetectiveDebugSlidingChoice): (kernel, template arguments) of every launch, the systolic second launches included."""
+    lens = np.array([e.shape[0] for e in entries])
+    hist = [(int(v), int(k)) for v, k in zip(*np.unique(lens, return_counts=True))]
+    out, left = [], n
+    while left:
+        w = lb.debug_sliding_choice(hist, int(lens.sum()), int(lens.max()), 0, L, nq, left, rg, False, True, cus)
+        assert 0 < w[0] <= left, (nq, left, w)
+        out.append((("sliding", "short", "short_multi")[w[1]],) + tuple(w[2:6]))
+        if w[17]:
+            out.append(("short", 1 if w[18] <= 6 else 4, w[0], 0, 0))
+        left -= w[0]
+    return out
+
+
+def test_every_scan_instance_is_launched_once(lb, gpu, oracle):
+    """Every kernel returns the same bits, so nothing but the decision itself (tests/test_sliding_choice_cpu.py) shows which one
+    ran.  Here each of the 52 scan instances -- 8 compare_sliding_kernel, 8 compare_short_kernel, 36 compare_short_multi_kernel --
+    runs at least once on a tiny corpus, bit-exact against the oracle; which instance a call takes is predicted through the
+    decision's debug entry point, and the union must be all of them."""
+    L = 200
+    rng = np.random.default_rng(5200)
+    cus = gpu.cuda.get_device_properties(0).multi_processor_count
+    seen = set()
+
+    def run(corpus, entries, nq, n, rg):
+        seen.update(_launched_instances(lb, entries, L, nq, n, rg, cus))
+        qs = []
+        for _ in range(n):
+            q = _rand_fp(rng, nq, L, p_zero=0.05, p_both=0.02)
+            src = entries[int(rng.integers(0, len(entries)))]
+            k = min(nq, src.shape[0])
+            q[:k] = src[:k]
+            q[::3, :30] ^= 1
+            qs.append(q)
+        fps = [lb.Fingerprint.from_bools(q) for q in qs]
+        got = corpus.query_batch(fps, rg) if n > 1 else [corpus.query(fps[0], rg)]
+        for q, g in zip(qs, got):
+            bi, bs = oracle.corpus_best_ragged(q, entries, rg if rg else L)
+            assert (g[0], _bits(g[1])) == (bi, _bits(bs)), (nq, n, rg, g, bi, bs)
+
+    # A: entries of 1..7 -- the systolic scan with one record per lane, whatever the query
+    lens = rng.integers(1, 8, 100)
+    lens[:2] = [7, 1]
+    entries = [_rand_fp(rng, int(n), L) for n in lens]
+    corpus, _ = _ragged_corpus(lb, gpu, entries, L)
+    for nq, n in ((3, 1), (9, 1), (9, 2), (9, 4), (9, 8)):
+        run(corpus, entries, nq, n, 0)
+    # B: entries of 1..12 and a query of 14 -- windows reach back eleven records: four records per lane
+    lens = rng.integers(1, 13, 100)
+    lens[:2] = [12, 1]
+    entries = [_rand_fp(rng, int(n), L) for n in lens]
+    corpus, _ = _ragged_corpus(lb, gpu, entries, L)
+    for n in (1, 2, 4):
+        run(corpus, entries, 14, n, 0)
+    # C: entries of 1..40 and one of 500 -- batches of short queries (and what they leave to the systolic scan), the task scan
+    lens = rng.integers(1, 41, 201)
+    lens[:3] = [500, 40, 1]
+    entries = [_rand_fp(rng, int(n), L) for n in lens]
+    corpus, _ = _ragged_corpus(lb, gpu, entries, L)
+    for nq in range(1, 13):
+        for n in (2, 4, 8):
+            run(corpus, entries, nq, n, 0)
+    for rg in (0, 7):
+        for n in (1, 2, 4):
+            run(corpus, entries, 21, n, rg)
+        run(corpus, entries, 481, 1, rg)
+
+    want = {("sliding", full, 1, qn, 1024) for full in (0, 1) for qn in (1, 2, 4)} | {("sliding", full, 0, 1, 1024) for full in (0, 1)}
+    want |= {("short", k, qn, 0, 0) for k in (1, 4) for qn in (1, 2, 4, 8)}
+    want |= {("short_multi", qn, nq, 0, 0) for qn in (2, 4, 8) for nq in range(1, 13)}
+    assert len(want) == 52 and seen == want, (sorted(want - seen), sorted(seen - want))

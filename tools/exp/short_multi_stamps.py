@@ -26,14 +26,14 @@ for nq in [int(v) for v in sys.argv[1:]] or [5]:
     for _ in range(3):
         c.query_batch_keys_device(fps, keys)
     torch.cuda.synchronize()
-    L.LBAudioDetectiveDebugSlideTimesReset()
+    L.LBAudioDetectiveDebugShortTimesReset()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     c.query_batch_keys_device(fps, keys)
     e1.record()
     torch.cuda.synchronize()
     tb = (C.c_ulonglong * (256 * 16 * 8))()
-    L.LBAudioDetectiveDebugSlideTimes(tb, 256 * 16 * 8)
+    L.LBAudioDetectiveDebugShortTimes(tb, 256 * 16 * 8)
     t = np.array(list(tb), dtype=np.float64).reshape(-1, 8)
     full = t.copy()
     if full[:, 0].min() > 0:

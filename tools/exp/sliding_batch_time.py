@@ -1,4 +1,4 @@
-"""Several queries of one length in one pass over the ragged corpus (k_sliding.hip, round 5): time of a batch of 1, 2, 4, 8
+"""Several queries of one length in one pass over the ragged corpus (k_sliding.hip, k_sliding_short.hip; round 5): time of a batch of 1, 2, 4, 8
 queries through LBAudioDetectiveCorpusQueryBatchKeysDevice against eight single scans; results checked against each other."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

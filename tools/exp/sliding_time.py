@@ -1,4 +1,4 @@
-"""Scan time of the ragged corpus (k_sliding.hip): 1 M synthetic entries of 20..70 sub-fingerprints, query of
+"""Scan time of the ragged corpus (k_sliding.hip, k_sliding_short.hip): 1 M synthetic entries of 20..70 sub-fingerprints, query of
 --nq sub-fingerprints; HIP events on the launch stream around `reps` key-only scans."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

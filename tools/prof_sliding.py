@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Driver for rocprofv3 passes over the ragged-corpus scan (k_sliding.hip):
+"""Driver for rocprofv3 passes over the ragged-corpus scan (k_sliding.hip, k_sliding_short.hip):
     python3 tools/prof_sliding.py [n_entries] [n_query] [lo] [hi] [reps]
 1 M synthetic entries of lo..hi sub-fingerprints, a query of n_query cut out of entry 777 777; `reps` key-only scans.
 A device-to-device copy of the record buffer's size follows (known byte count: calibrates FETCH_SIZE / WRITE_SIZE)."""

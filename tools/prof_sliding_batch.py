@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Driver for rocprofv3 passes over a BATCH of queries against the ragged corpus (k_sliding.hip, round 5):
+"""Driver for rocprofv3 passes over a BATCH of queries against the ragged corpus (k_sliding.hip, k_sliding_short.hip; round 5):
     python3 tools/prof_sliding_batch.py [n_entries] [n_query] [batch] [reps]
 `batch` queries of n_query sub-fingerprints through LBAudioDetectiveCorpusQueryBatchKeysDevice (four per launch of the task
 scan, eight of the systolic scan of short queries)."""

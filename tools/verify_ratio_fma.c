@@ -1,4 +1,4 @@
-/* Exhaustive check of the table-free ratio of compare_short_multi_kernel (k_sliding.hip, round 6):
+/* Exhaustive check of the table-free ratio of compare_short_multi_kernel (k_sliding_short.hip, round 6):
  *     pf = (float)possible;  rh = 1.0f / pf;  rl = fma(-pf, rh, 1.0f) * rh;
  *     ratio = fma(hf, rh, hf * rl)                                   with hf = (float)hits
  * against the correctly rounded (float)hits / (float)possible of LBAudioDetectiveFingerprint.m:175, for EVERY

@@ -520,6 +520,52 @@ OSStatus LBAudioDetectiveCorpusQueryBatchTopKKeysDevice(LBAudioDetectiveCorpusRe
  * that are <= 0 or NaN are never selected.  Allocates its own scratch and returns once the keys are written. */
 OSStatus LBAudioDetectiveTopKKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, UInt32 inK,
                                                   UInt64 inIndexBase, void* outKeys, void* inStream);
+/* Threshold queries: EVERY entry whose score reaches inThreshold, selected on the device -- "which entries match this query at
+ * all" (unrelated fingerprints score 0.5 +- 0.03, a real match far above: 0.7 is the level bound pruning starts from as well).
+ * Entry e scores exactly what LBAudioDetectiveCorpusScoresDevice returns for it and matches when score >= inThreshold as
+ * Float32 values (a NaN never matches).  A row has inCapacity slots: the first min(count, inCapacity) matches in ASCENDING
+ * entry index, then index -1, score 0 (and lag 0).  The count is always the TRUE number of matches: count > inCapacity tells
+ * that the list was cut, which is no error.  inThreshold is finite and > 0 (above 1 is legal and matches nothing),
+ * inCapacity >= 1, inCount x inCapacity <= 2^31, inRange == 0 means the sub-fingerprint length, queries of the corpus'
+ * sub-fingerprint length, inIndexBase + entries <= 2^32; NULL handles and pointers are kLBAudioDetectiveArgumentInvalid, and
+ * without a device every call returns kLBAudioDetectiveDeviceUnavailable.  An empty corpus gives counts 0, zero keys and zero
+ * lags.  Bound pruning never applies (these are scores scans, as for top-K).  The batch forms write inCount x inCapacity
+ * results (query q's list at q * inCapacity) and inCount counts; a batch equals inCount single calls, bit for bit.  The
+ * Aligned form adds every match's lag (see below), equal to LBAudioDetectiveCorpusAlignKeysDevice's on the same keys.
+ * The KeysDevice form writes inCount x inCapacity 64-bit keys (as the top-K calls', global index = inIndexBase + local; each
+ * row in ascending index, 0-padded -- sort a row descending for best-first) to the device pointer outKeys and inCount UInt64
+ * counts to the device pointer outCounts, asynchronously on inStream, which is never awaited.  Shards that hold contiguous
+ * index ranges merge by concatenating their rows in rank order and adding their counts.  The Packed form takes its queries
+ * as LBAudioDetectiveCorpusQueryPackedTopKKeysDevice does (nothing is copied to the host) and writes, unless outLags is NULL,
+ * inCount x inCapacity SInt32 lags to the device pointer outLags; its keys and counts equal the KeysDevice form's.  The
+ * scratch is the top-K calls' (scores, staged queries, its event) plus the selection's tile counts; a call waits for the
+ * previous top-K or threshold call's device work before it reuses it. */
+OSStatus LBAudioDetectiveCorpusQueryThreshold(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                              UInt32 inRange, Float32 inThreshold, UInt64 inCapacity, SInt64* outIndices,
+                                              Float32* outScores, UInt64* outCount);
+OSStatus LBAudioDetectiveCorpusQueryBatchThreshold(LBAudioDetectiveCorpusRef inCorpus,
+                                                   const LBAudioDetectiveFingerprintRef* inQueries, UInt32 inCount, UInt32 inRange,
+                                                   Float32 inThreshold, UInt64 inCapacity, SInt64* outIndices, Float32* outScores,
+                                                   UInt64* outCounts);
+OSStatus LBAudioDetectiveCorpusQueryBatchThresholdAligned(LBAudioDetectiveCorpusRef inCorpus,
+                                                          const LBAudioDetectiveFingerprintRef* inQueries, UInt32 inCount,
+                                                          UInt32 inRange, Float32 inThreshold, UInt64 inCapacity, SInt64* outIndices,
+                                                          Float32* outScores, SInt32* outLags, UInt64* outCounts);
+OSStatus LBAudioDetectiveCorpusQueryBatchThresholdKeysDevice(LBAudioDetectiveCorpusRef inCorpus,
+                                                             const LBAudioDetectiveFingerprintRef* inQueries, UInt32 inCount,
+                                                             UInt32 inRange, Float32 inThreshold, UInt64 inCapacity,
+                                                             UInt64 inIndexBase, void* outKeys, void* outCounts, void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                              UInt32 inCount, UInt32 inSubfingerprintsPerQuery, UInt32 inRange,
+                                                              Float32 inThreshold, UInt64 inCapacity, UInt64 inIndexBase,
+                                                              void* outKeys, void* outCounts, void* outLags, void* inStream);
+/* The selection on its own: inRows rows of inCount float32 scores (device, row r at inScores + r * inCount; any 4-byte
+ * aligned address) to inRows x inCapacity keys at outKeys and inRows UInt64 counts at outCounts (device pointers; index =
+ * inIndexBase + position in the row, inIndexBase + inCount <= 2^32, inRows x inCapacity <= 2^31).  Allocates its own scratch
+ * and returns once the keys are written. */
+OSStatus LBAudioDetectiveThresholdKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, Float32 inThreshold,
+                                                       UInt64 inCapacity, UInt64 inIndexBase, void* outKeys, void* outCounts,
+                                                       void* inStream);
 /* Where a match lies.  LBAudioDetectiveFingerprintCompareToFingerprint (Fp.m:119-149) slides the shorter fingerprint along
  * the longer one; the corpus passes the query as its first argument.  Entry longer than the query ("A"): the query slides
  * along the entry.  Otherwise ("B", equal lengths included): the entry slides along the query.  With n1 >= n2 the two counts,

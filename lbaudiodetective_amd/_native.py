@@ -170,6 +170,17 @@ _SIGNATURES = {
     "LBAudioDetectiveCorpusQueryBatchTopK": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, _P(SInt64), _P(Float32), _P(UInt32)]),
     "LBAudioDetectiveCorpusQueryBatchTopKKeysDevice": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, UInt64, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveTopKKeysFromScoresDevice": (OSStatus, [C.c_void_p, UInt64, UInt32, UInt32, UInt64, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusQueryThreshold": (OSStatus, [Ref, Ref, UInt32, Float32, UInt64, _P(SInt64), _P(Float32), _P(UInt64)]),
+    "LBAudioDetectiveCorpusQueryBatchThreshold": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, Float32, UInt64, _P(SInt64), _P(Float32),
+                                                             _P(UInt64)]),
+    "LBAudioDetectiveCorpusQueryBatchThresholdAligned": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, Float32, UInt64, _P(SInt64), _P(Float32),
+                                                                    _P(SInt32), _P(UInt64)]),
+    "LBAudioDetectiveCorpusQueryBatchThresholdKeysDevice": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, Float32, UInt64, UInt64, C.c_void_p,
+                                                                       C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, UInt32, Float32, UInt64, UInt64,
+                                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveThresholdKeysFromScoresDevice": (OSStatus, [C.c_void_p, UInt64, UInt32, Float32, UInt64, UInt64, C.c_void_p, C.c_void_p,
+                                                                 C.c_void_p]),
     "LBAudioDetectiveCorpusAlignKeysDevice": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, C.c_void_p, UInt64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusQueryBatchTopKAligned": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, _P(SInt64), _P(Float32), _P(SInt32), _P(UInt32)]),
     "LBAudioDetectiveCorpusQueryAligned": (OSStatus, [Ref, Ref, UInt32, _P(SInt64), _P(Float32), _P(SInt32)]),

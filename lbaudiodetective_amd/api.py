@@ -705,6 +705,67 @@ class Corpus:
                                                                       _stream_ptr(stream)), "CorpusQueryPackedTopKKeysDevice")
         return (keys_out, lags_out) if want_lags else keys_out
 
+    # ---- threshold queries: every entry whose score is >= threshold (a float32 compare), in ascending entry index, the first
+    # `capacity` of them; the count is always the true number of matches (count > capacity: the list was cut)
+    def query_threshold(self, fp: Fingerprint, threshold: float, capacity: int, range_: int = 0, aligned: bool = False):
+        """LBAudioDetectiveCorpusQueryThreshold: (indices int64[m], scores float32[m], count) with m = min(count, capacity), or
+        with aligned=True (indices, scores, lags int32[m], count)."""
+        return self.query_threshold_batch([fp], threshold, capacity, range_, aligned)[0]
+
+    def query_threshold_batch(self, fps, threshold: float, capacity: int, range_: int = 0, aligned: bool = False):
+        """query_threshold for several queries in one call -> list of its tuples; equal to separate calls, bit for bit."""
+        n = len(fps)
+        refs = (N.Ref * max(1, n))(*[f._ref for f in fps])
+        shape = (max(1, n), max(1, capacity))
+        idx = np.full(shape, -1, dtype=np.int64)
+        sc = np.zeros(shape, dtype=np.float32)
+        lag = np.zeros(shape if aligned else (1, 1), dtype=np.int32)
+        cnt = np.zeros(max(1, n), dtype=np.uint64)
+        pi, ps = idx.ctypes.data_as(C.POINTER(N.SInt64)), sc.ctypes.data_as(C.POINTER(N.Float32))
+        pc = cnt.ctypes.data_as(C.POINTER(N.UInt64))
+        if aligned:
+            _check(self._L.LBAudioDetectiveCorpusQueryBatchThresholdAligned(self._ref, refs, n, range_, threshold, capacity, pi, ps,
+                                                                            lag.ctypes.data_as(C.POINTER(N.SInt32)), pc),
+                   "CorpusQueryBatchThresholdAligned")
+        else:
+            _check(self._L.LBAudioDetectiveCorpusQueryBatchThreshold(self._ref, refs, n, range_, threshold, capacity, pi, ps, pc),
+                   "CorpusQueryBatchThreshold")
+        out = []
+        for i in range(n):
+            m = min(int(cnt[i]), capacity)
+            out.append((idx[i, :m].copy(), sc[i, :m].copy()) + ((lag[i, :m].copy(),) if aligned else ()) + (int(cnt[i]),))
+        return out
+
+    def query_batch_threshold_keys_device(self, fps, threshold: float, capacity: int, keys_out=None, counts_out=None, range_: int = 0,
+                                          index_base: int = 0, stream=None):
+        """LBAudioDetectiveCorpusQueryBatchThresholdKeysDevice: (keys int64 [len(fps), capacity], counts int64 [len(fps)]) on the
+        device (global index = index_base + local; rows in ascending index, 0-padded; decode a row with decode_threshold_keys),
+        asynchronously on `stream`."""
+        n = len(fps)
+        keys_out, counts_out, _ = _threshold_out(n, capacity, keys_out, counts_out, None, False, "cuda")
+        refs = (N.Ref * max(1, n))(*[f._ref for f in fps])
+        _check(self._L.LBAudioDetectiveCorpusQueryBatchThresholdKeysDevice(self._ref, refs, n, range_, threshold, capacity, index_base,
+                                                                          _dev_ptr(keys_out), _dev_ptr(counts_out),
+                                                                          _stream_ptr(stream)), "CorpusQueryBatchThresholdKeysDevice")
+        return keys_out, counts_out
+
+    def query_packed_threshold_keys_device(self, packed, n_queries: int, per_query: int, threshold: float, capacity: int,
+                                           keys_out=None, counts_out=None, lags_out=None, aligned: bool = False, range_: int = 0,
+                                           index_base: int = 0, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice: query_batch_threshold_keys_device's (keys, counts) for packed
+        fingerprints already on the device; with aligned=True (or a lags_out) also the int32 lags [n, capacity] -> (keys, counts,
+        lags).  Asynchronous on `stream`, nothing visits the host."""
+        _packed_ok(packed, n_queries, per_query)
+        want_lags = aligned or lags_out is not None
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        keys_out, counts_out, lags_out = _threshold_out(n_queries, capacity, keys_out, counts_out, lags_out, want_lags, dev)
+        _check(self._L.LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice(self._ref, _dev_ptr(packed), n_queries, per_query, range_,
+                                                                           threshold, capacity, index_base, _dev_ptr(keys_out),
+                                                                           _dev_ptr(counts_out),
+                                                                           _dev_ptr(lags_out) if want_lags else None,
+                                                                           _stream_ptr(stream)), "CorpusQueryPackedThresholdKeysDevice")
+        return (keys_out, counts_out, lags_out) if want_lags else (keys_out, counts_out)
+
     # ---- where a match lies (LBAudioDetectiveCorpusQueryAligned and kin): lag > 0, the query's sub-fingerprint 0 lines up
     # with the entry's sub-fingerprint lag (the entry is the longer one); lag < 0, the entry's sub-fingerprint 0 lines up with
     # the query's sub-fingerprint -lag; 0 for equal lengths and for empty slots.  Positions in seconds: lag x 128 x analysis
@@ -785,6 +846,23 @@ def _packed_ok(packed, n_queries: int, per_query: int):
 def _out_ok(out, n: int, what: str):
     if hasattr(out, "data_ptr") and (not out.is_cuda or not out.is_contiguous() or out.numel() < n):
         raise ValueError(f"{what} must be a contiguous device tensor of at least {n} elements")
+
+
+def _threshold_out(n: int, capacity: int, keys_out, counts_out, lags_out, want_lags: bool, device):
+    """the outputs of a threshold call on the device: made where they are missing, checked where they are given"""
+    if keys_out is None or counts_out is None or (want_lags and lags_out is None):
+        import torch
+        if keys_out is None:
+            keys_out = torch.empty((max(1, n), max(1, capacity)), dtype=torch.int64, device=device)
+        if counts_out is None:
+            counts_out = torch.empty(max(1, n), dtype=torch.int64, device=device)
+        if want_lags and lags_out is None:
+            lags_out = torch.empty((max(1, n), max(1, capacity)), dtype=torch.int32, device=device)
+    _out_ok(keys_out, n * capacity, "keys_out")
+    _out_ok(counts_out, n, "counts_out")
+    if want_lags:
+        _out_ok(lags_out, n * capacity, "lags_out")
+    return keys_out, counts_out, lags_out
 
 
 def identify_clips_device(det: "Detective", corpus: "Corpus", clips, k: int = 1, aligned: bool = False, range_: int = 0, stream=None):
@@ -941,6 +1019,28 @@ def decode_topk_keys(keys):
     """(indices int64[n], scores float32[n]) of one row of top-K keys (any int64 sequence; zero keys are padding)."""
     k = np.asarray(keys.cpu().numpy() if hasattr(keys, "cpu") else keys, dtype=np.int64).astype(np.uint64)
     k = k[k != 0]
+    return (0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32)
+
+
+def threshold_keys_from_scores_device(scores, threshold: float, capacity: int, index_base: int = 0, keys_out=None, counts_out=None,
+                                      stream=None):
+    """LBAudioDetectiveThresholdKeysFromScoresDevice: per row of `scores` (torch float32 on the device, [n] or [rows, n]) the keys
+    of the positions whose score is >= threshold, in ascending position, cut at `capacity`, 0-padded -> (keys int64 [rows,
+    capacity], counts int64 [rows]) (or ([capacity], scalar tensor) for a 1-d input); the counts are never cut."""
+    s = scores if scores.is_contiguous() else scores.contiguous()
+    rows, n = (1, s.numel()) if s.dim() == 1 else (s.shape[0], s.shape[1])
+    keys_out, counts_out, _ = _threshold_out(rows, capacity, keys_out, counts_out, None, False, s.device)
+    _check(N.lib().LBAudioDetectiveThresholdKeysFromScoresDevice(s.data_ptr(), n, rows, threshold, capacity, index_base,
+                                                                 _dev_ptr(keys_out), _dev_ptr(counts_out), _stream_ptr(stream)),
+           "ThresholdKeysFromScoresDevice")
+    return (keys_out[0], counts_out[0]) if s.dim() == 1 else (keys_out, counts_out)
+
+
+def decode_threshold_keys(row, count=None):
+    """(indices int64[m], scores float32[m]) of one row of threshold keys (any int64 sequence), m = min(count, len(row)) -- or,
+    without a count, the keys in front of the zero padding.  The order is the row's: ascending index."""
+    k = np.asarray(row.cpu().numpy() if hasattr(row, "cpu") else row, dtype=np.int64).astype(np.uint64).reshape(-1)
+    k = k[k != 0] if count is None else k[:min(int(count), len(k))]
     return (0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32)
 
 

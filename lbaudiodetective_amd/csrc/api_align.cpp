@@ -115,6 +115,16 @@ OSStatus align_keys_built(LBAudioDetectiveCorpus* c, const uint2* d_desc, const 
     return c->align_ev.record(stream);
 }
 
+// the same for queries given as handles (any k: the threshold queries align as many slots as a row has)
+OSStatus align_keys_handles(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range, uint32_t k,
+                            const unsigned long long* keys, uint64_t index_base, int32_t* lags, hipStream_t stream) {
+    if (!queries_ok(qs, n) || k == 0 || !keys || !lags || !corpus_ok(c, qs, n)) return kLBAudioDetectiveArgumentInvalid;
+    OSStatus st = c->align_ev.wait_or_create();
+    if (st == noErr) st = align_keys_impl(c, qs, n, range, k, keys, index_base, lags, nullptr, stream);
+    if (st != noErr) return st;
+    return c->align_ev.record(stream);
+}
+
 }  // namespace lbad
 
 extern "C" {

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <functional>
 
@@ -588,25 +589,66 @@ OSStatus reserve_topk(LBAudioDetectiveCorpus* c, uint32_t n) {
     return st;
 }
 
+// The score rows of one group of g <= kQueryBatchMax staged queries (q0 the group's first) to d_topk_scores, row i at i * count:
+// d_qblocks given (the batch scan's blocks of ALL the call's queries, on the device): ONE pass of the batch scan; otherwise
+// scan_one per query.
+OSStatus scan_group_scores(LBAudioDetectiveCorpus* c, uint32_t q0, uint32_t g, hipStream_t stream, const uint32_t* d_qblocks,
+                           const ScoreScan& scan_one) {
+    if (d_qblocks) {
+        LBAD_HIP(launch_compare_planes_batch_scores(c->d_planes, c->capacity, c->count, c->n_sub,
+                                                    d_qblocks + (size_t)q0 * plane_query_words(), g, c->d_topk_scores, stream));
+        return noErr;
+    }
+    for (uint32_t i = 0; i < g; ++i) {
+        OSStatus st = scan_one(q0 + i, c->d_topk_scores + (size_t)i * c->count, c->d_topk_scan_keys + i);
+        if (st != noErr) return st;
+    }
+    return noErr;
+}
+
 // The scans and the selection of n staged queries, their keys to keys (device, n x k): groups of up to kQueryBatchMax queries
-// write their score rows -- d_qblocks given (the batch scan's blocks of all n queries, on the device): ONE pass of the batch
-// scan; otherwise scan_one per query -- then one selection over the group's rows.
+// write their score rows (scan_group_scores), then one selection over the group's rows.
 OSStatus topk_scan_select(LBAudioDetectiveCorpus* c, uint32_t n, uint32_t k, uint64_t index_base, unsigned long long* keys,
                           hipStream_t stream, const uint32_t* d_qblocks, const ScoreScan& scan_one) {
-    const uint32_t kw = plane_query_words();
     for (uint32_t q0 = 0; q0 < n; q0 += kQueryBatchMax) {
         const uint32_t g = n - q0 < kQueryBatchMax ? n - q0 : kQueryBatchMax;
-        if (d_qblocks) {
-            LBAD_HIP(launch_compare_planes_batch_scores(c->d_planes, c->capacity, c->count, c->n_sub, d_qblocks + (size_t)q0 * kw, g,
-                                                        c->d_topk_scores, stream));
-        } else {
-            for (uint32_t i = 0; i < g; ++i) {
-                OSStatus st = scan_one(q0 + i, c->d_topk_scores + (size_t)i * c->count, c->d_topk_scan_keys + i);
-                if (st != noErr) return st;
-            }
-        }
+        OSStatus st = scan_group_scores(c, q0, g, stream, d_qblocks, scan_one);
+        if (st != noErr) return st;
         LBAD_HIP(launch_topk_keys(c->d_topk_scores, c->count, g, k, index_base, c->d_topk_scratch, keys + (size_t)q0 * k, stream));
     }
+    return noErr;
+}
+
+// ... and the same scans with the threshold selection of k_threshold.hip behind them: n x capacity keys and n counts
+OSStatus threshold_scan_select(LBAudioDetectiveCorpus* c, uint32_t n, float threshold, uint64_t capacity, uint64_t index_base,
+                               unsigned long long* keys, unsigned long long* counts, hipStream_t stream, const uint32_t* d_qblocks,
+                               const ScoreScan& scan_one) {
+    for (uint32_t q0 = 0; q0 < n; q0 += kQueryBatchMax) {
+        const uint32_t g = n - q0 < kQueryBatchMax ? n - q0 : kQueryBatchMax;
+        OSStatus st = scan_group_scores(c, q0, g, stream, d_qblocks, scan_one);
+        if (st != noErr) return st;
+        LBAD_HIP(launch_threshold_keys(c->d_topk_scores, c->count, g, threshold, capacity, index_base, c->d_threshold_scratch,
+                                       keys + (size_t)q0 * capacity, counts + q0, stream));
+    }
+    return noErr;
+}
+
+// the batch scan's blocks of n queries (uniform corpus, the specialised shape) through the pinned staging copy to the device,
+// every group's at once: the copy is asynchronous on `stream`
+OSStatus stage_plane_queries(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
+                             hipStream_t stream) {
+    const uint32_t kw = plane_query_words();
+    const size_t bytes = (size_t)n * kw * sizeof(uint32_t);
+    OSStatus st = c->topk_q.reserve((size_t)n * kw);
+    if (st != noErr) return st;
+    std::memset(c->topk_q.host, 0, bytes);
+    std::vector<uint32_t> slots, block;
+    for (uint32_t i = 0; i < n; ++i) {
+        pack_fingerprint(qs[i], slots);
+        build_plane_query(slots.data(), c->n_sub, range, block);
+        std::memcpy(c->topk_q.host + (size_t)i * kw, block.data(), block.size() * sizeof(uint32_t));
+    }
+    LBAD_HIP(hipMemcpyAsync(c->topk_q.dev, c->topk_q.host, bytes, hipMemcpyHostToDevice, stream));
     return noErr;
 }
 
@@ -629,19 +671,9 @@ OSStatus topk_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerp
     }
     st = reserve_topk(c, n);
     if (st != noErr) return st;
-    const uint32_t kw = plane_query_words();
     if (batch_scan) {
-        const size_t bytes = (size_t)n * kw * sizeof(uint32_t);   // every group's blocks at once: the copies are asynchronous
-        st = c->topk_q.reserve((size_t)n * kw);
+        st = stage_plane_queries(c, qs, n, range, stream);
         if (st != noErr) return st;
-        std::memset(c->topk_q.host, 0, bytes);
-        std::vector<uint32_t> slots, block;
-        for (uint32_t i = 0; i < n; ++i) {
-            pack_fingerprint(qs[i], slots);
-            build_plane_query(slots.data(), c->n_sub, range, block);
-            std::memcpy(c->topk_q.host + (size_t)i * kw, block.data(), block.size() * sizeof(uint32_t));
-        }
-        LBAD_HIP(hipMemcpyAsync(c->topk_q.dev, c->topk_q.host, bytes, hipMemcpyHostToDevice, stream));
     }
     st = topk_scan_select(c, n, k, index_base, keys, stream, batch_scan ? c->topk_q.dev.get() : nullptr,
                           [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
@@ -784,10 +816,205 @@ OSStatus topk_host_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerp
     return noErr;
 }
 
+// ---- threshold queries: the same scores scans, then every entry at or above the threshold (k_threshold.hip) ------------------
+// what needs neither corpus nor device: a finite threshold above 0, at least one slot per row, n x capacity <= 2^31 slots
+bool threshold_args_ok(uint32_t n, float threshold, uint64_t capacity) {
+    return n != 0 && std::isfinite(threshold) && threshold > 0.0f && capacity != 0 && capacity <= 0x80000000ull &&
+           (uint64_t)n * capacity <= 0x80000000ull;
+}
+
+// score rows, the scans' key words and the selection's tile words for a call of n queries; the caller has waited for topk_ev
+OSStatus reserve_threshold(LBAudioDetectiveCorpus* c, uint32_t n) {
+    const uint32_t rows = n < kQueryBatchMax ? n : kQueryBatchMax;
+    OSStatus st = c->d_topk_scores.reserve((size_t)rows * c->count);
+    if (st == noErr) st = c->d_threshold_scratch.reserve(threshold_scratch_bytes(c->count, rows));
+    if (st == noErr) st = c->d_topk_scan_keys.reserve(kQueryBatchMax);
+    return st;
+}
+
+// zero keys (and lags) and zero counts: the answer of an empty corpus
+OSStatus threshold_nothing(uint32_t n, uint64_t capacity, unsigned long long* keys, unsigned long long* counts, int32_t* lags,
+                           hipStream_t stream) {
+    LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * capacity * sizeof(unsigned long long), stream));
+    LBAD_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(unsigned long long), stream));
+    if (lags) LBAD_HIP(hipMemsetAsync(lags, 0, (size_t)n * capacity * sizeof(int32_t), stream));
+    return noErr;
+}
+
+// n queries staged from their handles as topk_keys_impl stages them, their n x capacity keys and n counts to the device
+OSStatus threshold_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
+                             float threshold, uint64_t capacity, uint64_t index_base, unsigned long long* keys,
+                             unsigned long long* counts, hipStream_t stream) {
+    if (!qs || !keys || !counts || !threshold_args_ok(n, threshold, capacity)) return kLBAudioDetectiveArgumentInvalid;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!qs[i] || qs[i]->count == 0) return kLBAudioDetectiveArgumentInvalid;
+    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
+    if (!c || index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
+    for (uint32_t i = 0; i < n; ++i)
+        if (qs[i]->length != c->subfp_len) return kLBAudioDetectiveArgumentInvalid;
+    if (range == 0) range = c->subfp_len;   // LBAudioDetective.m:443-445
+    bool batch_scan = !c->ragged && c->variant != 1;
+    for (uint32_t i = 0; i < n && batch_scan; ++i) batch_scan = planes_fast_supported(c->subfp_len, c->n_sub, qs[i]->count);
+    OSStatus st = c->topk_ev.wait_or_create();
+    if (st != noErr) return st;
+    if (c->count == 0) {
+        st = threshold_nothing(n, capacity, keys, counts, nullptr, stream);
+        return st != noErr ? st : c->topk_ev.record(stream);
+    }
+    st = reserve_threshold(c, n);
+    if (st == noErr && batch_scan) st = stage_plane_queries(c, qs, n, range, stream);
+    if (st != noErr) return st;
+    st = threshold_scan_select(c, n, threshold, capacity, index_base, keys, counts, stream, batch_scan ? c->topk_q.dev.get() : nullptr,
+                               [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
+                                   return run_query(c, qs[q], range, 0, d_scores, d_key, stream);
+                               });
+    if (st != noErr) return st;
+    return c->topk_ev.record(stream);
+}
+
+// the packed form: the builders' blocks (build_packed), the same scans and selection, and the lags of the compacted keys
+OSStatus packed_threshold_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t n, uint32_t per, uint32_t range,
+                               float threshold, uint64_t capacity, uint64_t index_base, unsigned long long* keys,
+                               unsigned long long* counts, int32_t* lags, hipStream_t stream) {
+    if (!d_rows || !keys || !counts || per == 0 || !threshold_args_ok(n, threshold, capacity)) return kLBAudioDetectiveArgumentInvalid;
+    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
+    if (!c || index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
+    if (range == 0) range = c->subfp_len;
+    OSStatus st = c->topk_ev.wait_or_create();
+    if (st != noErr) return st;
+    BuiltQueries b;
+    st = build_packed(c, d_rows, n, per, range, lags != nullptr, stream, b);
+    if (st != noErr) return st;
+    if (c->count == 0) {
+        st = threshold_nothing(n, capacity, keys, counts, lags, stream);
+    } else {
+        st = reserve_threshold(c, n);
+        if (st == noErr)
+            st = threshold_scan_select(c, n, threshold, capacity, index_base, keys, counts, stream, b.fast ? b.scan : nullptr,
+                                       [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
+                                           return scan_built_one(c, b, q, per, range, 0, d_scores, d_key, stream);
+                                       });
+    }
+    OSStatus rec = c->topk_ev.record(stream);
+    if (st == noErr && rec == noErr && lags && c->count != 0)       // (capacity <= 2^31 slots: it fits the alignment's 32-bit k)
+        st = align_keys_built(c, b.desc, b.words, n, per, range, (uint32_t)capacity, keys, index_base, lags, stream);
+    const OSStatus rec2 = c->pq_ev.record(stream);
+    return st != noErr ? st : (rec != noErr ? rec : rec2);
+}
+
+// host-returning forms: keys, counts and (out_lags given) lags in ONE block of the corpus' own key buffer on the null stream,
+// one read-back, then decoded.  A list that was cut (count > capacity) is no error.
+OSStatus threshold_host_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
+                             float threshold, uint64_t capacity, SInt64* out_idx, Float32* out_scores, SInt32* out_lags, bool want_lags,
+                             UInt64* out_counts) {
+    if (!qs || !out_idx || !out_scores || !out_counts || (want_lags && !out_lags) || !threshold_args_ok(n, threshold, capacity))
+        return kLBAudioDetectiveArgumentInvalid;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!qs[i] || qs[i]->count == 0 || (want_lags && qs[i]->count > 0x7FFFFFFFu)) return kLBAudioDetectiveArgumentInvalid;
+    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
+    if (!c) return kLBAudioDetectiveArgumentInvalid;
+    OSStatus st = c->topk_ev.wait();    // (the key buffer is the previous call's until then)
+    const size_t slots = (size_t)n * capacity;
+    const size_t words = slots + n + (want_lags ? (slots + 1) / 2 : 0);
+    if (st == noErr) st = c->d_topk_keys.reserve(words);
+    if (st != noErr) return st;
+    unsigned long long* d_keys = c->d_topk_keys;
+    unsigned long long* d_counts = d_keys + slots;
+    int32_t* d_lags = reinterpret_cast<int32_t*>(d_counts + n);
+    st = threshold_keys_impl(c, qs, n, range, threshold, capacity, 0, d_keys, d_counts, nullptr);
+    if (st == noErr && want_lags && c->count != 0)
+        st = align_keys_handles(c, qs, n, range, (uint32_t)capacity, d_keys, 0, d_lags, nullptr);
+    if (st != noErr) return st;
+    std::vector<unsigned long long> host(words);
+    LBAD_HIP(hipMemcpy(host.data(), d_keys, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    const int32_t* lags = reinterpret_cast<const int32_t*>(host.data() + slots + n);
+    for (size_t at = 0; at < slots; ++at) {
+        LBAudioDetectiveCorpusDecodeKey(host[at], out_idx + at, out_scores + at);
+        if (want_lags) out_lags[at] = out_idx[at] >= 0 && c->count != 0 ? lags[at] : 0;
+    }
+    for (uint32_t q = 0; q < n; ++q) out_counts[q] = host[slots + q];
+    return noErr;
+}
+
 }  // namespace
 }  // namespace lbad
 
 extern "C" {
+
+OSStatus LBAudioDetectiveCorpusQueryBatchThresholdKeysDevice(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
+                                                             UInt32 inCount, UInt32 inRange, Float32 inThreshold, UInt64 inCapacity,
+                                                             UInt64 inIndexBase, void* outKeys, void* outCounts, void* inStream) {
+    LBAD_GUARD_BEGIN
+    return lbad::threshold_keys_impl(c, inQueries, inCount, inRange, inThreshold, inCapacity, inIndexBase,
+                                     static_cast<unsigned long long*>(outKeys), static_cast<unsigned long long*>(outCounts),
+                                     static_cast<hipStream_t>(inStream));
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusQueryBatchThreshold(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
+                                                   UInt32 inCount, UInt32 inRange, Float32 inThreshold, UInt64 inCapacity,
+                                                   SInt64* outIndices, Float32* outScores, UInt64* outCounts) {
+    LBAD_GUARD_BEGIN
+    return lbad::threshold_host_impl(c, inQueries, inCount, inRange, inThreshold, inCapacity, outIndices, outScores, nullptr, false,
+                                     outCounts);
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusQueryBatchThresholdAligned(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
+                                                          UInt32 inCount, UInt32 inRange, Float32 inThreshold, UInt64 inCapacity,
+                                                          SInt64* outIndices, Float32* outScores, SInt32* outLags, UInt64* outCounts) {
+    LBAD_GUARD_BEGIN
+    return lbad::threshold_host_impl(c, inQueries, inCount, inRange, inThreshold, inCapacity, outIndices, outScores, outLags, true,
+                                     outCounts);
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusQueryThreshold(LBAudioDetectiveCorpusRef c, LBAudioDetectiveFingerprintRef inQuery, UInt32 inRange,
+                                              Float32 inThreshold, UInt64 inCapacity, SInt64* outIndices, Float32* outScores,
+                                              UInt64* outCount) {
+    LBAD_GUARD_BEGIN
+    if (!inQuery) return kLBAudioDetectiveArgumentInvalid;
+    return lbad::threshold_host_impl(c, &inQuery, 1, inRange, inThreshold, inCapacity, outIndices, outScores, nullptr, false, outCount);
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice(LBAudioDetectiveCorpusRef c, const void* inPackedQueries, UInt32 inCount,
+                                                              UInt32 inSubfingerprintsPerQuery, UInt32 inRange, Float32 inThreshold,
+                                                              UInt64 inCapacity, UInt64 inIndexBase, void* outKeys, void* outCounts,
+                                                              void* outLags, void* inStream) {
+    LBAD_GUARD_BEGIN
+    return lbad::packed_threshold_impl(c, static_cast<const uint32_t*>(inPackedQueries), inCount, inSubfingerprintsPerQuery, inRange,
+                                       inThreshold, inCapacity, inIndexBase, static_cast<unsigned long long*>(outKeys),
+                                       static_cast<unsigned long long*>(outCounts), static_cast<int32_t*>(outLags),
+                                       static_cast<hipStream_t>(inStream));
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveThresholdKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, Float32 inThreshold,
+                                                       UInt64 inCapacity, UInt64 inIndexBase, void* outKeys, void* outCounts,
+                                                       void* inStream) {
+    LBAD_GUARD_BEGIN
+    if (!inScores || !outKeys || !outCounts || !lbad::threshold_args_ok(inRows, inThreshold, inCapacity))
+        return kLBAudioDetectiveArgumentInvalid;
+    if (inCount > 0x100000000ull || inIndexBase + inCount > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
+    if (!lbad::device_ready()) return kLBAudioDetectiveDeviceUnavailable;
+    hipStream_t stream = static_cast<hipStream_t>(inStream);
+    unsigned long long* keys = static_cast<unsigned long long*>(outKeys);
+    unsigned long long* counts = static_cast<unsigned long long*>(outCounts);
+    const uint32_t rows = inRows < lbad::kThresholdRowsMax ? inRows : lbad::kThresholdRowsMax;
+    lbad::DeviceBuffer<void> scratch;                      // (its own, not counted among a corpus' bytes for long: freed on return)
+    OSStatus st = scratch.reserve(lbad::threshold_scratch_bytes(inCount, rows));
+    if (st != noErr) return st;
+    for (uint32_t r0 = 0; r0 < inRows && st == noErr; r0 += rows) {
+        const uint32_t g = inRows - r0 < rows ? inRows - r0 : rows;
+        st = lbad::hip_status(lbad::launch_threshold_keys(inScores + (size_t)r0 * inCount, inCount, g, inThreshold, inCapacity, inIndexBase,
+                                                          scratch, keys + (size_t)r0 * inCapacity, counts + r0, stream),
+                              "threshold selection", __LINE__);
+    }
+    const OSStatus done = lbad::hip_status(hipStreamSynchronize(stream), "threshold selection", __LINE__);
+    return st != noErr ? st : done;
+    LBAD_GUARD_END
+}
 
 OSStatus LBAudioDetectiveCorpusQueryBatchTopKKeysDevice(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
                                                         UInt32 inCount, UInt32 inRange, UInt32 inK, UInt64 inIndexBase,

@@ -267,6 +267,17 @@ size_t topk_scratch_bytes(uint32_t rows);
 hipError_t launch_topk_keys(const float* d_scores, uint64_t n, uint32_t rows, uint32_t k, uint64_t index_base, void* d_scratch,
                             unsigned long long* d_keys, hipStream_t stream);
 
+// threshold selection (k_threshold.hip): per row of n scores (row r at d_scores + r * n, 4-byte aligned) the keys of the entries
+// whose score is >= threshold (a float compare; threshold > 0), in ascending entry index, the first min(count, capacity) of them
+// to d_keys + r * capacity, zero keys behind them, and the true count to d_counts[r].  d_scratch: threshold_scratch_bytes(n,
+// rows) bytes, written before they are read; a memset and three launches on `stream`, no host round trip.  rows <=
+// kThresholdRowsMax, index_base + n <= 2^32.
+constexpr uint32_t kThresholdRowsMax = kQueryBatchMax;
+size_t threshold_scratch_bytes(uint64_t n, uint32_t rows);
+hipError_t launch_threshold_keys(const float* d_scores, uint64_t n, uint32_t rows, float threshold, uint64_t capacity,
+                                 uint64_t index_base, void* d_scratch, unsigned long long* d_keys, unsigned long long* d_counts,
+                                 hipStream_t stream);
+
 // alignment (k_align.hip): the best sliding offset of (query, entry) pairs, after selection.  A corpus as its kernels read it:
 struct AlignSource {
     bool ragged = false;
@@ -432,6 +443,9 @@ OSStatus fingerprint_clips_device(struct ::LBAudioDetective* d, const void* d_pc
 OSStatus align_keys_built(struct ::LBAudioDetectiveCorpus* c, const uint2* d_desc, const uint32_t* d_words, uint32_t n, uint32_t per,
                           uint32_t range, uint32_t k, const unsigned long long* keys, uint64_t index_base, int32_t* lags,
                           hipStream_t stream);
+// ... and for n queries given as handles, staged by the alignment itself
+OSStatus align_keys_handles(struct ::LBAudioDetectiveCorpus* c, const ::LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
+                            uint32_t k, const unsigned long long* keys, uint64_t index_base, int32_t* lags, hipStream_t stream);
 ::LBAudioDetectiveFingerprintRef fingerprint_from_bools(const struct ::LBAudioDetective* d, const Boolean* bools, uint64_t per);
 // the file entry points (api_files.cpp): decode, conversion and the window loop of n files in one launch chain per
 // hop value; statuses (optional) receives every file's status
@@ -574,6 +588,10 @@ struct LBAudioDetectiveCorpus {
     lbad::DeviceBuffer<unsigned long long> d_topk_scan_keys;   // kQueryBatchMax words
     lbad::DeviceBuffer<unsigned long long> d_topk_keys;
     lbad::Event topk_ev;
+    // threshold queries (api_corpus.cpp): the tile counts and offsets of the selection of k_threshold.hip.  The score rows, the
+    // scans' key words, the staged query blocks, the host forms' key buffer and the event are the top-K calls': one convention
+    // for one scratch.
+    lbad::DeviceBuffer<void> d_threshold_scratch;
     // alignment (api_align.cpp): the staged query words and their table (device + pinned), the per-pair maxima of a split
     // launch, and the results of the host-returning forms (keys, lags or a profile) on their way back.  Grown on demand; a
     // call reuses them only after align_ev, recorded behind the previous call's last kernel.

@@ -102,6 +102,41 @@ def gather_topk_aligned(local_pairs, k: int, group=None):
     return merge_topk_aligned(out.view(world, q, kk, two), k)
 
 
+def merge_threshold_keys(gathered_keys, gathered_counts, capacity: int):
+    """[R, Q, C] int64 threshold keys of R shards (rows in ascending index, 0-padded) and their [R, Q] counts -> ([Q, capacity]
+    keys, [Q] totals).  Row q is rank 0's first min(count, C) keys, then rank 1's, and so on, cut at `capacity` and 0-padded: the
+    shards hold contiguous index ranges in rank order, so the concatenation IS the global list in ascending index.  The total
+    is the sum over the ranks -- the true number of matches, also where a rank's list or the merged one was cut (with
+    capacity <= C a rank whose list was cut fills the merged row by itself, so the row is always the global list's head)."""
+    import torch
+    r, q, c = gathered_keys.shape
+    counts = gathered_counts.to(torch.int64)
+    held = counts.clamp(max=c)                                           # keys a rank's row really holds
+    start = torch.cumsum(held, dim=0) - held                             # [R, Q]: where a rank's keys begin in the merged row
+    slot = start.unsqueeze(2) + torch.arange(c, device=gathered_keys.device).view(1, 1, c)
+    live = (torch.arange(c, device=gathered_keys.device).view(1, 1, c) < held.unsqueeze(2)) & (slot < capacity)
+    out = torch.zeros((q, capacity), dtype=gathered_keys.dtype, device=gathered_keys.device)
+    rows = torch.arange(q, device=gathered_keys.device).view(1, q, 1).expand(r, q, c)
+    out[rows[live], slot[live]] = gathered_keys[live]
+    return out, counts.sum(dim=0)
+
+
+def gather_threshold_keys(local_keys, local_counts, capacity: int, group=None):
+    """Collective: this rank's [Q, C] threshold keys and [Q] counts -> merge_threshold_keys of every rank's (one
+    all_gather_into_tensor of the keys, one of the counts)."""
+    import torch
+    import torch.distributed as dist
+    if not _collective(group):
+        return merge_threshold_keys(local_keys.unsqueeze(0), local_counts.unsqueeze(0), capacity)
+    world = dist.get_world_size(group)
+    q, c = local_keys.shape
+    keys = torch.empty((world * q, c), dtype=local_keys.dtype, device=local_keys.device)
+    counts = torch.empty(world * q, dtype=torch.int64, device=local_keys.device)
+    dist.all_gather_into_tensor(keys, local_keys.contiguous(), group=group)
+    dist.all_gather_into_tensor(counts, local_counts.to(torch.int64).contiguous(), group=group)
+    return merge_threshold_keys(keys.view(world, q, c), counts.view(world, q), capacity)
+
+
 def gather_packed(local_packed, group=None):
     """Optional last step of sharded fingerprinting: every rank contributes its [n_local, count, 32]
     packed sub-fingerprints (160 B per one-second clip) and receives all of them in rank order.  Ranks
@@ -232,6 +267,15 @@ class ShardedCorpus:
             idx, sc = decode_topk_keys(row)
             out.append((idx, sc, lrow[: len(idx)].numpy().astype(np.int32)))
         return out
+
+    def query_threshold(self, fps, threshold: float, capacity: int, range_: int = 0):
+        """Collective: every entry of every shard whose score is >= threshold -> list of (global indices, scores, total) per
+        query, indices ascending, cut at `capacity`; total is the true number of matches over all shards.  This rank's keys
+        and counts (index_base = its first global index), one all-gather of each through torch.distributed, the concatenation."""
+        from .api import decode_threshold_keys
+        keys, counts = self.local.query_batch_threshold_keys_device(fps, threshold, capacity, range_=range_, index_base=self.begin)
+        merged, totals = gather_threshold_keys(keys, counts, capacity, self.group)
+        return [decode_threshold_keys(row, t) + (int(t),) for row, t in zip(merged.cpu(), totals.cpu())]
 
     def query(self, fp, range_: int = 0, key_out=None):
         """Collective: every rank calls it with the same query; returns (global index, score)."""

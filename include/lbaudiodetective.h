@@ -566,6 +566,42 @@ OSStatus LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice(LBAudioDetectiveCo
 OSStatus LBAudioDetectiveThresholdKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, Float32 inThreshold,
                                                        UInt64 inCapacity, UInt64 inIndexBase, void* outKeys, void* outCounts,
                                                        void* inStream);
+/* Corpus join: every pair (entry of inQueries used as a query, entry of inCorpus) whose score reaches inThreshold, found on the
+ * device -- "which entries of this corpus match each other" (inQueries == inCorpus is allowed) and "which of these new entries
+ * are in the main corpus already".  A row is one of the entries inFirstQuery .. inFirstQuery + inQueryCount - 1 of inQueries.
+ * Row i against entry j scores exactly what LBAudioDetectiveCorpusScoresDevice writes for entry j with row i's fingerprint as
+ * the query; the query supplies the non-zero pairs, so score(i -> j) != score(j -> i) in general and the join reports ORDERED
+ * pairs.  A pair matches when score >= inThreshold as Float32 values.  The result is CSR over the rows: outOffsets receives
+ * inQueryCount + 1 UInt64, offsets[r] = matches of the rows before r, offsets[inQueryCount] = the TRUE total, never cut;
+ * outKeys receives inCapacity keys (score bits << 32 | 0xFFFFFFFF - (inIndexBase + j)): the match at position p (rows ascending,
+ * entry index ascending inside a row) in slot p where p < inCapacity, zero keys behind min(total, inCapacity).  A total above
+ * inCapacity tells that the list was cut, which is no error; the row of slot p is the last r with offsets[r] <= p.  The result
+ * does not depend on launch order, grid or chunking.  inSkipSameIndex != 0 leaves out the pair whose row index (in inQueries)
+ * equals the entry's index (in inCorpus): the self-match of a self-join.  Both corpora are uniform and of ONE shape, sub-
+ * fingerprints of 200 Booleans and 1 .. 8 of them per entry; a ragged corpus, another shape or two different shapes are
+ * kLBAudioDetectiveArgumentInvalid.  inThreshold is finite and > 0 (above 1 is legal and matches nothing), inQueryCount >= 1,
+ * inFirstQuery + inQueryCount <= entries of inQueries, 1 <= inCapacity <= 2^31, inIndexBase + entries of inCorpus <= 2^32,
+ * inRange == 0 means the sub-fingerprint length; NULL handles and pointers are kLBAudioDetectiveArgumentInvalid, and without a
+ * device arguments that pass these checks get kLBAudioDetectiveDeviceUnavailable.  An empty inCorpus gives zero offsets and
+ * keys.  Bound pruning and LBAudioDetectiveCorpusSetKernelVariant do not apply.
+ * The KeysDevice form writes to device pointers, asynchronously on inStream, which it never awaits; the rows go through in
+ * chunks with nothing visiting the host in between, and the call waits ON THE DEVICE for the latest append of either corpus.
+ * LBAudioDetectiveCorpusJoinThreshold returns the first min(total, inCapacity) pairs to host arrays of inCapacity elements --
+ * (row index in inQueries, entry index, score) -- then -1 / -1 / 0, and the total.
+ * The scratch belongs to inCorpus: 16 + rows x (584 + 8 x tiles) + ceil(rows / 64) x 4 x tiles bytes for a chunk of `rows` rows
+ * (a multiple of 64, or all the call's rows), tiles = ceil(entries of inCorpus / 256).  It grows on demand up to the limit set
+ * with LBAudioDetectiveCorpusSetJoinScratchLimit (0 = the default, 256 MiB), which thereby sets the rows per chunk; a limit
+ * below one chunk of 64 rows is kLBAudioDetectiveArgumentInvalid at the call.  A call waits for the previous join's device work
+ * before it reuses the scratch. */
+OSStatus LBAudioDetectiveCorpusJoinThresholdKeysDevice(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveCorpusRef inQueries,
+                                                       UInt64 inFirstQuery, UInt64 inQueryCount, UInt32 inRange, Float32 inThreshold,
+                                                       UInt32 inSkipSameIndex, UInt64 inCapacity, UInt64 inIndexBase, void* outKeys,
+                                                       void* outOffsets, void* inStream);
+OSStatus LBAudioDetectiveCorpusJoinThreshold(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveCorpusRef inQueries,
+                                             UInt64 inFirstQuery, UInt64 inQueryCount, UInt32 inRange, Float32 inThreshold,
+                                             UInt32 inSkipSameIndex, UInt64 inCapacity, SInt64* outQueryIndices,
+                                             SInt64* outEntryIndices, Float32* outScores, UInt64* outTotal);
+OSStatus LBAudioDetectiveCorpusSetJoinScratchLimit(LBAudioDetectiveCorpusRef inCorpus, UInt64 inBytes);   /* 0 = default */
 /* Where a match lies.  LBAudioDetectiveFingerprintCompareToFingerprint (Fp.m:119-149) slides the shorter fingerprint along
  * the longer one; the corpus passes the query as its first argument.  Entry longer than the query ("A"): the query slides
  * along the entry.  Otherwise ("B", equal lengths included): the entry slides along the query.  With n1 >= n2 the two counts,

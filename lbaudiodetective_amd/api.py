@@ -766,6 +766,60 @@ class Corpus:
                                                                            _stream_ptr(stream)), "CorpusQueryPackedThresholdKeysDevice")
         return (keys_out, counts_out, lags_out) if want_lags else (keys_out, counts_out)
 
+    # ---- corpus join: the entries of a corpus (this one, or `queries`) as queries against this corpus -- every ORDERED pair
+    # (row, entry) whose score is >= threshold, rows ascending, entries ascending inside a row, as CSR.  Uniform corpora of one
+    # shape (sub-fingerprints of 200 Booleans, 1 .. 8 per entry).
+    def _join_args(self, queries, first, count, skip_same_index):
+        q = self if queries is None else queries
+        if count is None:
+            count = len(q) - first
+        if skip_same_index is None:
+            skip_same_index = q is self
+        return q, int(first), int(count), int(bool(skip_same_index))
+
+    def join_threshold_keys_device(self, threshold: float, capacity: int, queries=None, first: int = 0, count=None,
+                                   skip_same_index=None, range_: int = 0, index_base: int = 0, keys_out=None, offsets_out=None,
+                                   stream=None):
+        """LBAudioDetectiveCorpusJoinThresholdKeysDevice: (keys int64 [capacity], offsets int64 [count + 1]) on the device,
+        asynchronously on `stream`.  The rows are entries first .. first + count - 1 of `queries` (None: this corpus, a
+        self-join); offsets[r] = matches of the rows before r, offsets[count] = the true total (above the capacity: the list
+        was cut); slot p holds the p-th match's key (global entry index = index_base + local), zero keys behind the matches.
+        skip_same_index (None: on for a self-join, off otherwise) leaves out the pair whose row index equals the entry's index.
+        Decode with decode_join_keys."""
+        q, first, count, skip = self._join_args(queries, first, count, skip_same_index)
+        if keys_out is None or offsets_out is None:
+            import torch
+            if keys_out is None:
+                keys_out = torch.empty(max(1, capacity), dtype=torch.int64, device="cuda")
+            if offsets_out is None:
+                offsets_out = torch.empty(max(1, count) + 1, dtype=torch.int64, device="cuda")
+        _out_ok(keys_out, capacity, "keys_out")
+        _out_ok(offsets_out, count + 1, "offsets_out")
+        _check(self._L.LBAudioDetectiveCorpusJoinThresholdKeysDevice(self._ref, q._ref, first, count, range_, threshold, skip, capacity,
+                                                                    index_base, _dev_ptr(keys_out), _dev_ptr(offsets_out),
+                                                                    _stream_ptr(stream)), "CorpusJoinThresholdKeysDevice")
+        return keys_out, offsets_out
+
+    def join_threshold(self, threshold: float, capacity: int, queries=None, first: int = 0, count=None, skip_same_index=None,
+                       range_: int = 0):
+        """LBAudioDetectiveCorpusJoinThreshold: (rows int64[m], indices int64[m], scores float32[m], total) with m = min(total,
+        capacity): the pairs (row index in `queries`, entry index, score) in the device form's order."""
+        q, first, count, skip = self._join_args(queries, first, count, skip_same_index)
+        rows = np.full(max(1, capacity), -1, dtype=np.int64)
+        idx = np.full(max(1, capacity), -1, dtype=np.int64)
+        sc = np.zeros(max(1, capacity), dtype=np.float32)
+        total = N.UInt64(0)
+        _check(self._L.LBAudioDetectiveCorpusJoinThreshold(self._ref, q._ref, first, count, range_, threshold, skip, capacity,
+                                                          rows.ctypes.data_as(C.POINTER(N.SInt64)),
+                                                          idx.ctypes.data_as(C.POINTER(N.SInt64)),
+                                                          sc.ctypes.data_as(C.POINTER(N.Float32)), C.byref(total)), "CorpusJoinThreshold")
+        m = min(int(total.value), capacity)
+        return rows[:m].copy(), idx[:m].copy(), sc[:m].copy(), int(total.value)
+
+    def set_join_scratch_limit(self, n_bytes: int):
+        """bytes of device memory the join's scratch may take, and thereby the rows per chunk; 0 restores the default"""
+        _check(self._L.LBAudioDetectiveCorpusSetJoinScratchLimit(self._ref, n_bytes), "CorpusSetJoinScratchLimit")
+
     # ---- where a match lies (LBAudioDetectiveCorpusQueryAligned and kin): lag > 0, the query's sub-fingerprint 0 lines up
     # with the entry's sub-fingerprint lag (the entry is the longer one); lag < 0, the entry's sub-fingerprint 0 lines up with
     # the query's sub-fingerprint -lag; 0 for equal lengths and for empty slots.  Positions in seconds: lag x 128 x analysis
@@ -1042,6 +1096,18 @@ def decode_threshold_keys(row, count=None):
     k = np.asarray(row.cpu().numpy() if hasattr(row, "cpu") else row, dtype=np.int64).astype(np.uint64).reshape(-1)
     k = k[k != 0] if count is None else k[:min(int(count), len(k))]
     return (0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32)
+
+
+def decode_join_keys(keys, offsets, first: int = 0):
+    """(rows int64[m], indices int64[m], scores float32[m], total) of a join's keys and CSR offsets (any int64 sequences):
+    m = min(total, len(keys)), rows counted from `first` (the call's first row)."""
+    k = np.asarray(keys.cpu().numpy() if hasattr(keys, "cpu") else keys, dtype=np.int64).astype(np.uint64).reshape(-1)
+    off = np.asarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64).astype(np.uint64).reshape(-1)
+    total = int(off[-1])
+    k = k[:min(total, len(k))]
+    rows = np.searchsorted(off, np.arange(len(k), dtype=np.uint64), side="right").astype(np.int64) - 1 + int(first)
+    return (rows, (0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32),
+            total)
 
 
 def synth_corpus_device(seed: int, first: int, n_entries: int, n_sub: int, subfp_len: int, out=None, stream=None):

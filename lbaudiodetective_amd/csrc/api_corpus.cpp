@@ -420,8 +420,9 @@ OSStatus LBAudioDetectiveCorpusAppendRaggedPackedDevice(LBAudioDetectiveCorpusRe
 }
 
 // Everything that may still touch the corpus' memory is awaited first -- the plan, the scans, the top-K, alignment and packed
-// scratch, the polled query's stream -- and nothing else: NOT append_event or shard_stale_event (the latter may sit behind a
-// collective that never ends).  The members then release what they own.
+// scratch, the joins that scanned it or took their rows from it (join_ev, with the join scratch), the polled query's stream --
+// and nothing else: NOT append_event or shard_stale_event (the latter may sit behind a collective that never ends).  The
+// members then release what they own.
 void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
     if (!c) return;
     (void)c->plan_built.wait();
@@ -429,6 +430,7 @@ void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
     (void)c->topk_ev.wait();
     (void)c->align_ev.wait();
     (void)c->pq_ev.wait();
+    (void)c->join_ev.wait();
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     delete c;
 }
@@ -936,6 +938,109 @@ OSStatus threshold_host_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFi
     return noErr;
 }
 
+
+// ---- corpus join: the entries of `q` as queries against `c`, every pair at or above the threshold as CSR (k_join.hip) --------
+constexpr uint64_t kJoinScratchDefault = 256ull << 20;
+
+// what needs neither handle nor device
+bool join_args_ok(uint64_t first, uint64_t count, float threshold, uint64_t capacity, uint64_t index_base) {
+    return std::isfinite(threshold) && threshold > 0.0f && count != 0 && count <= 0xFFFFFFFFull && first <= 0xFFFFFFFFull &&
+           capacity != 0 && capacity <= 0x80000000ull && index_base <= 0x100000000ull;
+}
+
+// what the handles decide, before anything is reserved or launched: two uniform corpora of one shape, and that shape the
+// specialised scan's; the rows and the indices in range; rows per chunk under the scratch limit (at most `count`)
+OSStatus join_plan(const LBAudioDetectiveCorpus* c, const LBAudioDetectiveCorpus* q, uint64_t first, uint64_t count,
+                   uint64_t index_base, uint64_t* out_chunk) {
+    if (c->ragged || q->ragged || c->subfp_len != q->subfp_len || c->n_sub != q->n_sub ||
+        !planes_fast_supported(c->subfp_len, c->n_sub, c->n_sub))
+        return kLBAudioDetectiveArgumentInvalid;
+    if (first + count > q->count || index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
+    const uint64_t limit = c->join_scratch_limit ? c->join_scratch_limit : kJoinScratchDefault;
+    const uint64_t chunk = join_chunk_rows(c->count, limit);
+    if (chunk == 0) return kLBAudioDetectiveArgumentInvalid;          // the limit holds no row tile of this corpus
+    *out_chunk = chunk < count ? chunk : count;
+    return noErr;
+}
+
+OSStatus join_keys_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, uint64_t first, uint64_t count, uint32_t range,
+                        float threshold, uint32_t skip, uint64_t capacity, uint64_t index_base, unsigned long long* keys,
+                        unsigned long long* offsets, hipStream_t stream) {
+    if (!c || !q || !keys || !offsets || !join_args_ok(first, count, threshold, capacity, index_base)) return kLBAudioDetectiveArgumentInvalid;
+    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
+    uint64_t chunk = 0;
+    OSStatus st = join_plan(c, q, first, count, index_base, &chunk);
+    if (st != noErr) return st;
+    if (range == 0) range = c->subfp_len;
+    st = c->join_ev.wait_or_create();                                 // (the scratch is the previous call's until then)
+    if (st == noErr && q != c) st = q->join_ev.create();
+    if (st != noErr) return st;
+    // the rows' corpus keeps ONE event for every join that reads it: this stream goes behind the join recorded there last, so
+    // that the record below is behind all of them and a Dispose of `q` awaits them all
+    if (q != c) LBAD_HIP(hipStreamWaitEvent(stream, q->join_ev, 0));
+    // both corpora's latest appends, awaited on the device
+    if (c->append_event.ev) LBAD_HIP(hipStreamWaitEvent(stream, c->append_event, 0));
+    if (q != c && q->append_event.ev) LBAD_HIP(hipStreamWaitEvent(stream, q->append_event, 0));
+    LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)capacity * sizeof(unsigned long long), stream));
+    if (c->count == 0) {
+        LBAD_HIP(hipMemsetAsync(offsets, 0, (size_t)(count + 1) * sizeof(unsigned long long), stream));
+    } else {
+        st = c->d_join_scratch.reserve(join_scratch_bytes(c->count, chunk));
+        if (st != noErr) return st;
+        JoinCall call;
+        call.d_planes = c->d_planes; call.stride = c->capacity; call.n_entries = c->count;
+        call.d_qplanes = q->d_planes; call.qstride = q->capacity;
+        call.n_sub = c->n_sub; call.range = range; call.threshold = threshold; call.skip = skip != 0;
+        call.capacity = capacity; call.index_base = index_base; call.d_keys = keys; call.stream = stream;
+        hipError_t e = hipSuccess;
+        for (uint64_t r0 = 0; r0 < count && e == hipSuccess; r0 += chunk) {
+            const uint32_t rows = (uint32_t)(count - r0 < chunk ? count - r0 : chunk);
+            e = launch_join_chunk(call, c->d_join_scratch, (uint32_t)chunk, first + r0, rows, r0 == 0 ? 1u : 0u, offsets + r0);
+        }
+        st = hip_status(e, "join", __LINE__);
+    }
+    // behind whatever was launched, also after a failure: the scratch and both corpora's planes are in use until then
+    const OSStatus rec = c->join_ev.record(stream);
+    const OSStatus rec2 = q != c ? q->join_ev.record(stream) : noErr;
+    return st != noErr ? st : (rec != noErr ? rec : rec2);
+}
+
+// host-returning form: keys and offsets in ONE block of the corpus' key buffer on the null stream, one read-back, then decoded
+OSStatus join_host_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, uint64_t first, uint64_t count, uint32_t range,
+                        float threshold, uint32_t skip, uint64_t capacity, SInt64* out_rows, SInt64* out_idx, Float32* out_scores,
+                        UInt64* out_total) {
+    if (!c || !q || !out_rows || !out_idx || !out_scores || !out_total || !join_args_ok(first, count, threshold, capacity, 0))
+        return kLBAudioDetectiveArgumentInvalid;
+    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
+    uint64_t chunk = 0;
+    OSStatus st = join_plan(c, q, first, count, 0, &chunk);           // (a refused call reserves nothing)
+    if (st != noErr) return st;
+    st = c->topk_ev.wait();             // (the key buffer is the previous top-K or threshold call's until then)
+    const size_t words = (size_t)capacity + count + 1;
+    if (st == noErr) st = c->d_topk_keys.reserve(words);
+    if (st != noErr) return st;
+    unsigned long long* d_keys = c->d_topk_keys;
+    st = join_keys_impl(c, q, first, count, range, threshold, skip, capacity, 0, d_keys, d_keys + capacity, nullptr);
+    if (st != noErr) {
+        (void)hipStreamSynchronize(nullptr);       // whatever was launched has left the key buffer before its next user
+        return st;
+    }
+    std::vector<unsigned long long> host(words);
+    LBAD_HIP(hipMemcpy(host.data(), d_keys, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    const unsigned long long* off = host.data() + capacity;
+    uint64_t row = 0;
+    for (uint64_t at = 0; at < capacity; ++at) {
+        if (at >= off[count]) {
+            out_rows[at] = -1; out_idx[at] = -1; out_scores[at] = 0.0f;
+            continue;
+        }
+        while (off[row + 1] <= at) ++row;          // (at < the total: a row with this slot exists)
+        LBAudioDetectiveCorpusDecodeKey(host[at], out_idx + at, out_scores + at);
+        out_rows[at] = (SInt64)(first + row);
+    }
+    *out_total = off[count];
+    return noErr;
+}
 }  // namespace
 }  // namespace lbad
 
@@ -988,6 +1093,40 @@ OSStatus LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice(LBAudioDetectiveCo
                                        static_cast<unsigned long long*>(outCounts), static_cast<int32_t*>(outLags),
                                        static_cast<hipStream_t>(inStream));
     LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusJoinThresholdKeysDevice(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveCorpusRef inQueries,
+                                                       UInt64 inFirstQuery, UInt64 inQueryCount, UInt32 inRange, Float32 inThreshold,
+                                                       UInt32 inSkipSameIndex, UInt64 inCapacity, UInt64 inIndexBase, void* outKeys,
+                                                       void* outOffsets, void* inStream) {
+    LBAD_GUARD_BEGIN
+    return lbad::join_keys_impl(inCorpus, inQueries, inFirstQuery, inQueryCount, inRange, inThreshold, inSkipSameIndex, inCapacity,
+                                inIndexBase, static_cast<unsigned long long*>(outKeys), static_cast<unsigned long long*>(outOffsets),
+                                static_cast<hipStream_t>(inStream));
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusJoinThreshold(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveCorpusRef inQueries, UInt64 inFirstQuery,
+                                             UInt64 inQueryCount, UInt32 inRange, Float32 inThreshold, UInt32 inSkipSameIndex,
+                                             UInt64 inCapacity, SInt64* outQueryIndices, SInt64* outEntryIndices, Float32* outScores,
+                                             UInt64* outTotal) {
+    LBAD_GUARD_BEGIN
+    return lbad::join_host_impl(inCorpus, inQueries, inFirstQuery, inQueryCount, inRange, inThreshold, inSkipSameIndex, inCapacity,
+                                outQueryIndices, outEntryIndices, outScores, outTotal);
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusSetJoinScratchLimit(LBAudioDetectiveCorpusRef inCorpus, UInt64 inBytes) {
+    if (!inCorpus) return kLBAudioDetectiveArgumentInvalid;
+    inCorpus->join_scratch_limit = inBytes;
+    // a block above the new limit goes, once the call that uses it is done
+    const uint64_t limit = inBytes ? inBytes : lbad::kJoinScratchDefault;
+    if (inCorpus->d_join_scratch.capacity() > limit) {
+        OSStatus st = inCorpus->join_ev.wait();
+        if (st != noErr) return st;
+        inCorpus->d_join_scratch.reset();
+    }
+    return noErr;
 }
 
 OSStatus LBAudioDetectiveThresholdKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, Float32 inThreshold,

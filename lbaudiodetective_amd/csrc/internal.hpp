@@ -278,6 +278,33 @@ hipError_t launch_threshold_keys(const float* d_scores, uint64_t n, uint32_t row
                                  uint64_t index_base, void* d_scratch, unsigned long long* d_keys, unsigned long long* d_counts,
                                  hipStream_t stream);
 
+// corpus join (k_join.hip): every pair (row of `queries`, entry of the scanned corpus; two uniform corpora of ONE specialised
+// shape) whose score -- the row as the query of the specialised scan -- is >= threshold, as CSR: the keys in (row, entry)
+// order to d_keys where their position is below the capacity, the offsets of the rows to the caller's offsets.  The call's
+// constants:
+struct JoinCall {
+    const uint4* d_planes = nullptr;     // the scanned corpus: planes, plane stride (its capacity), entries
+    uint64_t stride = 0, n_entries = 0;
+    const uint4* d_qplanes = nullptr;    // the rows' corpus
+    uint64_t qstride = 0;
+    uint32_t n_sub = 0, range = 0;
+    float threshold = 0.0f;
+    bool skip = false;                   // leave out the pair whose row index equals the entry's index
+    uint64_t capacity = 0, index_base = 0;
+    unsigned long long* d_keys = nullptr;    // `capacity` slots, zeroed by the caller
+    hipStream_t stream = nullptr;
+};
+// scratch of a chunk of `rows` rows against n_entries entries, and the rows a chunk may have under a limit (a whole number of
+// row tiles; 0: the limit is too small for one tile)
+size_t join_scratch_bytes(uint64_t n_entries, uint64_t rows);
+uint64_t join_chunk_rows(uint64_t n_entries, uint64_t limit_bytes);
+// one chunk: `rows` rows from row `first_row` of the rows' corpus; out_offsets: the caller's offsets AT the chunk's first row
+// (rows + 1 words are written: the last is the running total).  d_scratch: join_scratch_bytes(n_entries, chunk_rows_max) bytes,
+// the SAME block and chunk_rows_max for every chunk of a call -- its first words carry the total from chunk to chunk;
+// first_chunk starts it at 0.  Five launches on the call's stream, nothing visits the host.
+hipError_t launch_join_chunk(const JoinCall& call, void* d_scratch, uint32_t chunk_rows_max, uint64_t first_row, uint32_t rows,
+                             uint32_t first_chunk, unsigned long long* out_offsets);
+
 // alignment (k_align.hip): the best sliding offset of (query, entry) pairs, after selection.  A corpus as its kernels read it:
 struct AlignSource {
     bool ragged = false;
@@ -603,4 +630,11 @@ struct LBAudioDetectiveCorpus {
     // alignment's table and words.  Grown on demand; a call reuses it only after pq_ev, recorded behind its last kernel.
     lbad::DeviceBuffer<uint32_t> d_pq;
     lbad::Event pq_ev;
+    // corpus join (LBAudioDetectiveCorpusJoinThreshold..., k_join.hip), held by the corpus that is scanned: the chunk's row
+    // blocks, counts, offsets and the total carried between chunks.  Grown on demand up to the limit (0 = the default); a call
+    // reuses it only after join_ev, recorded behind its last kernel.  A corpus that only supplies the rows records its own
+    // join_ev too, each join's stream first going behind the record before: Dispose awaits every join that reads the planes.
+    lbad::DeviceBuffer<void> d_join_scratch;
+    lbad::Event join_ev;
+    uint64_t join_scratch_limit = 0;
 };

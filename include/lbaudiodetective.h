@@ -309,8 +309,9 @@ OSStatus LBAudioDetectiveFingerprintClipsFormat(LBAudioDetectiveRef inDetective,
  * 3 = like 2 but the register-resident 2048-point kernel instead of the streaming one (measurement). */
 OSStatus LBAudioDetectiveSetKernelVariant(LBAudioDetectiveRef inDetective, UInt32 inVariant);
 /* Measurement knobs of the generic stage-1 kernel (the LDS-tile sizing sweep of tools/sweep_lds_tiles.py):
- * waves per workgroup (0 = automatic; a value the configuration cannot hold falls back to automatic) and
- * whether the shared per-lane twiddle cache is used (default 1).  Results never depend on them. */
+ * waves per workgroup (0 = automatic; a value the window size has no instance for, or that does not fit the LDS with the
+ * cache as asked, falls back to the smallest workgroup without the cache) and whether the shared per-lane twiddle cache is
+ * used (default 1).  Results never depend on them; LBAudioDetectiveDebugStage1Choice tells which instance a setting takes. */
 OSStatus LBAudioDetectiveSetKernelTuning(LBAudioDetectiveRef inDetective, UInt32 inWavesPerWorkgroup,
                                          UInt32 inTwiddleCache);
 /* HBM the frame-row buffer between the two kernels may take (default 512 MiB; 16 KiB per frame at 32
@@ -329,6 +330,32 @@ OSStatus LBAudioDetectiveFingerprintClipsDeviceTaps(LBAudioDetectiveRef inDetect
                                                     UInt64 inNumberOfClips, UInt64 inSamplesPerClip,
                                                     void* outPacked, Float32* outFramesRaw, Float32* outFramesHaar,
                                                     void* inStream);
+/* The same with integer PCM (inSampleFormat as in LBAudioDetectiveFingerprintClipsDeviceFormat): the frame rows every
+ * stage-1 kernel makes of int16 / int32 samples, for comparison with the reference's.  A raw tap keeps full rows between the
+ * stages (no compact frames). */
+OSStatus LBAudioDetectiveFingerprintClipsDeviceTapsFormat(LBAudioDetectiveRef inDetective, const void* inClips,
+                                                          UInt32 inSampleFormat, UInt64 inNumberOfClips,
+                                                          UInt64 inSamplesPerClip, void* outPacked, Float32* outFramesRaw,
+                                                          Float32* outFramesHaar, void* inStream);
+/* Debug / tests: which kernels ONE batch call (LBAudioDetectiveFingerprintClipsDevice and its kin) takes -- the call's own
+ * decision (api_detective.cpp: stage1_choose, and the instance functions of the kernel files that the launchers dispatch on)
+ * as words; touches no device.  The call is described by the settings, the kernel variant, the tuning
+ * (LBAudioDetectiveSetKernelTuning's two values), the sample format, the number of clips and samples per clip, the clip
+ * pointer's address modulo 8, whether the raw tap is wanted and whether a file tail is attached (the file entry points).
+ * Returns kLBAudioDetectiveArgumentInvalid for a NULL outWords, inCapacity < 12, a variant above 4, more than 16 waves or an
+ * address above 7; otherwise noErr and outWords:
+ *   0 the status the call would return on a working device (an OSStatus as UInt32)   1 whether kernels are launched (0: the
+ *   status is an error, or there is no clip or no whole frame -- every later word is 0)   2 the stage-1 family: 0
+ *   fft_bands_kernel (generic), 1 frame_rows_pruned_kernel, 2 rows_stream2_kernel, 3 rows_full_kernel, 4 rows_stream_kernel
+ *   3..6 the instance's template arguments: LOG2W, WPB, CACHED | FMT | FMT, QLO, QHI | LOG2L, FMT, S64, lean (SKIP != 0) | FMT
+ *   (the generic kernel reads the sample format at run time)   7 rows between the stages: 0 full, 1 compact   8 stage 2: 0
+ *   haar_select_kernel (generic), 1 k_haar_select32.hip, 2 its sparse form   9 the waves asked for were not taken   10 the
+ *   twiddle cache asked for was not taken (9 or 10 set: the tuning fell back)   11 frames per clip */
+OSStatus LBAudioDetectiveDebugStage1Choice(Float64 inSampleRate, UInt32 inWindowSize, UInt32 inAnalysisStride,
+                                           UInt32 inNumberOfPitchSteps, UInt32 inSubfingerprintLength, UInt32 inKernelVariant,
+                                           UInt32 inWavesPerWorkgroup, UInt32 inTwiddleCache, UInt32 inSampleFormat,
+                                           UInt64 inNumberOfClips, UInt64 inSamplesPerClip, UInt32 inClipAddressMod8,
+                                           UInt32 inRawTap, UInt32 inFileTail, UInt32* outWords, UInt32 inCapacity);
 
 /* Streaming (the essay's live-recording use): PCM arrives in chunks of any size; whenever the
  * buffered samples complete one or more frames they are fingerprinted and appended, and the partial

@@ -7,7 +7,7 @@ from ._native import build, lib, constant, LIB_PATH, PACKED_BYTES, PACKED_WORDS,
 from .api import (  # noqa: F401
     Comm, Corpus, Detective, Fingerprint, Frame, Stream, LBAudioDetectiveError, noErr, pack_subfingerprint,
     frames_to_subfingerprints_device, compact_layout, compact_bands, probe_shader_clock, read_audio_url, synth_clips_device, synth_corpus_device, synth_ragged_corpus_device, unpack_packed, unpack_subfingerprint,
-    decode_topk_keys, topk_keys_from_scores_device, identify_clips_device, debug_query_blocks, debug_sliding_choice, debug_live_bytes,
+    decode_topk_keys, topk_keys_from_scores_device, identify_clips_device, debug_query_blocks, debug_sliding_choice, debug_stage1_choice, debug_live_bytes,
     decode_threshold_keys, threshold_keys_from_scores_device, decode_join_keys,
 )
 from .sharded import (  # noqa: F401
@@ -19,7 +19,7 @@ __all__ = [
     "build", "lib", "constant", "Corpus", "Detective", "Fingerprint", "Frame", "Stream", "LBAudioDetectiveError",
     "Comm", "ShardedCorpus", "broadcast_fingerprint", "make_comm", "shard_range", "read_audio_url", "frames_to_subfingerprints_device", "compact_layout", "compact_bands", "pack_subfingerprint", "unpack_subfingerprint", "unpack_packed",
     "synth_clips_device", "synth_corpus_device", "synth_ragged_corpus_device",
-    "decode_topk_keys", "topk_keys_from_scores_device", "identify_clips_device", "debug_query_blocks", "debug_sliding_choice", "debug_live_bytes", "merge_topk_keys", "merge_topk_aligned", "gather_topk_aligned",
+    "decode_topk_keys", "topk_keys_from_scores_device", "identify_clips_device", "debug_query_blocks", "debug_sliding_choice", "debug_stage1_choice", "debug_live_bytes", "merge_topk_keys", "merge_topk_aligned", "gather_topk_aligned",
     "decode_threshold_keys", "threshold_keys_from_scores_device", "merge_threshold_keys", "gather_threshold_keys",
     "decode_join_keys",
 ]

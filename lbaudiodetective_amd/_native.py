@@ -130,6 +130,10 @@ _SIGNATURES = {
     "LBAudioDetectiveSetScratchLimit": (OSStatus, [Ref, UInt64]),
     "LBAudioDetectiveSetStageTiming": (OSStatus, [Ref, UInt32]),
     "LBAudioDetectiveGetStageTimes": (OSStatus, [Ref, _P(Float32), _P(Float32), _P(UInt32)]),
+    "LBAudioDetectiveFingerprintClipsDeviceTapsFormat": (OSStatus, [Ref, C.c_void_p, UInt32, UInt64, UInt64, C.c_void_p, C.c_void_p,
+                                                                    C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveDebugStage1Choice": (OSStatus, [Float64, UInt32, UInt32, UInt32, UInt32, UInt32, UInt32, UInt32, UInt32, UInt64,
+                                                     UInt64, UInt32, UInt32, UInt32, _P(UInt32), UInt32]),
     "LBAudioDetectiveFingerprintClipsDeviceTaps": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, C.c_void_p,
                                                               C.c_void_p, C.c_void_p]),
     "LBAudioDetectivePackSubfingerprint": (None, [C.c_void_p, UInt32, C.c_void_p]),

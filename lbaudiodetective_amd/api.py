@@ -7,6 +7,7 @@ marshals buffers (numpy on the host, ``torch`` tensors for device memory and str
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -389,27 +390,59 @@ class Detective:
         """Device batch on torch tensors: clips [n, samples] float32 (cuda) -> packed uint8 [n, count, 32].
 
         Asynchronous on the given (default: current) torch stream.  With taps=True also returns the
-        128 x bands frames before and after the Haar (unfused kernels only)."""
+        128 x bands frames before and after the Haar (full rows between the stages).  int16 / int32 PCM is taken as well."""
         import torch
         assert clips.is_cuda and clips.is_contiguous() and clips.dtype in (torch.float32, torch.int16, torch.int32)
-        assert not taps or clips.dtype == torch.float32
         n, spc = clips.shape
         per = self.subfingerprint_count(spc)
         if out is None:
             out = torch.empty((n, per, N.PACKED_BYTES), dtype=torch.uint8, device=clips.device)
         sp = _stream_ptr(stream)
+        fmt = {torch.float32: 0, torch.int16: 1, torch.int32: 2}[clips.dtype]
         if not taps:
-            fmt = {torch.float32: 0, torch.int16: 1, torch.int32: 2}[clips.dtype]
             _check(self._L.LBAudioDetectiveFingerprintClipsDeviceFormat(self._ref, clips.data_ptr(), fmt, n, spc,
                                                                        out.data_ptr(), sp), "FingerprintClipsDevice")
             return out
         bands = self.number_of_pitch_steps
         raw = torch.empty((n, per, N.ROWS_PER_FRAME, bands), dtype=torch.float32, device=clips.device)
         haar = torch.empty_like(raw)
-        _check(self._L.LBAudioDetectiveFingerprintClipsDeviceTaps(self._ref, clips.data_ptr(), n, spc, out.data_ptr(),
-                                                                 raw.data_ptr(), haar.data_ptr(), sp),
-               "FingerprintClipsDeviceTaps")
+        _check(self._L.LBAudioDetectiveFingerprintClipsDeviceTapsFormat(self._ref, clips.data_ptr(), fmt, n, spc, out.data_ptr(),
+                                                                       raw.data_ptr(), haar.data_ptr(), sp),
+               "FingerprintClipsDeviceTapsFormat")
         return out, raw, haar
+
+    def stage1_choice(self, fmt: int, n_clips: int, samples_per_clip: int, address: int = 0, taps: bool = False,
+                      tail: bool = False, variant: int = 0, waves: int = 0, cache: bool = True) -> "Stage1Choice":
+        """debug_stage1_choice for this detective's settings; variant and tuning are not readable from the handle and are
+        given as they were set."""
+        return debug_stage1_choice(self.processing_sample_rate, self.window_size, self.analysis_stride, self.number_of_pitch_steps,
+                                   self.subfingerprint_length, variant, waves, cache, fmt, n_clips, samples_per_clip, address % 8,
+                                   taps, tail)
+
+
+STAGE1_FAMILIES = ("generic", "pruned", "stream2", "full", "stream")
+STAGE2_FAMILIES = ("generic", "select32", "select32_sparse")
+Stage1Choice = collections.namedtuple("Stage1Choice", "status launches family args compact stage2 fell_back per words")
+
+
+def debug_stage1_choice(sample_rate: float, window: int, stride: int, bands: int, subfp_len: int, variant: int = 0, waves: int = 0,
+                        cache: bool = True, fmt: int = 0, n_clips: int = 1, samples_per_clip: int = 0, address_mod8: int = 0,
+                        taps: bool = False, tail: bool = False) -> "Stage1Choice":
+    """LBAudioDetectiveDebugStage1Choice (tests): the kernels one batch call takes, from the header's 12 words.  Needs no GPU.
+    family / stage2: names of STAGE1_FAMILIES / STAGE2_FAMILIES (None when nothing is launched); args: the instance's template
+    arguments -- generic (LOG2W, WPB, CACHED), pruned (FMT,), stream2 (FMT, QLO, QHI), full (LOG2L, FMT, S64, lean), stream (FMT,);
+    fell_back: the tuning asked for was not taken; status: what the call would return."""
+    out = (N.UInt32 * 12)()
+    _check(N.lib().LBAudioDetectiveDebugStage1Choice(float(sample_rate), window, stride, bands, subfp_len, variant, waves, int(cache),
+                                                     fmt, n_clips, samples_per_clip, address_mod8, int(taps), int(tail), out, 12),
+           "DebugStage1Choice")
+    w = [int(x) for x in out]
+    status = w[0] - (1 << 32) if w[0] >= (1 << 31) else w[0]
+    if not w[1]:
+        return Stage1Choice(status, False, None, (), False, None, False, 0, w)
+    family = STAGE1_FAMILIES[w[2]]
+    n_args = {"generic": 3, "pruned": 1, "stream2": 3, "full": 4, "stream": 1}[family]
+    return Stage1Choice(status, True, family, tuple(w[3:3 + n_args]), bool(w[7]), STAGE2_FAMILIES[w[8]], bool(w[9] or w[10]), w[11], w)
 
 
 def compact_layout(det: "Detective"):

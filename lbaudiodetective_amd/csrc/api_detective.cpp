@@ -22,9 +22,16 @@ static bool valid_window(uint32_t w) { return w >= kMinWindow && w <= kMaxWindow
 
 static void free_plan(Plan& p) { p = Plan(); }
 
-// stride-dependent part of a plan: which specialised stage-1 kernels apply, and their tables
-static OSStatus plan_kernels(Plan& p) {
+// stride-dependent part of a plan, host half: which specialised stage-1 kernels apply
+static void plan_kernels_host(Plan& p) {
     p.pruned_ok = rows_pruned_supported(p);
+    p.full_ok = rows_full_supported(p);
+    p.stream_ok = rows_stream_supported(p);
+    p.stream2_ok = rows_stream2_supported(p);
+}
+
+// ... and device half: their tables
+static OSStatus plan_kernels_device(Plan& p) {
     if (p.pruned_ok && !p.d_bin_const) {
         std::vector<float> bc;
         rows_pruned_constants(bc);
@@ -32,10 +39,29 @@ static OSStatus plan_kernels(Plan& p) {
         if (st != noErr) return st;
         LBAD_HIP(hipMemcpy(p.d_bin_const, bc.data(), bc.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    p.full_ok = rows_full_supported(p);
-    p.stream_ok = rows_stream_supported(p);
-    p.stream2_ok = rows_stream2_supported(p);
     return p.full_ok || p.stream_ok || p.stream2_ok ? p.d_claim.reserve(8) : noErr;
+}
+
+// The host half of a plan (a fresh Plan, or one whose device tables were released): the band table, the sparse form and
+// which kernels apply -- all stage1_choose reads.  ensure_plan adds the uploads; LBAudioDetectiveDebugStage1Choice stops here.
+OSStatus plan_host(Plan& p, double rate, uint32_t window, uint32_t stride, uint32_t bands, uint32_t subfp_len) {
+    if (!valid_window(window) || stride == 0 || bands == 0 || bands > kMaxBands || !(rate > 0.0) || subfp_len == 0 ||
+        subfp_len > LBAD_MAX_SUBFINGERPRINT_LENGTH || subfp_len > kRowsPerFrame * bands)
+        return kLBAudioDetectiveArgumentInvalid;
+    p.sample_rate = rate;
+    p.window = window;
+    p.stride = stride;
+    p.bands = bands;
+    p.subfp_len = subfp_len;
+    p.log2w = 0;
+    while ((1u << p.log2w) < p.window) ++p.log2w;
+    // Extract is asked for subfp_len wavelets but Add keeps subfp_len Booleans (:321-328,
+    // Fingerprint.m:91-94): only the first ceil(subfp_len / 2) ranks survive.
+    p.keep = (p.subfp_len + 1) / 2;
+    make_band_table(rate, p.window, p.bands, p.table);
+    plan_sparse(p);
+    plan_kernels_host(p);
+    return noErr;
 }
 
 // (re)build the device tables when the configuration changed since the last call
@@ -52,7 +78,8 @@ OSStatus ensure_plan(LBAudioDetective* d) {
         if (p.stride == d->stride) return noErr;
         p.stride = d->stride;          // the tables do not depend on the hop; the kernel choice does
         p.valid = false;
-        OSStatus st = plan_kernels(p);
+        plan_kernels_host(p);
+        OSStatus st = plan_kernels_device(p);
         if (st != noErr) return st;
         p.valid = true;
         return noErr;
@@ -61,25 +88,15 @@ OSStatus ensure_plan(LBAudioDetective* d) {
     free_plan(p);
     p.tune_waves = d->tune_waves;
     p.tune_cache = d->tune_cache;
-    p.sample_rate = rate;
-    p.window = d->window;
-    p.stride = d->stride;
-    p.bands = d->bands;
-    p.subfp_len = d->subfp_len;
-    p.log2w = 0;
-    while ((1u << p.log2w) < p.window) ++p.log2w;
-    // Extract is asked for subfp_len wavelets but Add keeps subfp_len Booleans (:321-328,
-    // Fingerprint.m:91-94): only the first ceil(subfp_len / 2) ranks survive.
-    p.keep = (p.subfp_len + 1) / 2;
-    make_band_table(rate, p.window, p.bands, p.table);
+    OSStatus st = plan_host(p, rate, d->window, d->stride, d->bands, d->subfp_len);
+    if (st != noErr) return st;
     std::vector<float> re, im;
     make_twiddles(p.window, re, im);
     const size_t half = p.window / 2;
-    OSStatus st = p.d_tw.reserve(2 * half);
+    st = p.d_tw.reserve(2 * half);
     if (st != noErr) return st;
     LBAD_HIP(hipMemcpy(p.d_tw, re.data(), half * sizeof(float), hipMemcpyHostToDevice));
     LBAD_HIP(hipMemcpy(p.d_tw + half, im.data(), half * sizeof(float), hipMemcpyHostToDevice));
-    plan_sparse(p);
     // [bands] lo, [bands] hi, [bands] divisor as float bits; then where the band's mean of row w goes inside a frame, as
     // multiplier and offset (w * mult + off): for rows of `bands` floats, and for the compact frame of plan.sparse
     // (off 0xFFFFFFFF: not stored); then the first word of the band's power terms in LDS (BandTable::term_at) and, one word,
@@ -109,7 +126,7 @@ OSStatus ensure_plan(LBAudioDetective* d) {
     st = p.d_bands.reserve(tbl.size());
     if (st != noErr) return st;
     LBAD_HIP(hipMemcpy(p.d_bands, tbl.data(), tbl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    st = plan_kernels(p);
+    st = plan_kernels_device(p);
     if (st != noErr) return st;
     p.valid = true;
     return noErr;
@@ -153,6 +170,78 @@ struct StreamOrder {
     }
 };
 
+// The ONE decision of a batch call: whether it launches at all, which stage-1 kernel and instance, which rows travel between
+// the stages and which stage 2.  fingerprint_clips_device launches what this returns; LBAudioDetectiveDebugStage1Choice
+// reports it (stage1_choice_words).
+Stage1Choice stage1_choose(const Plan& p, const Stage1Call& c) {
+    Stage1Choice ch;
+    auto fail = [&]() { ch.status = kLBAudioDetectiveArgumentInvalid; return ch; };
+    if (c.fmt > 2) return fail();
+    if (c.tail && (c.n_clips != 1 || c.fmt != 0)) return fail();
+    ch.per = subfingerprint_count(c.spc, p.window, p.stride);
+    if (ch.per == 0 || c.n_clips == 0) return ch;
+    if (ch.per > 0xFFFFFFFFull / kRowsPerFrame) return fail();
+    const uint32_t elem = c.fmt == 1 ? 2 : 4;
+    // variant 0: specialised kernels when the configuration has them; 1: generic kernels; 2: specialised or error
+    // the streaming kernels read the clips as aligned sample PAIRS: every clip must start on a pair boundary
+    const bool pairs_ok = c.ptr_mod8 % (2 * elem) == 0 && ((c.spc & 1) == 0 || c.n_clips == 1);
+    const bool stream_ok = p.stream_ok && pairs_ok;
+    const bool stream2_ok = p.stream2_ok && pairs_ok && c.variant != 3;
+    const bool full_ok = p.full_ok && rows_full_supported_fmt(p, c.fmt);
+    bool special = p.pruned_ok || full_ok || stream_ok || stream2_ok;
+    if (c.variant == 3) {                        // measurement: the non-streaming specialised kernel where both exist
+        if (!full_ok && !p.pruned_ok) return fail();
+    }
+    if (c.variant == 1) special = false;
+    if (c.variant >= 2 && !special) return fail();
+    ch.launches = true;
+    ch.stage2_select32 = c.variant != 1 && haar_select32_supported(p);   // (variants 2 and 3 use it as well)
+    // rows of 16 floats between the stages where more than half of the bands are structurally empty (plan.sparse): the
+    // pruned stage 1 with the sparse stage 2, no file tails (they rewrite whole rows), no tap of the raw frames; variant 4
+    // keeps full rows (measurement)
+    ch.compact = special && p.pruned_ok && ch.stage2_select32 && p.sparse.ok && !c.tail && !c.raw_tap && c.variant != 4;
+    if (special && p.pruned_ok) {
+        ch.family = Stage1Family::Pruned;
+    } else if (special && stream2_ok) {
+        ch.family = Stage1Family::Stream2;
+        ch.stream2 = rows_stream2_instance(p, c.fmt);
+    } else if (special && full_ok) {
+        ch.family = Stage1Family::Full;
+        ch.full = rows_full_instance(p, c.fmt);
+    } else if (special) {
+        ch.family = Stage1Family::Stream;
+    } else {
+        ch.family = Stage1Family::Generic;
+        ch.generic = fft_bands_instance(p);
+    }
+    return ch;
+}
+
+// LBAudioDetectiveDebugStage1Choice's words (include/lbaudiodetective.h has the legend)
+void stage1_choice_words(const Stage1Choice& ch, const Stage1Call& c, const Plan& p, uint32_t* w) {
+    for (uint32_t i = 0; i < kStage1ChoiceWords; ++i) w[i] = 0;
+    w[0] = (uint32_t)ch.status;
+    w[1] = ch.launches ? 1u : 0u;
+    if (!ch.launches) return;
+    w[2] = (uint32_t)ch.family;
+    switch (ch.family) {
+        case Stage1Family::Generic:
+            w[3] = ch.generic.log2w; w[4] = ch.generic.wpb; w[5] = ch.generic.cached ? 1u : 0u;
+            w[9] = p.tune_waves != 0 && p.tune_waves != ch.generic.wpb ? 1u : 0u;
+            w[10] = p.tune_cache && !ch.generic.cached ? 1u : 0u;
+            break;
+        case Stage1Family::Pruned: w[3] = c.fmt; break;
+        case Stage1Family::Stream2: w[3] = ch.stream2.fmt; w[4] = ch.stream2.qlo; w[5] = ch.stream2.qhi; break;
+        case Stage1Family::Full:
+            w[3] = ch.full.log2l; w[4] = ch.full.fmt; w[5] = ch.full.s64 ? 1u : 0u; w[6] = ch.full.lean ? 1u : 0u;
+            break;
+        case Stage1Family::Stream: w[3] = c.fmt; break;
+    }
+    w[7] = ch.compact ? 1u : 0u;
+    w[8] = ch.stage2_select32 ? (ch.compact ? 2u : 1u) : 0u;
+    w[11] = (uint32_t)ch.per;
+}
+
 // The batch hot path: every clip -> frames_per_clip packed sub-fingerprints.
 OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, uint32_t fmt, uint64_t n_clips,
                                   uint64_t spc, uint32_t* d_packed, float* d_raw, float* d_haar, hipStream_t stream,
@@ -165,34 +254,25 @@ OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, ui
     OSStatus st = ensure_plan(d);
     if (st != noErr) return st;
     const Plan& p = d->plan;
-    const uint64_t per = subfingerprint_count(spc, p.window, p.stride);
-    if (per == 0 || n_clips == 0) return noErr;
-    if (per > 0xFFFFFFFFull / kRowsPerFrame) return kLBAudioDetectiveArgumentInvalid;
-    // variant 0: specialised kernels when the configuration has them; 1: generic kernels; 2: specialised or error
-    // the streaming kernels read the clips as aligned sample PAIRS: every clip must start on a pair boundary
-    const bool pairs_ok = reinterpret_cast<uintptr_t>(d_pcm_raw) % (2 * elem) == 0 && ((spc & 1) == 0 || n_clips == 1);
-    const bool stream_ok = p.stream_ok && pairs_ok;
-    const bool stream2_ok = p.stream2_ok && pairs_ok && d->variant != 3;
-    const bool full_ok = p.full_ok && rows_full_supported_fmt(p, fmt);
-    bool special = p.pruned_ok || full_ok || stream_ok || stream2_ok;
-    if (d->variant == 3) {                       // measurement: the non-streaming specialised kernel where both exist
-        if (!full_ok && !p.pruned_ok) return kLBAudioDetectiveArgumentInvalid;
-    }
-    if (d->variant == 1) special = false;
-    if (d->variant >= 2 && !special) return kLBAudioDetectiveArgumentInvalid;
+    Stage1Call call;
+    call.variant = d->variant; call.fmt = fmt; call.n_clips = n_clips; call.spc = spc;
+    call.ptr_mod8 = (uint32_t)(reinterpret_cast<uintptr_t>(d_pcm_raw) % 8);
+    call.raw_tap = d_raw != nullptr; call.tail = tail != nullptr;
+    const Stage1Choice ch = stage1_choose(p, call);
+    if (ch.status != noErr || !ch.launches) return ch.status;
+    const uint64_t per = ch.per;
     StreamOrder order{d, stream};
     LBAD_HIP(order.begin());
-    const bool special2 = d->variant != 1 && haar_select32_supported(p);   // (variants 2 and 3 use it as well)
-    // rows of 16 floats between the stages where more than half of the bands are structurally empty (plan.sparse): the
-    // pruned stage 1 with the sparse stage 2, no file tails (they rewrite whole rows), no tap of the raw frames; variant 4
-    // keeps full rows (measurement)
-    const bool compact = special && p.pruned_ok && special2 && p.sparse.ok && !tail && !d_raw && d->variant != 4;
+    const bool compact = ch.compact;
     auto stage1 = [&](const void* pcm_in, uint64_t nc, float* frames_out) -> hipError_t {
-        if (special && p.pruned_ok)
-            return launch_rows_pruned(p, p.d_bin_const, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream, compact);
-        if (special && stream2_ok) return launch_rows_stream2(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
-        if (special && full_ok) return launch_rows_full(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
-        if (special) return launch_rows_stream(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
+        switch (ch.family) {
+            case Stage1Family::Pruned:
+                return launch_rows_pruned(p, p.d_bin_const, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream, compact);
+            case Stage1Family::Stream2: return launch_rows_stream2(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
+            case Stage1Family::Full: return launch_rows_full(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
+            case Stage1Family::Stream: return launch_rows_stream(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
+            case Stage1Family::Generic: break;
+        }
         return launch_fft_bands(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
     };
     auto stage2 = [&](float* frames_in, uint64_t nf, uint32_t* packed_out, float* haar_out) -> hipError_t {
@@ -200,8 +280,8 @@ OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, ui
             hipError_t e = hipMemsetAsync(haar_out, 0, nf * kRowsPerFrame * p.bands * sizeof(float), stream);
             if (e != hipSuccess) return e;
         }
-        return special2 ? launch_haar_select32(p, frames_in, nf, packed_out, haar_out, stream, compact)
-                        : launch_haar_select(p, frames_in, nf, packed_out, haar_out, stream);
+        return ch.stage2_select32 ? launch_haar_select32(p, frames_in, nf, packed_out, haar_out, stream, compact)
+                                  : launch_haar_select(p, frames_in, nf, packed_out, haar_out, stream);
     };
     const uint64_t frame_floats = (uint64_t)kRowsPerFrame * p.bands;
     if (d_raw) {  // the caller's tap buffer doubles as the inter-kernel scratch
@@ -520,13 +600,46 @@ UInt64 LBAudioDetectiveGetSubfingerprintCount(LBAudioDetectiveRef d, UInt64 inNu
     return lbad::subfingerprint_count(inNumberOfSamples, d->window, d->stride);
 }
 
+OSStatus LBAudioDetectiveFingerprintClipsDeviceTapsFormat(LBAudioDetectiveRef d, const void* inClips, UInt32 inSampleFormat,
+                                                          UInt64 inNumberOfClips, UInt64 inSamplesPerClip, void* outPacked,
+                                                          Float32* outFramesRaw, Float32* outFramesHaar, void* inStream) {
+    if (!d || (!inClips && inNumberOfClips) || (!outPacked && inNumberOfClips)) return kLBAudioDetectiveArgumentInvalid;
+    return lbad::fingerprint_clips_device(d, inClips, inSampleFormat, inNumberOfClips, inSamplesPerClip,
+                                          static_cast<uint32_t*>(outPacked), outFramesRaw, outFramesHaar,
+                                          static_cast<hipStream_t>(inStream));
+}
+
 OSStatus LBAudioDetectiveFingerprintClipsDeviceTaps(LBAudioDetectiveRef d, const Float32* inClips, UInt64 inNumberOfClips,
                                                     UInt64 inSamplesPerClip, void* outPacked, Float32* outFramesRaw,
                                                     Float32* outFramesHaar, void* inStream) {
-    if (!d || (!inClips && inNumberOfClips) || (!outPacked && inNumberOfClips)) return kLBAudioDetectiveArgumentInvalid;
-    return lbad::fingerprint_clips_device(d, inClips, 0, inNumberOfClips, inSamplesPerClip,
-                                          static_cast<uint32_t*>(outPacked), outFramesRaw, outFramesHaar,
-                                          static_cast<hipStream_t>(inStream));
+    return LBAudioDetectiveFingerprintClipsDeviceTapsFormat(d, inClips, 0, inNumberOfClips, inSamplesPerClip, outPacked, outFramesRaw,
+                                                            outFramesHaar, inStream);
+}
+
+// Debug / tests: the decision of one batch call (stage1_choose) as words, from the host half of the plan; no device is touched
+OSStatus LBAudioDetectiveDebugStage1Choice(Float64 inSampleRate, UInt32 inWindowSize, UInt32 inAnalysisStride, UInt32 inNumberOfPitchSteps,
+                                           UInt32 inSubfingerprintLength, UInt32 inKernelVariant, UInt32 inWavesPerWorkgroup,
+                                           UInt32 inTwiddleCache, UInt32 inSampleFormat, UInt64 inNumberOfClips, UInt64 inSamplesPerClip,
+                                           UInt32 inClipAddressMod8, UInt32 inRawTap, UInt32 inFileTail, UInt32* outWords,
+                                           UInt32 inCapacity) {
+    LBAD_GUARD_BEGIN
+    if (!outWords || inCapacity < lbad::kStage1ChoiceWords || inKernelVariant > 4 || inWavesPerWorkgroup > 16 || inClipAddressMod8 > 7)
+        return kLBAudioDetectiveArgumentInvalid;
+    lbad::Plan p;
+    p.tune_waves = inWavesPerWorkgroup;
+    p.tune_cache = inTwiddleCache != 0;
+    lbad::Stage1Call call;
+    call.variant = inKernelVariant; call.fmt = inSampleFormat; call.n_clips = inNumberOfClips; call.spc = inSamplesPerClip;
+    call.ptr_mod8 = inClipAddressMod8; call.raw_tap = inRawTap != 0; call.tail = inFileTail != 0;
+    lbad::Stage1Choice ch;
+    // the order of fingerprint_clips_device: the format and the tail's conditions, then the settings, then the rest
+    if (inSampleFormat > 2 || (call.tail && (inNumberOfClips != 1 || inSampleFormat != 0)))
+        ch.status = kLBAudioDetectiveArgumentInvalid;
+    else if ((ch.status = lbad::plan_host(p, inSampleRate, inWindowSize, inAnalysisStride, inNumberOfPitchSteps, inSubfingerprintLength)) == noErr)
+        ch = lbad::stage1_choose(p, call);
+    lbad::stage1_choice_words(ch, call, p, outWords);
+    return noErr;
+    LBAD_GUARD_END
 }
 
 OSStatus LBAudioDetectiveFramesToSubfingerprintsDevice(LBAudioDetectiveRef d, const Float32* inFrames, UInt64 inNumberOfFrames,

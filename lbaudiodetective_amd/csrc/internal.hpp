@@ -174,6 +174,52 @@ hipError_t launch_haar_select32(const Plan& plan, const float* d_frames, uint64_
                                 float* d_haar_out, hipStream_t stream, bool compact = false);
 void plan_sparse(Plan& plan);    // fills plan.sparse from plan.table
 
+// ---- stage 1: ONE decision per call (api_detective.cpp: stage1_choose), and per kernel file ONE function that names the
+// template instance -- each launcher dispatches on what its function returns and LBAudioDetectiveDebugStage1Choice reports the
+// same value, so the report cannot drift from the launch.  None of them touches a device.
+enum class Stage1Family : uint32_t { Generic = 0, Pruned = 1, Stream2 = 2, Full = 3, Stream = 4 };
+// fft_bands_kernel<log2w, wpb, cached> (k_fft_bands.hip)
+struct FftBandsInstance {
+    uint32_t log2w = 0, wpb = 0;
+    bool cached = false;
+};
+FftBandsInstance fft_bands_instance(const Plan& plan);
+// rows_full_kernel<log2l, fmt, s64, lean ? the default table's unread terms : 0> (k_rows_full.hip).  ok == false: integer
+// input at a stride other than 64 (rows_full_supported_fmt), the launch fails
+struct RowsFullInstance {
+    uint32_t log2l = 0, fmt = 0;
+    bool s64 = false, lean = false, ok = false;
+};
+RowsFullInstance rows_full_instance(const Plan& plan, uint32_t fmt);
+// rows_stream2_kernel<fmt, qlo, qhi> (k_rows_stream2.hip)
+struct RowsStream2Instance {
+    uint32_t fmt = 0, qlo = 0, qhi = 0;
+};
+RowsStream2Instance rows_stream2_instance(const Plan& plan, uint32_t fmt);
+// what the decision looks at beside the plan
+struct Stage1Call {
+    uint32_t variant = 0, fmt = 0;
+    uint64_t n_clips = 0, spc = 0;
+    uint32_t ptr_mod8 = 0;          // the clip pointer's address modulo 8
+    bool raw_tap = false, tail = false;
+};
+struct Stage1Choice {
+    OSStatus status = noErr;        // what the call returns as far as the choice decides it
+    bool launches = false;          // false: the status is an error, or there is no clip or no whole frame
+    uint64_t per = 0;               // frames per clip
+    Stage1Family family = Stage1Family::Generic;
+    FftBandsInstance generic;       // the family's instance (the others stay zero)
+    RowsFullInstance full;
+    RowsStream2Instance stream2;
+    bool compact = false;           // rows of plan.sparse's stored bands between the stages
+    bool stage2_select32 = false;   // k_haar_select32.hip (its sparse form when compact), else k_haar_select.hip
+};
+Stage1Choice stage1_choose(const Plan& plan, const Stage1Call& call);
+constexpr uint32_t kStage1ChoiceWords = 12;
+void stage1_choice_words(const Stage1Choice& ch, const Stage1Call& call, const Plan& plan, uint32_t* out12);   // LBAudioDetectiveDebugStage1Choice's words
+// the host half of a plan: everything stage1_choose reads (table, sparse form, which specialised kernels apply), no device
+OSStatus plan_host(Plan& p, double rate, uint32_t window, uint32_t stride, uint32_t bands, uint32_t subfp_len);
+
 // end-of-file chain of upstream's file loop, tail mode "stale" (k_file_tail.hip); d_tbl: per window
 // [n_read, lo[bands], hi[bands]]
 hipError_t launch_empty_rows(const Plan& p, float* d_rows, uint64_t n_rows, hipStream_t stream);

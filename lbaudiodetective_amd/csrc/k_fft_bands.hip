@@ -430,15 +430,19 @@ bool fits(const Plan& plan, bool cached) {
     return cache_bytes + ((size_t)2 * nread + (size_t)WPB * (point_floats<LOG2W>() + nread)) * sizeof(float) <= 160 * 1024;
 }
 
+// THE choice of the instance for one window size: the first workgroup size of the list that is wanted (0: any) and fits;
+// when none does -- the cache does not fit beside even the smallest workgroup, or the wanted size is not listed -- the
+// smallest workgroup with global twiddle loads
 template <int LOG2W>
-hipError_t launch_one(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips, uint64_t samples_per_clip,
-                      uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {
+FftBandsInstance choose_one(const Plan& plan) {
     const int want = (int)plan.tune_waves;
     const bool cached = plan.tune_cache;
-#define LBAD_TRY(w)                                                                                              \
-    if ((want == 0 || want == w) && fits<LOG2W, w>(plan, cached)) {                                             \
-        if (cached) return launch_variant<LOG2W, w, true>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream); \
-        return launch_variant<LOG2W, w, false>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream); \
+    FftBandsInstance r;
+    r.log2w = LOG2W;
+#define LBAD_TRY(w)                                                      \
+    if ((want == 0 || want == w) && fits<LOG2W, w>(plan, cached)) {     \
+        r.wpb = w; r.cached = cached;                                    \
+        return r;                                                        \
     }
     if constexpr (LOG2W == 11) {
         LBAD_TRY(12) LBAD_TRY(8) LBAD_TRY(4) LBAD_TRY(2) LBAD_TRY(1)
@@ -450,13 +454,50 @@ hipError_t launch_one(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_
         LBAD_TRY(4)
     }
 #undef LBAD_TRY
-    // the cache does not fit beside even the smallest workgroup: global twiddle loads
-    if constexpr (LOG2W >= 12)
-        return launch_variant<LOG2W, 1, false>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-    return launch_variant<LOG2W, 4, false>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
+    r.wpb = LOG2W >= 12 ? 1 : 4;
+    r.cached = false;
+    return r;
+}
+
+template <int LOG2W>
+hipError_t launch_one(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips, uint64_t samples_per_clip,
+                      uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {
+    const FftBandsInstance c = choose_one<LOG2W>(plan);
+#define LBAD_GO(w)                                                                                               \
+    if (c.wpb == w) {                                                                                            \
+        if (c.cached) return launch_variant<LOG2W, w, true>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream); \
+        return launch_variant<LOG2W, w, false>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream); \
+    }
+    if constexpr (LOG2W == 11) {
+        LBAD_GO(12) LBAD_GO(8) LBAD_GO(4) LBAD_GO(2) LBAD_GO(1)
+    } else if constexpr (LOG2W == 12) {
+        LBAD_GO(7) LBAD_GO(6) LBAD_GO(4) LBAD_GO(2) LBAD_GO(1)
+    } else if constexpr (LOG2W == 13) {
+        LBAD_GO(2) LBAD_GO(1)
+    } else {
+        LBAD_GO(4)
+    }
+#undef LBAD_GO
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
+
+FftBandsInstance fft_bands_instance(const Plan& plan) {
+    switch (plan.log2w) {
+        case 4: return choose_one<4>(plan);
+        case 5: return choose_one<5>(plan);
+        case 6: return choose_one<6>(plan);
+        case 7: return choose_one<7>(plan);
+        case 8: return choose_one<8>(plan);
+        case 9: return choose_one<9>(plan);
+        case 10: return choose_one<10>(plan);
+        case 11: return choose_one<11>(plan);
+        case 12: return choose_one<12>(plan);
+        case 13: return choose_one<13>(plan);
+        default: return FftBandsInstance();
+    }
+}
 
 hipError_t launch_fft_bands(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips,
                             uint64_t samples_per_clip, uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {

@@ -539,16 +539,15 @@ hipError_t launch_full_fmt(const Plan& plan, const void* d_pcm, uint64_t n_frame
 template <int LOG2L>
 hipError_t launch_full(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_frames, uint64_t samples_per_clip,
                        uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {
-    // 2048-sample windows, float32: the instance without the terms the default table never reads, when this table does not either
-    const bool lean = LOG2L == 4 && fmt == 0 && (plan.table.unread_terms16 & kDefaultUnread16) == kDefaultUnread16;
+    const RowsFullInstance c = rows_full_instance(plan, fmt);
     constexpr uint64_t kLean = LOG2L == 4 ? kDefaultUnread16 : 0ull;
-    if (plan.stride != (uint32_t)kStride) {                // any other stride: float32 input only (rows_full_supported_fmt)
-        if (fmt != 0) return hipErrorInvalidValue;
-        if (lean) return launch_full_fmt<LOG2L, 0, false, kLean>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
+    if (!c.ok || c.log2l != (uint32_t)LOG2L) return hipErrorInvalidValue;
+    if (!c.s64) {
+        if (c.lean) return launch_full_fmt<LOG2L, 0, false, kLean>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
         return launch_full_fmt<LOG2L, 0, false>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
     }
-    if (lean) return launch_full_fmt<LOG2L, 0, true, kLean>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
-    switch (fmt) {
+    if (c.lean) return launch_full_fmt<LOG2L, 0, true, kLean>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
+    switch (c.fmt) {
         case 0: return launch_full_fmt<LOG2L, 0, true>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
         case 1: return launch_full_fmt<LOG2L, 1, true>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
         case 2: return launch_full_fmt<LOG2L, 2, true>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
@@ -579,6 +578,19 @@ bool rows_full_supported(const Plan& p) {
 
 // strides other than 64 take float32 input (integer PCM at those strides runs on the generic kernel)
 bool rows_full_supported_fmt(const Plan& p, uint32_t fmt) { return p.stride == (uint32_t)kStride || fmt == 0; }
+
+// THE choice of the instance (a configuration rows_full_supported accepts): the window's LOG2L, the stride-64 span loader or
+// the general one (float32 input only), and for 2048-sample windows of float32 the instance without the terms the default
+// table never reads, when this table does not read them either
+RowsFullInstance rows_full_instance(const Plan& p, uint32_t fmt) {
+    RowsFullInstance r;
+    r.log2l = p.window == 256 ? 1 : p.window == 512 ? 2 : p.window == 1024 ? 3 : 4;
+    r.fmt = fmt;
+    r.s64 = p.stride == (uint32_t)kStride;
+    r.lean = r.log2l == 4 && fmt == 0 && (p.table.unread_terms16 & kDefaultUnread16) == kDefaultUnread16;
+    r.ok = fmt <= 2 && (r.s64 || fmt == 0);
+    return r;
+}
 
 hipError_t launch_rows_full(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips, uint64_t samples_per_clip,
                             uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {

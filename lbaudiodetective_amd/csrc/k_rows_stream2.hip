@@ -358,13 +358,25 @@ static hipError_t launch_stream2_q(const Plan& plan, const void* d_pcm, uint64_t
     return hipGetLastError();
 }
 
+// THE choice of the instance: the default table (5512 Hz: bins 86..758) needs q = 2..23; anything else takes the full range
+RowsStream2Instance rows_stream2_instance(const Plan& plan, uint32_t fmt) {
+    RowsStream2Instance r;
+    r.fmt = fmt;
+    const bool narrow = plan.table.kmin >= 64 && plan.table.kmax <= 768;
+    r.qlo = narrow ? 2 : 0;
+    r.qhi = narrow ? 24 : 32;
+    return r;
+}
+
 template <int FMT>
 static hipError_t launch_stream2_fmt(const Plan& plan, const void* d_pcm, uint64_t n_frames, uint64_t samples_per_clip,
                                      uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {
-    // the default table (5512 Hz: bins 86..758) needs q = 2..23; anything else takes the full range
-    if (plan.table.kmin >= 64 && plan.table.kmax <= 768)
+    const RowsStream2Instance c = rows_stream2_instance(plan, FMT);
+    if (c.qlo == 2 && c.qhi == 24)
         return launch_stream2_q<FMT, 2, 24>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
-    return launch_stream2_q<FMT, 0, 32>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
+    if (c.qlo == 0 && c.qhi == 32)
+        return launch_stream2_q<FMT, 0, 32>(plan, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_rows_stream2(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips, uint64_t samples_per_clip,

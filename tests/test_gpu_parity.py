@@ -9,6 +9,8 @@ import struct
 import numpy as np
 import pytest
 
+from test_gpu_band_means import _same_bits
+
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -832,7 +834,7 @@ def test_stream2_kernel_shapes(lb, gpu, oracle):
 def test_random_configurations_bit_exact(lb, gpu, oracle):
     rng = np.random.default_rng(20260101)
     for trial in range(40):
-        window = int(2 ** rng.integers(4, 13))                     # 16 .. 4096
+        window = int(2 ** rng.integers(4, 14))                     # 16 .. 8192
         stride = int(rng.choice([1, 3, 7, 16, 31, 64, 100, 257]))
         bands = int(rng.choice([1, 2, 5, 16, 31, 32, 33, 64]))
         subfp_len = int(min(rng.choice([1, 2, 9, 64, 199, 200, 201, 256]), 128 * bands))
@@ -849,6 +851,11 @@ def test_random_configurations_bit_exact(lb, gpu, oracle):
         assert want.shape[1] == frames
         got = _fingerprint_device(lb, gpu, pcm, cfg)
         assert np.array_equal(got, want), (trial, window, stride, bands, subfp_len, rate, n)
+        # the bits hardly move when a band mean is off by an ulp: the raw tap's floats as bit patterns as well
+        tapped, raw, _ = _fingerprint_device(lb, gpu, pcm, cfg, taps=True)
+        assert np.array_equal(tapped, want), (trial, window, stride, bands, subfp_len, rate, n)
+        for c in range(n_clips):
+            assert _same_bits(raw[c], oracle.fingerprint_pcm(pcm[c], cfg, taps=True)[1]), (trial, c, window, stride, bands, rate, n)
 
 
 def test_random_compare_shapes(lb, gpu, oracle):
@@ -1020,6 +1027,18 @@ def test_compact_frames_between_the_stages_change_nothing(lb, gpu, oracle):
         per = outs[0].shape[1]
         want = oracle.fingerprint_batch(clips.cpu().numpy(), oracle.Config(44100, 1024), nthreads=8)
         assert np.array_equal(lb.unpack_packed(outs[0].cpu().numpy(), 200).reshape(48, per, 200), want)
+        # int16 input (the last length is odd: the clips then start on 2-byte boundaries only) against the oracle on the
+        # float32 values the integers convert to
+        ints = (clips * 30000.0).round().clamp(-32768, 32767).to(gpu.int16)
+        outs16 = []
+        for variant in (0, 4, 1):
+            det = lb.Detective().configure(sample_rate=44100, window=1024)
+            det.set_kernel_variant(variant)
+            outs16.append(det.fingerprint_clips_device(ints).clone())
+        assert gpu.equal(outs16[0], outs16[1]) and gpu.equal(outs16[0], outs16[2])
+        as_float = (ints.cpu().numpy().astype(np.float64) / 32768.0).astype(np.float32)
+        want16 = oracle.fingerprint_batch(as_float, oracle.Config(44100, 1024), nthreads=8)
+        assert np.array_equal(lb.unpack_packed(outs16[0].cpu().numpy(), 200).reshape(48, per, 200), want16)
     # other sampling rates with 1024-sample windows: whatever the band table, the layout choice must not matter
     for rate in (44100, 32000, 22050, 48000, 16000, 8000):
         det = lb.Detective().configure(sample_rate=rate, window=1024)

@@ -53,7 +53,7 @@ for t in range(trials):
         n = 1024 + 64 * 128 * int(rng.integers(1, 4)) + int(rng.integers(0, 8192))
         clips = int(rng.integers(1, 9))
     else:
-        cfg = O.Config(float(rng.choice([5512, 8000, 16000, 22050, 44100, 48000])), int(2 ** rng.integers(4, 13)),
+        cfg = O.Config(float(rng.choice([5512, 8000, 16000, 22050, 44100, 48000])), int(2 ** rng.integers(4, 14)),
                        int(rng.integers(1, 300)), int(rng.integers(1, 65)), 1)
         cfg.subfp_len = int(rng.integers(1, min(256, 128 * cfg.bands) + 1))
         n = cfg.window + cfg.stride * 128 * int(rng.integers(1, 3)) + int(rng.integers(0, 128 * cfg.stride))
@@ -92,6 +92,17 @@ for t in range(trials):
     if not np.array_equal(got, want):
         bad += 1
         print("MISMATCH", t, kind, mode, cfg.sample_rate, cfg.window, cfg.stride, cfg.bands, cfg.subfp_len, n, clips, flush=True)
+    # the bits hardly move when a band mean is off by an ulp: the raw tap's floats (full rows) as bit patterns, first clips
+    tapped, raw, _ = det.fingerprint_clips_device(torch.from_numpy(pcm).cuda(), taps=True)
+    if not torch.equal(tapped, packed):
+        bad += 1
+        print("TAP BITS MISMATCH", t, kind, mode, cfg.sample_rate, cfg.window, cfg.stride, cfg.bands, cfg.subfp_len, n, clips, flush=True)
+    raw = raw[:4].cpu().numpy()
+    for c in range(raw.shape[0]):
+        oraw = O.fingerprint_pcm(pcm[c], cfg, taps=True)[1]
+        if not ((raw[c].view(np.uint32) == oraw.view(np.uint32)) | (np.isnan(raw[c]) & np.isnan(oraw))).all():
+            bad += 1
+            print("BAND MEAN MISMATCH", t, kind, mode, c, cfg.sample_rate, cfg.window, cfg.stride, cfg.bands, cfg.subfp_len, n, clips, flush=True)
     # compare leg on the fresh fingerprints
     if want.shape[1] >= 1 and clips >= 2:
         a, b = want[0], want[1]

@@ -629,6 +629,47 @@ OSStatus LBAudioDetectiveCorpusJoinThreshold(LBAudioDetectiveCorpusRef inCorpus,
                                              UInt32 inSkipSameIndex, UInt64 inCapacity, SInt64* outQueryIndices,
                                              SInt64* outEntryIndices, Float32* outScores, UInt64* outTotal);
 OSStatus LBAudioDetectiveCorpusSetJoinScratchLimit(LBAudioDetectiveCorpusRef inCorpus, UInt64 inBytes);   /* 0 = default */
+/* Removal: entries taken out of a corpus on the device, the other half of the corpus life cycle -- the take-down of one
+ * recording, or the action behind a join's duplicate pairs.  Both forms, both kinds of corpus (uniform of any shape, ragged):
+ * the named entries go, the others keep their relative order and close up -- the entry at old index i gets the new index
+ * i - (removed entries below i).  Afterwards the corpus cannot be told from one made fresh with the same capacities by
+ * appending the kept entries in order: every query form returns the same bits, LBAudioDetectiveCorpusSave writes the same
+ * bytes, GetCount and GetSubfingerprintTotal return the same values.  Capacity and the addresses of the corpus' blocks do not
+ * change; later appends reuse the room that was freed.  outRemoved receives the number of DISTINCT entries removed (0 from a
+ * call that is refused or fails, wherever outRemoved itself is not NULL);
+ * outNewIndices, when given, one UInt32 per OLD entry: its new index, or 0xFFFFFFFF for a removed entry.
+ * LBAudioDetectiveCorpusRemoveIndices takes indices on the host (outNewIndices: host).  Duplicates are allowed; any index >= the
+ * count is kLBAudioDetectiveArgumentInvalid and nothing changes.
+ * LBAudioDetectiveCorpusRemoveKeysDevice takes inCount 64-bit keys on the device exactly as the top-K, threshold and join calls
+ * write them -- the low word is 0xFFFFFFFF - (inIndexBase + index), the score word is ignored -- and outNewIndices is a device
+ * pointer.  Zero keys and keys whose index lies outside [inIndexBase, inIndexBase + count) are skipped (the alignment's
+ * convention), duplicates are allowed: a key list padded with zeros can be passed as it is.  Its kernels run on inStream, the
+ * stream that produced the keys (or one the caller has put behind their producer).
+ * A removal is a SYNCHRONOUS maintenance call: it first waits for everything the corpus has in flight (appends, queries of
+ * every form, alignments, joins), and both forms return when the device work is done and the count (and a ragged corpus'
+ * offsets and length histogram) are up to date; everything issued later finds the new corpus.  One read-back per call: the
+ * tile offsets, and the index map when the host form returns it or the corpus is ragged.  Like appends, a removal must not run
+ * concurrently with any other call on the same corpus.  The sharded key block is left alone; a sharded corpus has no removal
+ * (the index bases of all later shards would shift).
+ * inCount == 0, or a list that names nothing valid: noErr, 0 removed, the identity map, nothing is moved.  Removing every entry
+ * leaves a working empty corpus; removing only the last entries moves nothing (entries below the lowest removed index are
+ * neither read nor written).  A NULL handle, a NULL outRemoved, a NULL list with inCount != 0 and inIndexBase > 2^32 are
+ * kLBAudioDetectiveArgumentInvalid, decided before a handle is read; then a missing device is
+ * kLBAudioDetectiveDeviceUnavailable; then inIndexBase + count > 2^32 is kLBAudioDetectiveArgumentInvalid.
+ * The scratch belongs to the corpus and grows on demand: the index block, 4 x (8 + 2 x tiles + 2 x 1024 x tiles) + 4 bytes
+ * rounded up to 16 for tiles = ceil(count / 1024) tiles of 1024 entries (flags, map, tile counts and offsets); the host form's
+ * staged list, 8 x inCount bytes; a ragged corpus' second offsets array, 4 x (entry capacity + 1) bytes; and the bounce buffer
+ * the kept planes or records pass through in ascending chunks, min(limit, items above the lowest removed index rounded up to
+ * whole tiles) x LBAudioDetectiveCorpusGetEntryStrideBytes, a whole number of tiles of 1024 entries (uniform) or 1024 records
+ * (ragged).  LBAudioDetectiveCorpusSetRemoveScratchLimit bounds the bounce buffer (0 = the default, 256 MiB) and so sets the
+ * items per chunk; a limit below one tile is kLBAudioDetectiveArgumentInvalid at the removal call, and the result never depends
+ * on the limit. */
+OSStatus LBAudioDetectiveCorpusRemoveIndices(LBAudioDetectiveCorpusRef inCorpus, const UInt64* inIndices, UInt64 inCount,
+                                             UInt32* outNewIndices /* host, may be NULL */, UInt64* outRemoved);
+OSStatus LBAudioDetectiveCorpusRemoveKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inKeys /* device */, UInt64 inCount,
+                                                UInt64 inIndexBase, void* outNewIndices /* device, may be NULL */,
+                                                UInt64* outRemoved /* host */, void* inStream);
+OSStatus LBAudioDetectiveCorpusSetRemoveScratchLimit(LBAudioDetectiveCorpusRef inCorpus, UInt64 inBytes);   /* 0 = default */
 /* Where a match lies.  LBAudioDetectiveFingerprintCompareToFingerprint (Fp.m:119-149) slides the shorter fingerprint along
  * the longer one; the corpus passes the query as its first argument.  Entry longer than the query ("A"): the query slides
  * along the entry.  Otherwise ("B", equal lengths included): the entry slides along the query.  With n1 >= n2 the two counts,

@@ -853,6 +853,41 @@ class Corpus:
         """bytes of device memory the join's scratch may take, and thereby the rows per chunk; 0 restores the default"""
         _check(self._L.LBAudioDetectiveCorpusSetJoinScratchLimit(self._ref, n_bytes), "CorpusSetJoinScratchLimit")
 
+    # ---- removal: the named entries go, the others keep their order and close up (old index i -> i - removed below i); the
+    # corpus is afterwards what a fresh one would be after appending the kept entries.  Synchronous calls.
+    def remove(self, indices, return_map: bool = False):
+        """LBAudioDetectiveCorpusRemoveIndices: remove the entries at `indices` (host integers, duplicates allowed; an index >=
+        len(self) is refused and nothing changes).  Returns the number of distinct entries removed, or with return_map=True
+        (removed, uint32 array with one word per OLD entry: its new index, 0xFFFFFFFF for a removed entry)."""
+        idx = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.uint64)
+        new = np.full(max(1, len(self)), 0xFFFFFFFF, dtype=np.uint32) if return_map else None
+        n_old, removed = len(self), N.UInt64(0)
+        _check(self._L.LBAudioDetectiveCorpusRemoveIndices(self._ref, idx.ctypes.data_as(C.POINTER(N.UInt64)) if idx.size else None,
+                                                          idx.size, new.ctypes.data_as(C.POINTER(N.UInt32)) if return_map else None,
+                                                          C.byref(removed)), "CorpusRemoveIndices")
+        return (int(removed.value), new[:n_old].copy()) if return_map else int(removed.value)
+
+    def remove_keys_device(self, keys, index_base: int = 0, new_indices_out=None, stream=None) -> int:
+        """LBAudioDetectiveCorpusRemoveKeysDevice: remove the entries named by 64-bit keys on the device, exactly as the top-K,
+        threshold and join calls write them (global index = index_base + local; zero keys and keys of other entries are skipped,
+        duplicates allowed).  new_indices_out: an int32 / uint32 device tensor of len(self) words that receives the map.  The
+        kernels run on `stream` (the stream that produced the keys); the call returns when they are done."""
+        assert keys.is_cuda and keys.is_contiguous() and keys.element_size() == 8
+        n = keys.numel()
+        if new_indices_out is not None:
+            assert new_indices_out.element_size() == 4
+            _out_ok(new_indices_out, len(self), "new_indices_out")
+        removed = N.UInt64(0)
+        _check(self._L.LBAudioDetectiveCorpusRemoveKeysDevice(self._ref, _dev_ptr(keys) if n else None, n, index_base,
+                                                             _dev_ptr(new_indices_out) if new_indices_out is not None else None,
+                                                             C.byref(removed), _stream_ptr(stream)), "CorpusRemoveKeysDevice")
+        return int(removed.value)
+
+    def set_remove_scratch_limit(self, n_bytes: int):
+        """bytes of device memory a removal's bounce buffer may take, and thereby the entries (records) per chunk; 0 restores
+        the default"""
+        _check(self._L.LBAudioDetectiveCorpusSetRemoveScratchLimit(self._ref, n_bytes), "CorpusSetRemoveScratchLimit")
+
     # ---- where a match lies (LBAudioDetectiveCorpusQueryAligned and kin): lag > 0, the query's sub-fingerprint 0 lines up
     # with the entry's sub-fingerprint lag (the entry is the longer one); lag < 0, the entry's sub-fingerprint 0 lines up with
     # the query's sub-fingerprint -lag; 0 for equal lengths and for empty slots.  Positions in seconds: lag x 128 x analysis

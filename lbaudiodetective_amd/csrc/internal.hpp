@@ -351,6 +351,34 @@ uint64_t join_chunk_rows(uint64_t n_entries, uint64_t limit_bytes);
 hipError_t launch_join_chunk(const JoinCall& call, void* d_scratch, uint32_t chunk_rows_max, uint64_t first_row, uint32_t rows,
                              uint32_t first_chunk, unsigned long long* out_offsets);
 
+// removal (k_remove.hip): the index of a call -- which entries go and where the others land -- and the moves of a chunk.
+// The index block of a corpus of `count` entries (remove_index_layout places it in d_block, 16-byte aligned, `words` words):
+// head (entries kept, lowest removed index or 0xFFFFFFFF, two zero words), tiles + 1 tile offsets (kept entries below the
+// tile; the last word = the total), the map (new index per entry, 0xFFFFFFFF for a removed one), then the flags and the per-tile
+// words.  The host reads the first head_words words, or map_words of them when it wants the map as well: ONE copy.
+struct RemoveIndex {
+    uint64_t tiles = 0;
+    uint32_t *head = nullptr, *tile_offsets = nullptr, *map = nullptr, *flags = nullptr, *tile_counts = nullptr, *tile_first = nullptr;
+    uint64_t words = 0, head_words = 0, map_at = 0, map_words = 0;    // map_at: the map's first word inside the block
+};
+uint32_t remove_tile_entries();          // entries (records of a ragged corpus) per tile: what a chunk is a whole number of
+RemoveIndex remove_index_layout(void* d_block, uint64_t count);
+// a memset and four launches on `stream`: d_list holds n_list keys (keys: 0xFFFFFFFF - low word = index_base + entry; zero keys
+// and keys of other entries are skipped) or n_list 64-bit indices.  1 <= count <= 2^32 - 1.
+hipError_t launch_remove_index(const unsigned long long* d_list, uint64_t n_list, bool keys, uint64_t index_base, uint64_t count,
+                               const RemoveIndex& ix, hipStream_t stream);
+// uniform: the kept entries of [e0, e1), new indices base .. , to d_bounce (plane p at p * bstride; bstride >= entries kept)
+hipError_t launch_remove_gather_planes(const uint4* d_planes, uint64_t stride, uint32_t n_planes, const uint32_t* d_map, uint64_t e0,
+                                       uint64_t e1, uint32_t base, uint4* d_bounce, uint64_t bstride, hipStream_t stream);
+// the first k uint4 of every plane of d_bounce to d_dst + p * stride + base
+hipError_t launch_remove_scatter(const uint4* d_bounce, uint64_t bstride, uint32_t n_planes, uint4* d_dst, uint64_t stride, uint64_t base,
+                                 uint64_t k, hipStream_t stream);
+// ragged: the records [r0, r1) of kept entries, new positions base .. , to d_bounce (`slots` records), their entry-index field
+// rewritten; d_new_off: the kept entries' new first records, by NEW index
+hipError_t launch_remove_gather_records(const uint4* d_recs, const uint32_t* d_old_off, const uint32_t* d_new_off, const uint32_t* d_map,
+                                        uint64_t n_entries, uint64_t r0, uint64_t r1, uint64_t base, uint4* d_bounce, uint64_t slots,
+                                        hipStream_t stream);
+
 // alignment (k_align.hip): the best sliding offset of (query, entry) pairs, after selection.  A corpus as its kernels read it:
 struct AlignSource {
     bool ragged = false;
@@ -683,4 +711,13 @@ struct LBAudioDetectiveCorpus {
     lbad::DeviceBuffer<void> d_join_scratch;
     lbad::Event join_ev;
     uint64_t join_scratch_limit = 0;
+    // removal (LBAudioDetectiveCorpusRemove..., api_remove.cpp, k_remove.hip): the index block (RemoveIndex) with the staged
+    // list of the host form and, ragged, the new offsets behind it; and the bounce buffer the kept planes or records of a chunk
+    // pass through, bounded by the limit (0 = the default).  Both grow on demand; a removal is synchronous, nothing of it is in
+    // flight when it returns.
+    lbad::DeviceBuffer<uint32_t> d_remove_index;
+    lbad::DeviceBuffer<unsigned long long> d_remove_list;
+    lbad::DeviceBuffer<uint32_t> d_remove_off;
+    lbad::DeviceBuffer<uint4> d_remove_bounce;
+    uint64_t remove_scratch_limit = 0;
 };

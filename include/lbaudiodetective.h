@@ -670,6 +670,50 @@ OSStatus LBAudioDetectiveCorpusRemoveKeysDevice(LBAudioDetectiveCorpusRef inCorp
                                                 UInt64 inIndexBase, void* outNewIndices /* device, may be NULL */,
                                                 UInt64* outRemoved /* host */, void* inStream);
 OSStatus LBAudioDetectiveCorpusSetRemoveScratchLimit(LBAudioDetectiveCorpusRef inCorpus, UInt64 inBytes);   /* 0 = default */
+/* Gather: entries handed back out of a corpus on the device, in the packed layout LBAudioDetectiveFingerprintClipsDevice writes
+ * and every ...Packed...Device query and both Append...PackedDevice calls read -- so the matches of a top-K, threshold or join
+ * call can be queried again (also against a ragged corpus, with its own entries), appended to another corpus or looked at,
+ * without the host seeing them.  Both kinds of corpus (uniform of any shape, ragged).
+ * Rows and offsets.  Row i of the output belongs to element i of the list, in list order; nothing is sorted, a duplicate yields
+ * a second copy.  LBAudioDetectiveCorpusGatherKeysDevice reads inCount 64-bit keys on the device as
+ * LBAudioDetectiveCorpusRemoveKeysDevice reads them: the low word is 0xFFFFFFFF - (inIndexBase + index), the score word is
+ * ignored.  A zero key, or a key whose index lies outside [inIndexBase, inIndexBase + count), yields an EMPTY row (the
+ * alignment's and the removal's convention): a top-K or threshold row padded with zeros can be passed as it is.  outOffsets
+ * receives inCount + 1 UInt64: offsets[0] = 0, offsets[i + 1] - offsets[i] = the sub-fingerprints of row i (0 for an empty row,
+ * subfingerprintsPerEntry for a uniform corpus, the entry's own count for a ragged one), offsets[inCount] = the TRUE total,
+ * never cut.
+ * Packed output and capacity.  outPacked has room for inCapacity sub-fingerprints of LBAD_PACKED_BYTES each.  The sub-fingerprint
+ * at output position p (row i's sub-fingerprint s at offsets[i] + s) is written when p < inCapacity; nothing is written at or
+ * beyond the capacity.  A total above the capacity tells that the output was cut, which is no error; an entry may be cut in
+ * the middle.  inCapacity == 0 with outPacked == NULL is the sizing call: it writes the offsets only.
+ * Bytes returned.  Boolean b at bit b & 31 of word b >> 5.  The output holds the stored Booleans below the sub-fingerprint
+ * length rounded up to an even number -- what both corpus layouts keep -- and every higher bit is zero; the derived fields of a
+ * ragged corpus' records never appear.  For rows that were appended with their unused bits zero (the packed contract) the
+ * gather returns the appended bytes bit for bit, and appending a gathered entry to a fresh corpus reproduces its stored bytes.
+ * Sharding.  A shard with inIndexBase serves exactly the keys of its own range and leaves the other rows empty; the outputs of
+ * all ranks for one key list merge by taking, per row, the one non-empty copy.
+ * The device form writes to device pointers (outPacked 16-byte aligned, inKeys and outOffsets 8-byte aligned; anything else is
+ * kLBAudioDetectiveArgumentInvalid), asynchronously on inStream, which it never awaits; it waits ON THE DEVICE for the latest
+ * append.  The scratch belongs to the corpus: 8 x ceil(inCount / 1024) bytes, the sums of the tiles of 1024 keys (the row
+ * lengths themselves are scanned in place in outOffsets).  It grows on demand, and a call waits for the previous gather's device
+ * work before it reuses it.  Like every other call, a gather must not run concurrently with a removal of the same corpus.
+ * LBAudioDetectiveCorpusGatherIndices is the device form on the null stream with one read-back: indices, packed bytes and
+ * offsets are in host memory, duplicates are allowed, and any index >= the count is kLBAudioDetectiveArgumentInvalid with
+ * nothing written.
+ * LBAudioDetectiveCorpusCopyFingerprint returns a NEW host fingerprint holding entry inIndex -- the corpus' sub-fingerprint
+ * length, the entry's sub-fingerprints in order; it equals (LBAudioDetectiveFingerprintEqualToFingerprint) the fingerprint
+ * LBAudioDetectiveCorpusAppendFingerprint stored, and the caller disposes it.  NULL for a NULL corpus, an index >= the count,
+ * no device or a failed device call.
+ * A NULL corpus, a NULL outOffsets, a NULL list with inCount != 0, a NULL outPacked with inCapacity != 0, inCount > 2^31 and
+ * inIndexBase > 2^32 are kLBAudioDetectiveArgumentInvalid, decided before a handle is read; then a missing device is
+ * kLBAudioDetectiveDeviceUnavailable; then inIndexBase + entries > 2^32 is kLBAudioDetectiveArgumentInvalid.  inCount == 0 is
+ * noErr and writes offsets[0] = 0; an empty corpus makes every row empty. */
+OSStatus LBAudioDetectiveCorpusGatherKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inKeys /* device */,
+                                                UInt64 inCount, UInt64 inIndexBase, void* outPacked /* device */,
+                                                UInt64 inCapacity, void* outOffsets /* device */, void* inStream);
+OSStatus LBAudioDetectiveCorpusGatherIndices(LBAudioDetectiveCorpusRef inCorpus, const UInt64* inIndices, UInt64 inCount,
+                                             void* outPacked /* host */, UInt64 inCapacity, UInt64* outOffsets /* host */);
+LBAudioDetectiveFingerprintRef LBAudioDetectiveCorpusCopyFingerprint(LBAudioDetectiveCorpusRef inCorpus, UInt64 inIndex);
 /* Where a match lies.  LBAudioDetectiveFingerprintCompareToFingerprint (Fp.m:119-149) slides the shorter fingerprint along
  * the longer one; the corpus passes the query as its first argument.  Entry longer than the query ("A"): the query slides
  * along the entry.  Otherwise ("B", equal lengths included): the entry slides along the query.  With n1 >= n2 the two counts,

@@ -888,6 +888,65 @@ class Corpus:
         the default"""
         _check(self._L.LBAudioDetectiveCorpusSetRemoveScratchLimit(self._ref, n_bytes), "CorpusSetRemoveScratchLimit")
 
+    # ---- gather: entries handed back in the packed layout (Boolean b at bit b & 31 of word b >> 5, 32 bytes per sub-fingerprint),
+    # row i = element i of the list, with the rows' offsets: offsets[i + 1] - offsets[i] sub-fingerprints, offsets[-1] the total.
+    def gather_keys_device(self, keys, index_base: int = 0, packed_out=None, offsets_out=None, capacity=None, stream=None):
+        """LBAudioDetectiveCorpusGatherKeysDevice: the entries named by 64-bit keys on the device, exactly as the top-K, threshold
+        and join calls write them (global index = index_base + local; a zero key or a key of another entry is an empty row,
+        duplicates yield copies) -> (packed uint8 [capacity, 32], offsets int64 [len(keys) + 1]) on the device, asynchronously on
+        `stream`.  Positions at or above the capacity are not written; offsets[-1] is the true total either way.  With neither
+        capacity nor packed_out given the call sizes itself first (the sizing call and one read-back of the total)."""
+        import torch
+        assert keys.is_cuda and keys.is_contiguous() and keys.element_size() == 8
+        n = keys.numel()
+        sp = _stream_ptr(stream)
+        if offsets_out is None:
+            offsets_out = torch.empty(n + 1, dtype=torch.int64, device=keys.device)
+        _out_ok(offsets_out, n + 1, "offsets_out")
+        fn = self._L.LBAudioDetectiveCorpusGatherKeysDevice
+        if capacity is None:
+            if packed_out is not None:
+                capacity = packed_out.numel() * packed_out.element_size() // N.PACKED_BYTES
+            else:
+                _check(fn(self._ref, _dev_ptr(keys) if n else None, n, index_base, None, 0, _dev_ptr(offsets_out), sp),
+                       "CorpusGatherKeysDevice")
+                if stream is not None:
+                    stream.synchronize()
+                else:
+                    torch.cuda.current_stream().synchronize()
+                capacity = int(offsets_out[n].item())
+        if packed_out is None:
+            packed_out = torch.empty((capacity, N.PACKED_BYTES), dtype=torch.uint8, device=keys.device)
+        if not packed_out.is_cuda or not packed_out.is_contiguous() or packed_out.numel() * packed_out.element_size() < capacity * N.PACKED_BYTES:
+            raise ValueError("packed_out must be a contiguous device tensor of at least capacity * 32 bytes")
+        _check(fn(self._ref, _dev_ptr(keys) if n else None, n, index_base, _dev_ptr(packed_out) if capacity else None, capacity,
+                  _dev_ptr(offsets_out), sp), "CorpusGatherKeysDevice")
+        return packed_out, offsets_out
+
+    def gather(self, indices):
+        """LBAudioDetectiveCorpusGatherIndices: the entries at `indices` (host integers, duplicates allowed; an index >= len(self)
+        is refused) -> numpy (packed uint8 [total, 32], offsets uint64 [len(indices) + 1])."""
+        idx = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.uint64)
+        n = idx.size
+        ip = idx.ctypes.data_as(C.POINTER(N.UInt64)) if n else None
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        op = offsets.ctypes.data_as(C.POINTER(N.UInt64))
+        _check(self._L.LBAudioDetectiveCorpusGatherIndices(self._ref, ip, n, None, 0, op), "CorpusGatherIndices")
+        total = int(offsets[n])
+        packed = np.zeros((total, N.PACKED_BYTES), dtype=np.uint8)
+        if total:
+            _check(self._L.LBAudioDetectiveCorpusGatherIndices(self._ref, ip, n, packed.ctypes.data, total, op), "CorpusGatherIndices")
+        return packed, offsets
+
+    def fingerprint(self, index: int) -> Fingerprint:
+        """LBAudioDetectiveCorpusCopyFingerprint: entry `index` as a new host Fingerprint (IndexError for index >= len(self))."""
+        if not 0 <= index < len(self):
+            raise IndexError(f"entry {index} of a corpus of {len(self)}")
+        ref = self._L.LBAudioDetectiveCorpusCopyFingerprint(self._ref, index)
+        if not ref:
+            raise LBAudioDetectiveError(1, "CorpusCopyFingerprint")
+        return Fingerprint(_ref=ref)
+
     # ---- where a match lies (LBAudioDetectiveCorpusQueryAligned and kin): lag > 0, the query's sub-fingerprint 0 lines up
     # with the entry's sub-fingerprint lag (the entry is the longer one); lag < 0, the entry's sub-fingerprint 0 lines up with
     # the query's sub-fingerprint -lag; 0 for equal lengths and for empty slots.  Positions in seconds: lag x 128 x analysis

@@ -420,7 +420,8 @@ OSStatus LBAudioDetectiveCorpusAppendRaggedPackedDevice(LBAudioDetectiveCorpusRe
 }
 
 // Everything that may still touch the corpus' memory is awaited first -- the plan, the scans, the top-K, alignment and packed
-// scratch, the joins that scanned it or took their rows from it (join_ev, with the join scratch), the polled query's stream --
+// scratch, the joins that scanned it or took their rows from it (join_ev, with the join scratch), the gathers (gather_ev), the
+// polled query's stream --
 // and nothing else: NOT append_event or shard_stale_event (the latter may sit behind a collective that never ends).  The
 // members then release what they own.
 void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
@@ -431,6 +432,7 @@ void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
     (void)c->align_ev.wait();
     (void)c->pq_ev.wait();
     (void)c->join_ev.wait();
+    (void)c->gather_ev.wait();
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     delete c;
 }

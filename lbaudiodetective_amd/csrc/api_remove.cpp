@@ -32,6 +32,7 @@ OSStatus await_in_flight(LBAudioDetectiveCorpus* c, hipStream_t stream) {
     if (st == noErr) st = c->align_ev.wait();
     if (st == noErr) st = c->pq_ev.wait();
     if (st == noErr) st = c->join_ev.wait();
+    if (st == noErr) st = c->gather_ev.wait();
     if (st != noErr) return st;
     if (c->stream) LBAD_HIP(hipStreamSynchronize(c->stream));        // the polled top-1 query's own stream
     if (c->append_event.ev) LBAD_HIP(hipStreamWaitEvent(stream, c->append_event, 0));

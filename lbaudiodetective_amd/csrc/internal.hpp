@@ -379,6 +379,27 @@ hipError_t launch_remove_gather_records(const uint4* d_recs, const uint32_t* d_o
                                         uint64_t n_entries, uint64_t r0, uint64_t r1, uint64_t base, uint4* d_bounce, uint64_t slots,
                                         hipStream_t stream);
 
+// gather (k_gather.hip): entries handed back in the packed layout, named by keys.  A corpus as its kernels read it:
+struct GatherSource {
+    bool ragged = false;
+    const uint4* recs = nullptr;        // ragged: the records, the entries' record positions and the longest entry
+    const uint32_t* off = nullptr;
+    uint32_t ne_max = 0;
+    const uint4* planes = nullptr;      // uniform: the planes, plane stride `stride`, planes per entry
+    uint64_t stride = 0;
+    uint32_t n_planes = 0, n_sub = 0;
+    uint64_t count = 0;
+    uint32_t subfp_len = 0;
+};
+uint32_t gather_tile_keys();                     // keys per tile of the lengths and offsets launches
+size_t gather_scratch_bytes(uint64_t n_keys);    // one 64-bit sum per tile
+// 1 <= n_keys <= 2^31 keys at d_keys (a zero key, or an index outside [index_base, index_base + count): an empty row) -> the
+// rows' offsets (n_keys + 1 words, the last one the true total) to d_offsets and the sub-fingerprints at positions below
+// `capacity` to d_packed (16-byte aligned; may be null when capacity is 0), 32 bytes each.  d_scratch: gather_scratch_bytes(n_keys)
+// bytes, written before they are read.  Three launches and the copy on `stream`, nothing visits the host.
+hipError_t launch_gather(const GatherSource& src, const unsigned long long* d_keys, uint64_t n_keys, uint64_t index_base, void* d_scratch,
+                         void* d_packed, uint64_t capacity, unsigned long long* d_offsets, hipStream_t stream);
+
 // alignment (k_align.hip): the best sliding offset of (query, entry) pairs, after selection.  A corpus as its kernels read it:
 struct AlignSource {
     bool ragged = false;
@@ -720,4 +741,8 @@ struct LBAudioDetectiveCorpus {
     lbad::DeviceBuffer<uint32_t> d_remove_off;
     lbad::DeviceBuffer<uint4> d_remove_bounce;
     uint64_t remove_scratch_limit = 0;
+    // gather (LBAudioDetectiveCorpusGather..., api_gather.cpp, k_gather.hip): the tile sums of the offsets' scan.  Grown on demand;
+    // a call reuses it only after gather_ev, recorded behind its last kernel.
+    lbad::DeviceBuffer<void> d_gather_scratch;
+    lbad::Event gather_ev;
 };

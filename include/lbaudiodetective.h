@@ -714,6 +714,57 @@ OSStatus LBAudioDetectiveCorpusGatherKeysDevice(LBAudioDetectiveCorpusRef inCorp
 OSStatus LBAudioDetectiveCorpusGatherIndices(LBAudioDetectiveCorpusRef inCorpus, const UInt64* inIndices, UInt64 inCount,
                                              void* outPacked /* host */, UInt64 inCapacity, UInt64* outOffsets /* host */);
 LBAudioDetectiveFingerprintRef LBAudioDetectiveCorpusCopyFingerprint(LBAudioDetectiveCorpusRef inCorpus, UInt64 inIndex);
+/* Groups: the step between a join's duplicate pairs and the removal -- the connected components of the match graph, computed on
+ * the device where the keys lie, and the key list "every entry except the first of its group", which
+ * LBAudioDetectiveCorpusRemoveKeysDevice and LBAudioDetectiveCorpusGatherKeysDevice take as it is.  (The join reports ORDERED
+ * pairs, so a pair of near-copies shows up as i -> j and j -> i: removing the join's keys themselves removes every member of
+ * every duplicate set, the original included.)  Neither call takes a corpus: they work on keys and labels alone.
+ * The graph.  The vertices are the entries 0 .. inEntryCount - 1 of ONE index space (in practice a corpus joined with itself).
+ * Every key slot p < inSlotCount that holds a valid key is an undirected edge {entry of p's row, entry of the key}.  A key is
+ * read as the removal reads it: the low word is 0xFFFFFFFF - (inIndexBase + index), the score word is ignored, a zero key and
+ * a key whose index lies outside [inIndexBase, inIndexBase + inEntryCount) are skipped; self-edges and repeated edges are
+ * harmless.  A match in EITHER direction joins two entries (score(i -> j) >= t does not imply score(j -> i) >= t): a group is
+ * a component of the undirected graph, and there is no "both directions only" mode.
+ * The row of a slot.  inOffsets given: the join's CSR, inRowCount + 1 UInt64; slot p belongs to the last row r with
+ * offsets[r] <= p, and only slots below min(offsets[inRowCount], inSlotCount) are read -- a cut list is used as far as it goes
+ * and no status says so (the caller has the true total in the offsets); inRowPitch is ignored.  inOffsets NULL: pitched rows,
+ * the threshold batch calls' layout; slot p belongs to row p / inRowPitch, inRowPitch >= 1 and inSlotCount == inRowCount x
+ * inRowPitch, and the zero padding inside the rows is skipped.
+ * The entry of a row.  inRowKeys NULL: row r is entry inFirstRow + r (the join's inFirstQuery).  inRowKeys given: inRowCount
+ * keys, row r is the entry key r names and a zero or out-of-range row key makes the whole row empty (inFirstRow is ignored) --
+ * the key list a LBAudioDetectiveCorpusGatherKeysDevice call was given, which serves a ragged corpus' route: gather the entries
+ * of one length, query them with LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice, group the key block.
+ * The result.  ioLabels[i] (UInt32) is the LOWEST entry index of i's component: that entry is the group's first entry, and its
+ * label is its own index.  outGroupCount, when given, receives the number of components as one UInt64.  The result is a
+ * function of the edge set alone: it does not depend on launch order, grid, slot order or chunking.
+ * Several calls.  inReset != 0 starts from "every entry alone"; inReset == 0 adds this call's edges to the grouping ioLabels
+ * holds, so a self-join made in row chunks is grouped chunk by chunk, in any order of the chunks, into the labels of one call
+ * over all edges.  Without a reset ioLabels is read as a forest -- a word below its own index is the entry's parent, any other
+ * word makes the entry a group's first -- so no content of it can make the call read out of range or run on.
+ * The call is asynchronous on inStream, which is never awaited; nothing is read back, the number of launches (at most three and
+ * one 8-byte memset) does not depend on the data, and there is no scratch beyond the caller's buffers.
+ * Decided before anything touches the device, each kLBAudioDetectiveArgumentInvalid: a NULL ioLabels; a NULL inKeys with
+ * inSlotCount != 0; inIndexBase > 2^32 or inIndexBase + inEntryCount > 2^32; inSlotCount > 2^31; inRowCount > 2^32; inRowKeys
+ * NULL and inFirstRow + inRowCount > inEntryCount; the pitch rules; a pointer not aligned to its element (8 bytes for keys,
+ * offsets, row keys and the group count, 4 for labels).  Then a missing device is kLBAudioDetectiveDeviceUnavailable.
+ * inEntryCount == 0 is noErr and writes a group count of 0; inRowCount == 0 or inSlotCount == 0 adds no edge (with inReset
+ * the labels are the identity).
+ * LBAudioDetectiveGroupExtraKeysFromLabelsDevice writes the key of every entry whose label is not its own index -- every entry
+ * that is not its group's first -- in ascending index to the slots 0 .. min(count, inCapacity) - 1 of outKeys, zero keys
+ * behind them, and the TRUE number, inEntryCount - groups, to *outCount (host).  A key's score word is the bits of 1.0f, so a
+ * key is never zero, also for index 0xFFFFFFFF.  Like LBAudioDetectiveThresholdKeysFromScoresDevice the call owns its scratch
+ * (8 x (ceil(inEntryCount / 1024) + 1) bytes) and returns once the keys are written.  NULL inLabels, outKeys or outCount,
+ * inCapacity outside 1 .. 2^31, the index-base rules above and misaligned device pointers are
+ * kLBAudioDetectiveArgumentInvalid; then a missing device is kLBAudioDetectiveDeviceUnavailable. */
+OSStatus LBAudioDetectiveGroupLabelsFromKeysDevice(const void* inKeys /* device */, UInt64 inSlotCount,
+                                                   const void* inOffsets /* device, inRowCount + 1 UInt64, or NULL */,
+                                                   UInt64 inRowPitch, UInt64 inRowCount, UInt64 inFirstRow,
+                                                   const void* inRowKeys /* device, inRowCount keys, or NULL */, UInt64 inIndexBase,
+                                                   UInt64 inEntryCount, UInt32 inReset, void* ioLabels /* device, inEntryCount UInt32 */,
+                                                   void* outGroupCount /* device, one UInt64, may be NULL */, void* inStream);
+OSStatus LBAudioDetectiveGroupExtraKeysFromLabelsDevice(const void* inLabels /* device */, UInt64 inEntryCount, UInt64 inIndexBase,
+                                                        UInt64 inCapacity, void* outKeys /* device, inCapacity keys */,
+                                                        UInt64* outCount /* host */, void* inStream);
 /* Where a match lies.  LBAudioDetectiveFingerprintCompareToFingerprint (Fp.m:119-149) slides the shorter fingerprint along
  * the longer one; the corpus passes the query as its first argument.  Entry longer than the query ("A"): the query slides
  * along the entry.  Otherwise ("B", equal lengths included): the entry slides along the query.  With n1 >= n2 the two counts,

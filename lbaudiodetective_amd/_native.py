@@ -196,6 +196,9 @@ _SIGNATURES = {
     "LBAudioDetectiveCorpusGatherKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, UInt64, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusGatherIndices": (OSStatus, [Ref, _P(UInt64), UInt64, C.c_void_p, UInt64, _P(UInt64)]),
     "LBAudioDetectiveCorpusCopyFingerprint": (Ref, [Ref, UInt64]),
+    "LBAudioDetectiveGroupLabelsFromKeysDevice": (OSStatus, [C.c_void_p, UInt64, C.c_void_p, UInt64, UInt64, UInt64, C.c_void_p, UInt64, UInt64,
+                                                             UInt32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveGroupExtraKeysFromLabelsDevice": (OSStatus, [C.c_void_p, UInt64, UInt64, UInt64, C.c_void_p, _P(UInt64), C.c_void_p]),
     "LBAudioDetectiveCorpusAlignKeysDevice": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, C.c_void_p, UInt64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusQueryBatchTopKAligned": (OSStatus, [Ref, _P(Ref), UInt32, UInt32, UInt32, _P(SInt64), _P(Float32), _P(SInt32), _P(UInt32)]),
     "LBAudioDetectiveCorpusQueryAligned": (OSStatus, [Ref, Ref, UInt32, _P(SInt64), _P(Float32), _P(SInt32)]),

@@ -947,6 +947,59 @@ class Corpus:
             raise LBAudioDetectiveError(1, "CorpusCopyFingerprint")
         return Fingerprint(_ref=ref)
 
+    # ---- duplicate groups: the connected components of the self-join's match graph (a match in either direction joins two
+    # entries), and the removal of everything except each group's first entry.  Composites in Python over the device calls, as
+    # identify_clips_device is; uniform corpora of the join's shape (the join refuses the rest).
+    def duplicate_groups(self, threshold: float, key_capacity: int = 1 << 22, rows_per_call=None, range_: int = 0, stream=None):
+        """(labels int32 [len(self)], group_count int64 [1]) on the device: labels[i] is the lowest index of the entries that
+        entry i is connected to through pairs scoring >= threshold in either direction (see group_labels_from_keys_device).  A
+        self-join with skip_same_index in chunks of rows, each chunk's keys grouped into the one labels tensor.  Each chunk's
+        total is read back; a chunk whose total exceeds key_capacity is redone with half the rows (a multiple of 64 while there
+        are 64 or more), and a single row that does not fit raises ValueError: the result never rests on a cut list and
+        depends on neither key_capacity nor rows_per_call."""
+        import torch
+        n = len(self)
+        if key_capacity < 1:
+            raise ValueError("key_capacity must be at least 1")
+        labels = torch.empty(max(1, n), dtype=torch.int32, device="cuda")[:n]
+        groups = torch.zeros(1, dtype=torch.int64, device="cuda")
+        if n == 0:
+            return labels, groups
+        rows = n if rows_per_call is None else max(1, min(int(rows_per_call), n))
+        keys = torch.empty(key_capacity, dtype=torch.int64, device="cuda")
+        offsets = torch.empty(rows + 1, dtype=torch.int64, device="cuda")
+        first, reset = 0, True
+        while first < n:
+            count = min(rows, n - first)
+            while True:
+                self.join_threshold_keys_device(threshold, key_capacity, first=first, count=count, skip_same_index=True, range_=range_,
+                                                keys_out=keys, offsets_out=offsets, stream=stream)
+                if stream is not None:
+                    stream.synchronize()
+                total = int(offsets[count].item())         # (the one read-back of a chunk: its true total)
+                if total <= key_capacity:
+                    break
+                if count == 1:
+                    raise ValueError(f"row {first} alone has {total} matches: key_capacity {key_capacity} is too small")
+                count = count // 2 // 64 * 64 if count >= 128 else max(1, count // 2)
+                rows = count                               # (it stays: the rows behind are likely as dense)
+            group_labels_from_keys_device(keys, n, offsets=offsets, n_rows=count, first_row=first, labels=labels, reset=reset,
+                                          group_count=groups, n_slots=min(total, key_capacity), stream=stream)
+            reset = False
+            first += count
+        return labels, groups
+
+    def deduplicate(self, threshold: float, key_capacity: int = 1 << 22, rows_per_call=None, range_: int = 0, stream=None):
+        """duplicate_groups, then the keys of every entry that is not its group's first, then remove_keys_device: one entry per
+        group stays, the first.  Returns (removed, labels_before): the number of entries removed and the labels over the OLD
+        indices."""
+        labels, _ = self.duplicate_groups(threshold, key_capacity=key_capacity, rows_per_call=rows_per_call, range_=range_, stream=stream)
+        if len(self) == 0:
+            return 0, labels
+        keys, count = group_extra_keys_from_labels_device(labels, stream=stream)
+        removed = self.remove_keys_device(keys[:count], stream=stream) if count else 0
+        return removed, labels
+
     # ---- where a match lies (LBAudioDetectiveCorpusQueryAligned and kin): lag > 0, the query's sub-fingerprint 0 lines up
     # with the entry's sub-fingerprint lag (the entry is the longer one); lag < 0, the entry's sub-fingerprint 0 lines up with
     # the query's sub-fingerprint -lag; 0 for equal lengths and for empty slots.  Positions in seconds: lag x 128 x analysis
@@ -1235,6 +1288,71 @@ def decode_join_keys(keys, offsets, first: int = 0):
     rows = np.searchsorted(off, np.arange(len(k), dtype=np.uint64), side="right").astype(np.int64) - 1 + int(first)
     return (rows, (0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32),
             total)
+
+
+def group_labels_from_keys_device(keys, n_entries: int, offsets=None, row_pitch: int = 0, first_row: int = 0, row_keys=None,
+                                  index_base: int = 0, labels=None, reset: bool = True, stream=None, n_rows=None, n_slots=None,
+                                  group_count=None):
+    """LBAudioDetectiveGroupLabelsFromKeysDevice: the connected components of the graph whose edges are match keys on the device
+    -> (labels int32 [n_entries], group_count int64 [1]), both on the device, asynchronously on `stream`.  labels[i] is the
+    lowest entry index of i's component.  `keys` with `offsets` (int64 [rows + 1]) is a join's CSR; without offsets the keys
+    are rows of row_pitch slots (a 2-d tensor gives its own pitch), the threshold batch calls' layout.  Row r is entry
+    first_row + r, or the entry row_keys[r] names.  reset=False adds the edges to the grouping `labels` already holds.  n_rows
+    and n_slots default to what the tensors hold; group_count may be given to be reused."""
+    import torch
+    assert keys.is_cuda and keys.is_contiguous() and keys.element_size() == 8
+    if offsets is not None:
+        assert offsets.is_cuda and offsets.is_contiguous() and offsets.element_size() == 8
+        if n_rows is None:
+            n_rows = offsets.numel() - 1
+        _out_ok(offsets, n_rows + 1, "offsets")
+        if n_slots is None:
+            n_slots = keys.numel()
+    else:
+        if not row_pitch:
+            if keys.dim() != 2:
+                raise ValueError("pitched rows need row_pitch or a 2-d key tensor")
+            row_pitch = keys.shape[1]
+        if n_rows is None:
+            n_rows = keys.numel() // row_pitch
+        if n_slots is None:
+            n_slots = n_rows * row_pitch
+    _out_ok(keys, n_slots, "keys")
+    if row_keys is not None:
+        assert row_keys.is_cuda and row_keys.is_contiguous() and row_keys.element_size() == 8
+        _out_ok(row_keys, n_rows, "row_keys")
+    if labels is None:
+        if not reset:
+            raise ValueError("reset=False needs the labels of the calls before")
+        labels = torch.empty(max(1, n_entries), dtype=torch.int32, device=keys.device)[:n_entries]
+    assert labels.element_size() == 4
+    _out_ok(labels, n_entries, "labels")
+    if group_count is None:
+        group_count = torch.empty(1, dtype=torch.int64, device=keys.device)
+    _out_ok(group_count, 1, "group_count")
+    _check(N.lib().LBAudioDetectiveGroupLabelsFromKeysDevice(_dev_ptr(keys) if n_slots else None, n_slots,
+                                                             _dev_ptr(offsets) if offsets is not None else None, row_pitch, n_rows,
+                                                             first_row, _dev_ptr(row_keys) if row_keys is not None else None,
+                                                             index_base, n_entries, int(bool(reset)), _dev_ptr(labels),
+                                                             _dev_ptr(group_count), _stream_ptr(stream)), "GroupLabelsFromKeysDevice")
+    return labels, group_count
+
+
+def group_extra_keys_from_labels_device(labels, capacity=None, index_base: int = 0, stream=None):
+    """LBAudioDetectiveGroupExtraKeysFromLabelsDevice: the keys (score word 1.0f) of every entry whose label is not its own
+    index -- everything except the first entry of each group -- in ascending index -> (keys int64 [capacity] on the device,
+    0-padded, count): the true number, also above the capacity (None: one slot per entry).  Corpus.remove_keys_device and
+    Corpus.gather_keys_device take the keys as they are.  Returns once the keys are written."""
+    import torch
+    assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 4
+    n = labels.numel()
+    if capacity is None:
+        capacity = max(1, n)
+    keys = torch.empty(max(1, capacity), dtype=torch.int64, device=labels.device)
+    count = N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveGroupExtraKeysFromLabelsDevice(_dev_ptr(labels), n, index_base, capacity, _dev_ptr(keys),
+                                                                  C.byref(count), _stream_ptr(stream)), "GroupExtraKeysFromLabelsDevice")
+    return keys, int(count.value)
 
 
 def synth_corpus_device(seed: int, first: int, n_entries: int, n_sub: int, subfp_len: int, out=None, stream=None):

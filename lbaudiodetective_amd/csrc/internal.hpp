@@ -400,6 +400,20 @@ size_t gather_scratch_bytes(uint64_t n_keys);    // one 64-bit sum per tile
 hipError_t launch_gather(const GatherSource& src, const unsigned long long* d_keys, uint64_t n_keys, uint64_t index_base, void* d_scratch,
                          void* d_packed, uint64_t capacity, unsigned long long* d_offsets, hipStream_t stream);
 
+// groups (k_groups.hip): the connected components of the graph whose edges are match keys, and the keys of every entry that is
+// not its group's first.  1 <= n <= 2^32 vertices, labels as a forest whose parents lie below their vertices (any content is
+// legal input without a reset).  Slots: n_slots <= 2^31 keys; their rows by d_offsets (n_rows + 1 words, CSR) or, when it is
+// null, by rows of `pitch` slots; a row's entry is first_row + r or, with d_row_keys, the entry key r names.  d_group_count
+// (may be null) must hold 0: the flatten launch ADDS the number of roots.  At most three launches on `stream`.
+hipError_t launch_group_labels(const unsigned long long* d_keys, uint64_t n_slots, const unsigned long long* d_offsets, uint64_t pitch,
+                               uint64_t n_rows, uint64_t first_row, const unsigned long long* d_row_keys, uint64_t index_base, uint64_t n,
+                               bool reset, uint32_t* d_labels, unsigned long long* d_group_count, hipStream_t stream);
+size_t group_extra_scratch_bytes(uint64_t n);    // one 64-bit count per tile of 1024 vertices and the total behind them
+// the keys (score word 1.0f) of the vertices whose label is not their own index, ascending, to the slots below `capacity` of
+// d_keys (zeroed by the caller); the true count to the last word of d_scratch (group_extra_scratch_bytes(n) bytes)
+hipError_t launch_group_extra_keys(const uint32_t* d_labels, uint64_t n, uint64_t index_base, uint64_t capacity, void* d_scratch,
+                                   unsigned long long* d_keys, hipStream_t stream);
+
 // alignment (k_align.hip): the best sliding offset of (query, entry) pairs, after selection.  A corpus as its kernels read it:
 struct AlignSource {
     bool ragged = false;

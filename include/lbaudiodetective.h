@@ -629,6 +629,38 @@ OSStatus LBAudioDetectiveCorpusJoinThreshold(LBAudioDetectiveCorpusRef inCorpus,
                                              UInt32 inSkipSameIndex, UInt64 inCapacity, SInt64* outQueryIndices,
                                              SInt64* outEntryIndices, Float32* outScores, UInt64* outTotal);
 OSStatus LBAudioDetectiveCorpusSetJoinScratchLimit(LBAudioDetectiveCorpusRef inCorpus, UInt64 inBytes);   /* 0 = default */
+/* The join of RAGGED corpora (LBAudioDetectiveCorpusNewRagged): the contract above, word for word, except for what follows.
+ * Both corpora are ragged and of one sub-fingerprint length (inQueries == inCorpus is allowed); a uniform corpus on either
+ * side, two sub-fingerprint lengths, or a longest entry above LBAD_JOIN_RAGGED_MAX_SUBFINGERPRINTS in either corpus are
+ * kLBAudioDetectiveArgumentInvalid (the cap bounds a pair's offsets and a tile's task count to 32 bits and lets a row live in
+ * LDS; 1024 sub-fingerprints are a 25-minute recording at the default settings).  Row i against entry j scores, bit for bit,
+ * what LBAudioDetectiveCorpusScoresDevice(inCorpus, copy of row i's fingerprint, inRange) writes for entry j: the shorter of
+ * the two slides along the longer, fingerprint1 is the entry when the row is shorter and the row otherwise (equal lengths
+ * included), score = max(0, max over the offsets of fl(fl(sum of the steps' hits / possible) / steps)), and a pair matches when
+ * score >= inThreshold as Float32 -- the compare is on the quotient.  outLags (device, inCapacity SInt32, may be NULL; the host
+ * form's outLags likewise) receives in slot p the signed lag of the match in slot p, the value
+ * LBAudioDetectiveCorpusAlignKeysDevice gives for that row and key: +offset when the entry is longer than the row, -offset
+ * otherwise, of the LOWEST offset that reaches the score; 0 behind the matches.  Keys and offsets do not depend on outLags.
+ * Two facts about the ordered pairs, checked on the CPU oracle (260 synthetic entries of 1 .. 300 sub-fingerprints): for
+ * entries of DIFFERENT lengths score(i -> j) and score(j -> i) are the same bits and the lags are opposite -- both directions
+ * slide the shorter along the longer with the longer as fingerprint1; for EQUAL lengths they differ in general (956 of 1 174
+ * equal-length cells did).  The join reports ordered pairs all the same.
+ * The host form returns (row, entry, score, lag), then -1 / -1 / 0 / 0, and the total.  Bound pruning and
+ * LBAudioDetectiveCorpusSetKernelVariant do not apply.
+ * The scratch is inCorpus' join scratch, under LBAudioDetectiveCorpusSetJoinScratchLimit: 16 + rows x (8 + 8 x tiles) +
+ * ceil(rows / 64) x 4 x tiles bytes for a chunk of `rows` rows (a multiple of 64, or all the call's rows), tiles =
+ * ceil(entries of inCorpus / 256); the records of the rows and of inCorpus do not enter it.  A limit below one chunk of 64
+ * rows is kLBAudioDetectiveArgumentInvalid at the call. */
+#define LBAD_JOIN_RAGGED_MAX_SUBFINGERPRINTS 1024
+OSStatus LBAudioDetectiveCorpusJoinRaggedThresholdKeysDevice(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveCorpusRef inQueries,
+                                                             UInt64 inFirstQuery, UInt64 inQueryCount, UInt32 inRange,
+                                                             Float32 inThreshold, UInt32 inSkipSameIndex, UInt64 inCapacity,
+                                                             UInt64 inIndexBase, void* outKeys, void* outLags, void* outOffsets,
+                                                             void* inStream);
+OSStatus LBAudioDetectiveCorpusJoinRaggedThreshold(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveCorpusRef inQueries,
+                                                   UInt64 inFirstQuery, UInt64 inQueryCount, UInt32 inRange, Float32 inThreshold,
+                                                   UInt32 inSkipSameIndex, UInt64 inCapacity, SInt64* outQueryIndices,
+                                                   SInt64* outEntryIndices, Float32* outScores, SInt32* outLags, UInt64* outTotal);
 /* Removal: entries taken out of a corpus on the device, the other half of the corpus life cycle -- the take-down of one
  * recording, or the action behind a join's duplicate pairs.  Both forms, both kinds of corpus (uniform of any shape, ragged):
  * the named entries go, the others keep their relative order and close up -- the entry at old index i gets the new index

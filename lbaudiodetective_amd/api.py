@@ -849,6 +849,53 @@ class Corpus:
         m = min(int(total.value), capacity)
         return rows[:m].copy(), idx[:m].copy(), sc[:m].copy(), int(total.value)
 
+    # ---- the join of RAGGED corpora (Corpus.ragged): the same CSR; the score is the ragged scan's (the shorter entry slides along
+    # the longer) and every match comes with its signed lag.  No entry of either corpus above LBAD_JOIN_RAGGED_MAX_SUBFINGERPRINTS (the header).
+    def join_ragged_threshold_keys_device(self, threshold: float, capacity: int, queries=None, first: int = 0, count=None,
+                                          skip_same_index=None, range_: int = 0, index_base: int = 0, keys_out=None, lags_out=None,
+                                          offsets_out=None, want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusJoinRaggedThresholdKeysDevice: (keys int64 [capacity], lags int32 [capacity] or None, offsets
+        int64 [count + 1]) on the device, asynchronously on `stream`; join_threshold_keys_device's arguments and layout.
+        lags[p] is the lag of the match in slot p (+offset: the entry is longer than the row; -offset otherwise; 0 behind the
+        matches), what align_keys_device gives for that row and key.  want_lags=False (and no lags_out) passes NULL: the keys
+        and offsets are the same."""
+        q, first, count, skip = self._join_args(queries, first, count, skip_same_index)
+        import torch
+        if keys_out is None:
+            keys_out = torch.empty(max(1, capacity), dtype=torch.int64, device="cuda")
+        if lags_out is None and want_lags:
+            lags_out = torch.empty(max(1, capacity), dtype=torch.int32, device="cuda")
+        if offsets_out is None:
+            offsets_out = torch.empty(max(1, count) + 1, dtype=torch.int64, device="cuda")
+        _out_ok(keys_out, capacity, "keys_out")
+        _out_ok(offsets_out, count + 1, "offsets_out")
+        if lags_out is not None:
+            _out_ok(lags_out, capacity, "lags_out")
+        _check(self._L.LBAudioDetectiveCorpusJoinRaggedThresholdKeysDevice(
+            self._ref, q._ref, first, count, range_, threshold, skip, capacity, index_base, _dev_ptr(keys_out),
+            _dev_ptr(lags_out) if lags_out is not None else None, _dev_ptr(offsets_out), _stream_ptr(stream)),
+            "CorpusJoinRaggedThresholdKeysDevice")
+        return keys_out, lags_out, offsets_out
+
+    def join_ragged_threshold(self, threshold: float, capacity: int, queries=None, first: int = 0, count=None, skip_same_index=None,
+                              range_: int = 0):
+        """LBAudioDetectiveCorpusJoinRaggedThreshold: (rows int64[m], indices int64[m], scores float32[m], lags int32[m], total)
+        with m = min(total, capacity), in the device form's order."""
+        q, first, count, skip = self._join_args(queries, first, count, skip_same_index)
+        rows = np.full(max(1, capacity), -1, dtype=np.int64)
+        idx = np.full(max(1, capacity), -1, dtype=np.int64)
+        sc = np.zeros(max(1, capacity), dtype=np.float32)
+        lags = np.zeros(max(1, capacity), dtype=np.int32)
+        total = N.UInt64(0)
+        _check(self._L.LBAudioDetectiveCorpusJoinRaggedThreshold(self._ref, q._ref, first, count, range_, threshold, skip, capacity,
+                                                                rows.ctypes.data_as(C.POINTER(N.SInt64)),
+                                                                idx.ctypes.data_as(C.POINTER(N.SInt64)),
+                                                                sc.ctypes.data_as(C.POINTER(N.Float32)),
+                                                                lags.ctypes.data_as(C.POINTER(N.SInt32)), C.byref(total)),
+               "CorpusJoinRaggedThreshold")
+        m = min(int(total.value), capacity)
+        return rows[:m].copy(), idx[:m].copy(), sc[:m].copy(), lags[:m].copy(), int(total.value)
+
     def set_join_scratch_limit(self, n_bytes: int):
         """bytes of device memory the join's scratch may take, and thereby the rows per chunk; 0 restores the default"""
         _check(self._L.LBAudioDetectiveCorpusSetJoinScratchLimit(self._ref, n_bytes), "CorpusSetJoinScratchLimit")
@@ -949,7 +996,7 @@ class Corpus:
 
     # ---- duplicate groups: the connected components of the self-join's match graph (a match in either direction joins two
     # entries), and the removal of everything except each group's first entry.  Composites in Python over the device calls, as
-    # identify_clips_device is; uniform corpora of the join's shape (the join refuses the rest).
+    # identify_clips_device is; uniform corpora of the join's shape and ragged corpora (the ragged join), the joins refuse the rest.
     def duplicate_groups(self, threshold: float, key_capacity: int = 1 << 22, rows_per_call=None, range_: int = 0, stream=None):
         """(labels int32 [len(self)], group_count int64 [1]) on the device: labels[i] is the lowest index of the entries that
         entry i is connected to through pairs scoring >= threshold in either direction (see group_labels_from_keys_device).  A
@@ -968,12 +1015,18 @@ class Corpus:
         rows = n if rows_per_call is None else max(1, min(int(rows_per_call), n))
         keys = torch.empty(key_capacity, dtype=torch.int64, device="cuda")
         offsets = torch.empty(rows + 1, dtype=torch.int64, device="cuda")
+        ragged = self.subfingerprints_per_entry == 0       # (Corpus.ragged: entries of any length)
         first, reset = 0, True
         while first < n:
             count = min(rows, n - first)
             while True:
-                self.join_threshold_keys_device(threshold, key_capacity, first=first, count=count, skip_same_index=True, range_=range_,
-                                                keys_out=keys, offsets_out=offsets, stream=stream)
+                if ragged:
+                    self.join_ragged_threshold_keys_device(threshold, key_capacity, first=first, count=count, skip_same_index=True,
+                                                           range_=range_, keys_out=keys, offsets_out=offsets, want_lags=False,
+                                                           stream=stream)
+                else:
+                    self.join_threshold_keys_device(threshold, key_capacity, first=first, count=count, skip_same_index=True,
+                                                    range_=range_, keys_out=keys, offsets_out=offsets, stream=stream)
                 if stream is not None:
                     stream.synchronize()
                 total = int(offsets[count].item())         # (the one read-back of a chunk: its true total)

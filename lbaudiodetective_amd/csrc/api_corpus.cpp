@@ -951,27 +951,34 @@ bool join_args_ok(uint64_t first, uint64_t count, float threshold, uint64_t capa
 }
 
 // what the handles decide, before anything is reserved or launched: two uniform corpora of one shape, and that shape the
-// specialised scan's; the rows and the indices in range; rows per chunk under the scratch limit (at most `count`)
+// specialised scan's -- or, for the ragged join, two ragged corpora of one sub-fingerprint length with no entry above the cap
+// (ne_max: the host knows it); the rows and the indices in range; rows per chunk under the scratch limit (at most `count`)
 OSStatus join_plan(const LBAudioDetectiveCorpus* c, const LBAudioDetectiveCorpus* q, uint64_t first, uint64_t count,
-                   uint64_t index_base, uint64_t* out_chunk) {
-    if (c->ragged || q->ragged || c->subfp_len != q->subfp_len || c->n_sub != q->n_sub ||
-        !planes_fast_supported(c->subfp_len, c->n_sub, c->n_sub))
+                   uint64_t index_base, bool ragged, uint64_t* out_chunk) {
+    if (ragged) {
+        if (!c->ragged || !q->ragged || c->subfp_len != q->subfp_len || c->ne_max > LBAD_JOIN_RAGGED_MAX_SUBFINGERPRINTS ||
+            q->ne_max > LBAD_JOIN_RAGGED_MAX_SUBFINGERPRINTS)
+            return kLBAudioDetectiveArgumentInvalid;
+    } else if (c->ragged || q->ragged || c->subfp_len != q->subfp_len || c->n_sub != q->n_sub ||
+               !planes_fast_supported(c->subfp_len, c->n_sub, c->n_sub)) {
         return kLBAudioDetectiveArgumentInvalid;
+    }
     if (first + count > q->count || index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
     const uint64_t limit = c->join_scratch_limit ? c->join_scratch_limit : kJoinScratchDefault;
-    const uint64_t chunk = join_chunk_rows(c->count, limit);
+    const uint64_t chunk = ragged ? join_ragged_chunk_rows(c->count, limit) : join_chunk_rows(c->count, limit);
     if (chunk == 0) return kLBAudioDetectiveArgumentInvalid;          // the limit holds no row tile of this corpus
     *out_chunk = chunk < count ? chunk : count;
     return noErr;
 }
 
+// (ragged: the join of two ragged corpora, k_join_ragged.hip; lags: its optional lag slots, NULL for the uniform join)
 OSStatus join_keys_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, uint64_t first, uint64_t count, uint32_t range,
-                        float threshold, uint32_t skip, uint64_t capacity, uint64_t index_base, unsigned long long* keys,
-                        unsigned long long* offsets, hipStream_t stream) {
+                        float threshold, uint32_t skip, uint64_t capacity, uint64_t index_base, bool ragged, unsigned long long* keys,
+                        int32_t* lags, unsigned long long* offsets, hipStream_t stream) {
     if (!c || !q || !keys || !offsets || !join_args_ok(first, count, threshold, capacity, index_base)) return kLBAudioDetectiveArgumentInvalid;
     if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
     uint64_t chunk = 0;
-    OSStatus st = join_plan(c, q, first, count, index_base, &chunk);
+    OSStatus st = join_plan(c, q, first, count, index_base, ragged, &chunk);
     if (st != noErr) return st;
     if (range == 0) range = c->subfp_len;
     st = c->join_ev.wait_or_create();                                 // (the scratch is the previous call's until then)
@@ -984,8 +991,23 @@ OSStatus join_keys_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, ui
     if (c->append_event.ev) LBAD_HIP(hipStreamWaitEvent(stream, c->append_event, 0));
     if (q != c && q->append_event.ev) LBAD_HIP(hipStreamWaitEvent(stream, q->append_event, 0));
     LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)capacity * sizeof(unsigned long long), stream));
+    if (lags) LBAD_HIP(hipMemsetAsync(lags, 0, (size_t)capacity * sizeof(int32_t), stream));
     if (c->count == 0) {
         LBAD_HIP(hipMemsetAsync(offsets, 0, (size_t)(count + 1) * sizeof(unsigned long long), stream));
+    } else if (ragged) {
+        st = c->d_join_scratch.reserve(join_ragged_scratch_bytes(c->count, chunk));
+        if (st != noErr) return st;
+        JoinRaggedCall call;
+        call.d_recs = c->d_recs; call.d_off = c->d_off; call.n_entries = c->count;
+        call.d_qrecs = q->d_recs; call.d_qoff = q->d_off; call.q_ne_max = q->ne_max;
+        call.subfp_len = c->subfp_len; call.range = range; call.threshold = threshold; call.skip = skip != 0;
+        call.capacity = capacity; call.index_base = index_base; call.d_keys = keys; call.d_lags = lags; call.stream = stream;
+        hipError_t e = hipSuccess;
+        for (uint64_t r0 = 0; r0 < count && e == hipSuccess; r0 += chunk) {
+            const uint32_t rows = (uint32_t)(count - r0 < chunk ? count - r0 : chunk);
+            e = launch_join_ragged_chunk(call, c->d_join_scratch, (uint32_t)chunk, first + r0, rows, r0 == 0 ? 1u : 0u, offsets + r0);
+        }
+        st = hip_status(e, "ragged join", __LINE__);
     } else {
         st = c->d_join_scratch.reserve(join_scratch_bytes(c->count, chunk));
         if (st != noErr) return st;
@@ -1007,22 +1029,24 @@ OSStatus join_keys_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, ui
     return st != noErr ? st : (rec != noErr ? rec : rec2);
 }
 
-// host-returning form: keys and offsets in ONE block of the corpus' key buffer on the null stream, one read-back, then decoded
+// host-returning form: keys and offsets (and the ragged join's lags behind them, where they are wanted) in ONE block of the
+// corpus' key buffer on the null stream, one read-back, then decoded
 OSStatus join_host_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, uint64_t first, uint64_t count, uint32_t range,
-                        float threshold, uint32_t skip, uint64_t capacity, SInt64* out_rows, SInt64* out_idx, Float32* out_scores,
-                        UInt64* out_total) {
+                        float threshold, uint32_t skip, uint64_t capacity, bool ragged, SInt64* out_rows, SInt64* out_idx,
+                        Float32* out_scores, SInt32* out_lags, UInt64* out_total) {
     if (!c || !q || !out_rows || !out_idx || !out_scores || !out_total || !join_args_ok(first, count, threshold, capacity, 0))
         return kLBAudioDetectiveArgumentInvalid;
     if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
     uint64_t chunk = 0;
-    OSStatus st = join_plan(c, q, first, count, 0, &chunk);           // (a refused call reserves nothing)
+    OSStatus st = join_plan(c, q, first, count, 0, ragged, &chunk);   // (a refused call reserves nothing)
     if (st != noErr) return st;
     st = c->topk_ev.wait();             // (the key buffer is the previous top-K or threshold call's until then)
-    const size_t words = (size_t)capacity + count + 1;
+    const size_t words = (size_t)capacity + count + 1 + (out_lags ? (capacity + 1) / 2 : 0);
     if (st == noErr) st = c->d_topk_keys.reserve(words);
     if (st != noErr) return st;
     unsigned long long* d_keys = c->d_topk_keys;
-    st = join_keys_impl(c, q, first, count, range, threshold, skip, capacity, 0, d_keys, d_keys + capacity, nullptr);
+    int32_t* d_lags = out_lags ? reinterpret_cast<int32_t*>(d_keys + capacity + count + 1) : nullptr;
+    st = join_keys_impl(c, q, first, count, range, threshold, skip, capacity, 0, ragged, d_keys, d_lags, d_keys + capacity, nullptr);
     if (st != noErr) {
         (void)hipStreamSynchronize(nullptr);       // whatever was launched has left the key buffer before its next user
         return st;
@@ -1030,8 +1054,10 @@ OSStatus join_host_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, ui
     std::vector<unsigned long long> host(words);
     LBAD_HIP(hipMemcpy(host.data(), d_keys, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     const unsigned long long* off = host.data() + capacity;
+    const int32_t* lags = reinterpret_cast<const int32_t*>(off + count + 1);
     uint64_t row = 0;
     for (uint64_t at = 0; at < capacity; ++at) {
+        if (out_lags) out_lags[at] = at < off[count] ? lags[at] : 0;
         if (at >= off[count]) {
             out_rows[at] = -1; out_idx[at] = -1; out_scores[at] = 0.0f;
             continue;
@@ -1103,8 +1129,30 @@ OSStatus LBAudioDetectiveCorpusJoinThresholdKeysDevice(LBAudioDetectiveCorpusRef
                                                        void* outOffsets, void* inStream) {
     LBAD_GUARD_BEGIN
     return lbad::join_keys_impl(inCorpus, inQueries, inFirstQuery, inQueryCount, inRange, inThreshold, inSkipSameIndex, inCapacity,
-                                inIndexBase, static_cast<unsigned long long*>(outKeys), static_cast<unsigned long long*>(outOffsets),
-                                static_cast<hipStream_t>(inStream));
+                                inIndexBase, false, static_cast<unsigned long long*>(outKeys), nullptr,
+                                static_cast<unsigned long long*>(outOffsets), static_cast<hipStream_t>(inStream));
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusJoinRaggedThresholdKeysDevice(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveCorpusRef inQueries,
+                                                             UInt64 inFirstQuery, UInt64 inQueryCount, UInt32 inRange,
+                                                             Float32 inThreshold, UInt32 inSkipSameIndex, UInt64 inCapacity,
+                                                             UInt64 inIndexBase, void* outKeys, void* outLags, void* outOffsets,
+                                                             void* inStream) {
+    LBAD_GUARD_BEGIN
+    return lbad::join_keys_impl(inCorpus, inQueries, inFirstQuery, inQueryCount, inRange, inThreshold, inSkipSameIndex, inCapacity,
+                                inIndexBase, true, static_cast<unsigned long long*>(outKeys), static_cast<int32_t*>(outLags),
+                                static_cast<unsigned long long*>(outOffsets), static_cast<hipStream_t>(inStream));
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveCorpusJoinRaggedThreshold(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveCorpusRef inQueries,
+                                                   UInt64 inFirstQuery, UInt64 inQueryCount, UInt32 inRange, Float32 inThreshold,
+                                                   UInt32 inSkipSameIndex, UInt64 inCapacity, SInt64* outQueryIndices,
+                                                   SInt64* outEntryIndices, Float32* outScores, SInt32* outLags, UInt64* outTotal) {
+    LBAD_GUARD_BEGIN
+    return lbad::join_host_impl(inCorpus, inQueries, inFirstQuery, inQueryCount, inRange, inThreshold, inSkipSameIndex, inCapacity,
+                                true, outQueryIndices, outEntryIndices, outScores, outLags, outTotal);
     LBAD_GUARD_END
 }
 
@@ -1114,7 +1162,7 @@ OSStatus LBAudioDetectiveCorpusJoinThreshold(LBAudioDetectiveCorpusRef inCorpus,
                                              UInt64* outTotal) {
     LBAD_GUARD_BEGIN
     return lbad::join_host_impl(inCorpus, inQueries, inFirstQuery, inQueryCount, inRange, inThreshold, inSkipSameIndex, inCapacity,
-                                outQueryIndices, outEntryIndices, outScores, outTotal);
+                                false, outQueryIndices, outEntryIndices, outScores, nullptr, outTotal);
     LBAD_GUARD_END
 }
 

@@ -350,6 +350,33 @@ uint64_t join_chunk_rows(uint64_t n_entries, uint64_t limit_bytes);
 // first_chunk starts it at 0.  Five launches on the call's stream, nothing visits the host.
 hipError_t launch_join_chunk(const JoinCall& call, void* d_scratch, uint32_t chunk_rows_max, uint64_t first_row, uint32_t rows,
                              uint32_t first_chunk, unsigned long long* out_offsets);
+// the two scans between a join's count and scatter kernels: counts[row][entry tile] -> tile_at (offsets inside the row), row_base
+// and the caller's offsets on top of *state (the total carried between chunks); shared with k_join_ragged.hip
+void launch_join_scans(const uint32_t* counts, uint64_t etiles, uint32_t rows, uint32_t* tile_at, unsigned long long* row_base,
+                       unsigned long long* state, uint32_t first_chunk, unsigned long long* out_offsets, hipStream_t stream);
+
+// ragged corpus join (k_join_ragged.hip): the same CSR for two RAGGED corpora of one sub-fingerprint length; the score of a pair
+// is the ragged scan's (the shorter slides along the longer), and each match's signed lag goes to d_lags where that is given.
+struct JoinRaggedCall {
+    const uint4* d_recs = nullptr;       // the scanned corpus: records, record positions, entries
+    const uint32_t* d_off = nullptr;
+    uint64_t n_entries = 0;
+    const uint4* d_qrecs = nullptr;      // the rows' corpus
+    const uint32_t* d_qoff = nullptr;
+    uint32_t q_ne_max = 0;               // its longest entry (<= LBAD_JOIN_RAGGED_MAX_SUBFINGERPRINTS, as the scanned corpus')
+    uint32_t subfp_len = 0, range = 0;
+    float threshold = 0.0f;
+    bool skip = false;
+    uint64_t capacity = 0, index_base = 0;
+    unsigned long long* d_keys = nullptr;    // `capacity` slots, zeroed by the caller
+    int32_t* d_lags = nullptr;               // optional: `capacity` slots, zeroed by the caller
+    hipStream_t stream = nullptr;
+};
+// as join_scratch_bytes / join_chunk_rows / launch_join_chunk (four launches: no row blocks are built)
+size_t join_ragged_scratch_bytes(uint64_t n_entries, uint64_t rows);
+uint64_t join_ragged_chunk_rows(uint64_t n_entries, uint64_t limit_bytes);
+hipError_t launch_join_ragged_chunk(const JoinRaggedCall& call, void* d_scratch, uint32_t chunk_rows_max, uint64_t first_row,
+                                    uint32_t rows, uint32_t first_chunk, unsigned long long* out_offsets);
 
 // removal (k_remove.hip): the index of a call -- which entries go and where the others land -- and the moves of a chunk.
 // The index block of a corpus of `count` entries (remove_index_layout places it in d_block, 16-byte aligned, `words` words):

@@ -661,6 +661,47 @@ OSStatus LBAudioDetectiveCorpusJoinRaggedThreshold(LBAudioDetectiveCorpusRef inC
                                                    UInt64 inFirstQuery, UInt64 inQueryCount, UInt32 inRange, Float32 inThreshold,
                                                    UInt32 inSkipSameIndex, UInt64 inCapacity, SInt64* outQueryIndices,
                                                    SInt64* outEntryIndices, Float32* outScores, SInt32* outLags, UInt64* outTotal);
+/* Occurrences: every place ONE query -- a long recording -- matches a RAGGED corpus, found on the device.  Every other corpus
+ * call folds the sliding compare into one number per entry, max over the offsets; these calls return the cells themselves.  For
+ * entry j the cells are the n1 - n2 + 1 values q_o that LBAudioDetectiveCorpusMatchProfile(inCorpus, inQuery, inRange, j) returns,
+ * bit for bit: fingerprint1 is the entry when the query is shorter (lag +o), the query otherwise (equal lengths included, lag
+ * -o), q_o = fl(fl(sum of the steps' hits / possible, in step order from +0) / n2), possible from fingerprint1's pairs inside the
+ * range.  A cell matches when q_o >= inThreshold as Float32; with inPeaksOnly != 0 it must also be a local peak of its own
+ * profile, (o == 0 or q_o > q_(o-1)) and (o == last or q_o >= q_(o+1)) as Float32 -- a plateau reports its first cell only, cells
+ * outside the profile do not exist, and a neighbour below the threshold still takes part in the test.
+ * outKeys receives inCapacity 64-bit keys, q_o bits << 32 | 0xFFFFFFFF - (inIndexBase + j), the key format of every other call;
+ * outLags (may be NULL) inCapacity SInt32 signed lags; outCount one UInt64, the TRUE number of matching cells, never cut -- a
+ * count above inCapacity is no error.  The matches lie in ascending entry index and inside an entry in ascending offset o (with
+ * the query as fingerprint1 that is descending lag); slot p < min(count, capacity) holds match p, every slot behind a zero key
+ * and lag 0.  Keys and count do not depend on outLags, launch order, grid or chunking.  Shards that hold contiguous index ranges
+ * merge by concatenating in rank order and adding counts.
+ * The corpus is ragged (a uniform corpus is kLBAudioDetectiveArgumentInvalid: gather it into a ragged one) with no entry above
+ * LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS; the query has the corpus' sub-fingerprint length and 1 .. 2^31 - 1 sub-
+ * fingerprints; inThreshold is finite and > 0 (above 1 is legal and matches nothing), 1 <= inCapacity <= 2^31, inIndexBase +
+ * entries <= 2^32, inRange == 0 means the sub-fingerprint length; NULL handles and pointers but outLags are
+ * kLBAudioDetectiveArgumentInvalid.  What needs no handle is refused first, then kLBAudioDetectiveDeviceUnavailable, then what
+ * needs the corpus.  An empty corpus gives count 0 and zero keys and lags.
+ * The KeysDevice forms write to device pointers, asynchronously on inStream, which they never await, and wait ON THE DEVICE
+ * for the corpus' latest append.  The Packed form takes the query as inSubfingerprints x LBAD_PACKED_BYTES bytes on the device
+ * (4-byte aligned, bits at or above the sub-fingerprint length ignored; nothing of it visits the host); its keys, lags and count
+ * equal the handle form's bit for bit.  LBAudioDetectiveCorpusQueryOccurrences returns (index, score, lag) of the first
+ * min(count, inCapacity) matches to host arrays of inCapacity elements, then -1 / 0 / 0, and the count.
+ * The scratch is the corpus' join scratch, under LBAudioDetectiveCorpusSetJoinScratchLimit: the entries go through in chunks of
+ * a multiple of 64 with nothing visiting the host in between, 24 + entries x (16 + 8 x tiles) + ceil(entries / 64) x
+ * ceil(tiles / 4) x 4 bytes for a chunk, tiles = ceil(most offsets of any pair / 126); a limit below one chunk of 64 entries is
+ * kLBAudioDetectiveArgumentInvalid at the call. */
+#define LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS 1024
+OSStatus LBAudioDetectiveCorpusQueryOccurrencesKeysDevice(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                                          UInt32 inRange, Float32 inThreshold, UInt32 inPeaksOnly, UInt64 inCapacity,
+                                                          UInt64 inIndexBase, void* outKeys, void* outLags, void* outCount,
+                                                          void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryPackedOccurrencesKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQuery,
+                                                                UInt32 inSubfingerprints, UInt32 inRange, Float32 inThreshold,
+                                                                UInt32 inPeaksOnly, UInt64 inCapacity, UInt64 inIndexBase,
+                                                                void* outKeys, void* outLags, void* outCount, void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryOccurrences(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                                UInt32 inRange, Float32 inThreshold, UInt32 inPeaksOnly, UInt64 inCapacity,
+                                                SInt64* outIndices, Float32* outScores, SInt32* outLags, UInt64* outCount);
 /* Removal: entries taken out of a corpus on the device, the other half of the corpus life cycle -- the take-down of one
  * recording, or the action behind a join's duplicate pairs.  Both forms, both kinds of corpus (uniform of any shape, ragged):
  * the named entries go, the others keep their relative order and close up -- the entry at old index i gets the new index

@@ -194,6 +194,12 @@ _SIGNATURES = {
                                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusJoinRaggedThreshold": (OSStatus, [Ref, Ref, UInt64, UInt64, UInt32, Float32, UInt32, UInt64, _P(SInt64),
                                                              _P(SInt64), _P(Float32), _P(SInt32), _P(UInt64)]),
+    "LBAudioDetectiveCorpusQueryOccurrencesKeysDevice": (OSStatus, [Ref, Ref, UInt32, Float32, UInt32, UInt64, UInt64, C.c_void_p, C.c_void_p,
+                                                                    C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusQueryPackedOccurrencesKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, Float32, UInt32, UInt64, UInt64,
+                                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusQueryOccurrences": (OSStatus, [Ref, Ref, UInt32, Float32, UInt32, UInt64, _P(SInt64), _P(Float32), _P(SInt32),
+                                                          _P(UInt64)]),
     "LBAudioDetectiveCorpusRemoveIndices": (OSStatus, [Ref, _P(UInt64), UInt64, _P(UInt32), _P(UInt64)]),
     "LBAudioDetectiveCorpusRemoveKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, _P(UInt64), C.c_void_p]),
     "LBAudioDetectiveCorpusSetRemoveScratchLimit": (OSStatus, [Ref, UInt64]),

@@ -896,6 +896,53 @@ class Corpus:
         m = min(int(total.value), capacity)
         return rows[:m].copy(), idx[:m].copy(), sc[:m].copy(), lags[:m].copy(), int(total.value)
 
+    # ---- occurrences: every place ONE query (a long recording) matches a ragged corpus -- each cell (entry, sliding offset) of
+    # match_profile's values that is >= threshold, with peaks=True only the local peaks of every profile; entries ascending,
+    # offsets ascending inside an entry.  The total is always the true number of matching cells.
+    def query_occurrences(self, fp: Fingerprint, threshold: float, capacity: int, peaks: bool = False, range_: int = 0):
+        """LBAudioDetectiveCorpusQueryOccurrences: (indices int64[m], scores float32[m], lags int32[m], total) with m = min(total,
+        capacity).  lags[p] is +offset when the entry is longer than the query, -offset otherwise."""
+        idx = np.full(max(1, capacity), -1, dtype=np.int64)
+        sc = np.zeros(max(1, capacity), dtype=np.float32)
+        lags = np.zeros(max(1, capacity), dtype=np.int32)
+        total = N.UInt64(0)
+        _check(self._L.LBAudioDetectiveCorpusQueryOccurrences(self._ref, fp._ref, range_, threshold, int(bool(peaks)), capacity,
+                                                             idx.ctypes.data_as(C.POINTER(N.SInt64)),
+                                                             sc.ctypes.data_as(C.POINTER(N.Float32)),
+                                                             lags.ctypes.data_as(C.POINTER(N.SInt32)), C.byref(total)),
+               "CorpusQueryOccurrences")
+        m = min(int(total.value), capacity)
+        return idx[:m].copy(), sc[:m].copy(), lags[:m].copy(), int(total.value)
+
+    def query_occurrences_keys_device(self, fp: Fingerprint, threshold: float, capacity: int, peaks: bool = False, range_: int = 0,
+                                      index_base: int = 0, keys_out=None, lags_out=None, count_out=None, want_lags: bool = True,
+                                      stream=None):
+        """LBAudioDetectiveCorpusQueryOccurrencesKeysDevice: (keys int64 [capacity], lags int32 [capacity] or None, count int64
+        [1]) on the device, asynchronously on `stream`; slot p holds match p (global entry index = index_base + local), zero keys
+        and lags behind min(count, capacity).  want_lags=False (and no lags_out) passes NULL: keys and count are the same.
+        Decode with decode_occurrence_keys."""
+        keys_out, lags_out, count_out = _occurrences_out(capacity, keys_out, lags_out, count_out, want_lags, "cuda")
+        _check(self._L.LBAudioDetectiveCorpusQueryOccurrencesKeysDevice(
+            self._ref, fp._ref, range_, threshold, int(bool(peaks)), capacity, index_base, _dev_ptr(keys_out),
+            _dev_ptr(lags_out) if lags_out is not None else None, _dev_ptr(count_out), _stream_ptr(stream)),
+            "CorpusQueryOccurrencesKeysDevice")
+        return keys_out, lags_out, count_out
+
+    def query_packed_occurrences_keys_device(self, packed, per_query: int, threshold: float, capacity: int, peaks: bool = False,
+                                             range_: int = 0, index_base: int = 0, keys_out=None, lags_out=None, count_out=None,
+                                             want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedOccurrencesKeysDevice: query_occurrences_keys_device's result for ONE query of
+        per_query packed sub-fingerprints already on the device (what Detective.fingerprint_clips_device writes); nothing
+        visits the host."""
+        _packed_ok(packed, 1, per_query)
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        keys_out, lags_out, count_out = _occurrences_out(capacity, keys_out, lags_out, count_out, want_lags, dev)
+        _check(self._L.LBAudioDetectiveCorpusQueryPackedOccurrencesKeysDevice(
+            self._ref, _dev_ptr(packed), per_query, range_, threshold, int(bool(peaks)), capacity, index_base, _dev_ptr(keys_out),
+            _dev_ptr(lags_out) if lags_out is not None else None, _dev_ptr(count_out), _stream_ptr(stream)),
+            "CorpusQueryPackedOccurrencesKeysDevice")
+        return keys_out, lags_out, count_out
+
     def set_join_scratch_limit(self, n_bytes: int):
         """bytes of device memory the join's scratch may take, and thereby the rows per chunk; 0 restores the default"""
         _check(self._L.LBAudioDetectiveCorpusSetJoinScratchLimit(self._ref, n_bytes), "CorpusSetJoinScratchLimit")
@@ -1152,6 +1199,23 @@ def _threshold_out(n: int, capacity: int, keys_out, counts_out, lags_out, want_l
     return keys_out, counts_out, lags_out
 
 
+def _occurrences_out(capacity: int, keys_out, lags_out, count_out, want_lags: bool, device):
+    """the outputs of an occurrences call on the device: made where they are missing, checked where they are given"""
+    if keys_out is None or count_out is None or (want_lags and lags_out is None):
+        import torch
+        if keys_out is None:
+            keys_out = torch.empty(max(1, capacity), dtype=torch.int64, device=device)
+        if count_out is None:
+            count_out = torch.empty(1, dtype=torch.int64, device=device)
+        if want_lags and lags_out is None:
+            lags_out = torch.empty(max(1, capacity), dtype=torch.int32, device=device)
+    _out_ok(keys_out, capacity, "keys_out")
+    _out_ok(count_out, 1, "count_out")
+    if lags_out is not None:
+        _out_ok(lags_out, capacity, "lags_out")
+    return keys_out, lags_out, count_out
+
+
 def identify_clips_device(det: "Detective", corpus: "Corpus", clips, k: int = 1, aligned: bool = False, range_: int = 0, stream=None):
     """Clips on the device -> their k best corpus matches on the device: Detective.fingerprint_clips_device, then
     Corpus.query_packed_topk_keys_device on its output, on ONE stream with nothing in between (no handle, no copy to the host,
@@ -1329,6 +1393,18 @@ def decode_threshold_keys(row, count=None):
     k = np.asarray(row.cpu().numpy() if hasattr(row, "cpu") else row, dtype=np.int64).astype(np.uint64).reshape(-1)
     k = k[k != 0] if count is None else k[:min(int(count), len(k))]
     return (0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32)
+
+
+def decode_occurrence_keys(keys, lags=None, count=None):
+    """(indices int64[m], scores float32[m], lags int32[m] or None) of an occurrences call's keys (any int64 sequence), m =
+    min(count, len(keys)) -- or, without a count, the keys in front of the zero padding.  The order is the call's."""
+    k = np.asarray(keys.cpu().numpy() if hasattr(keys, "cpu") else keys, dtype=np.int64).astype(np.uint64).reshape(-1)
+    m = int(np.count_nonzero(k)) if count is None else min(int(count), len(k))
+    k = k[:m]
+    lg = None
+    if lags is not None:
+        lg = np.asarray(lags.cpu().numpy() if hasattr(lags, "cpu") else lags, dtype=np.int32).reshape(-1)[:m].copy()
+    return ((0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32), lg)
 
 
 def decode_join_keys(keys, offsets, first: int = 0):

@@ -942,7 +942,7 @@ OSStatus threshold_host_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFi
 
 
 // ---- corpus join: the entries of `q` as queries against `c`, every pair at or above the threshold as CSR (k_join.hip) --------
-constexpr uint64_t kJoinScratchDefault = 256ull << 20;
+// (kJoinScratchDefault: internal.hpp, shared with api_occurrences.cpp)
 
 // what needs neither handle nor device
 bool join_args_ok(uint64_t first, uint64_t count, float threshold, uint64_t capacity, uint64_t index_base) {

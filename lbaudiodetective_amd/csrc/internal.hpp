@@ -378,6 +378,39 @@ uint64_t join_ragged_chunk_rows(uint64_t n_entries, uint64_t limit_bytes);
 hipError_t launch_join_ragged_chunk(const JoinRaggedCall& call, void* d_scratch, uint32_t chunk_rows_max, uint64_t first_row,
                                     uint32_t rows, uint32_t first_chunk, unsigned long long* out_offsets);
 
+// occurrences (k_occurrences.hip): every cell (entry, sliding offset) of ONE query against a ragged corpus whose quotient q_o --
+// LBAudioDetectiveCorpusMatchProfile's value -- is >= threshold (with `peaks`: and a local peak of its profile), in (entry,
+// offset) order: keys and, where given, signed lags to the slots below the capacity.
+struct OccurrencesCall {
+    const uint4* d_recs = nullptr;       // the corpus: records, record positions
+    const uint32_t* d_off = nullptr;
+    uint32_t ne_min = 0, ne_max = 0;     // its shortest and longest entry (ne_max <= LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS)
+    uint32_t subfp_len = 0, range = 0;
+    const uint32_t* d_qwords = nullptr;  // the query as build_align_query's ragged form, 16-byte aligned, on the device
+    uint32_t n_query = 0;
+    uint64_t tiles = 0;                  // occurrences_tiles(n_query, ne_min, ne_max)
+    float threshold = 0.0f;
+    bool peaks = false;
+    uint64_t capacity = 0, index_base = 0;
+    unsigned long long* d_keys = nullptr;    // `capacity` slots, zeroed by the caller
+    int32_t* d_lags = nullptr;               // optional: `capacity` slots, zeroed by the caller
+    hipStream_t stream = nullptr;
+};
+uint32_t occurrences_block_entries();    // entries a chunk is a whole number of
+// tiles per entry: a bound over every pair of the call
+uint64_t occurrences_tiles(uint32_t n_query, uint32_t ne_min, uint32_t ne_max);
+// scratch of a chunk of `entries` entries, the entries a chunk may have under a limit (0: the limit is too small for one block of
+// entries), and the LDS of a workgroup
+size_t occurrences_scratch_bytes(uint64_t entries, uint64_t tiles);
+uint64_t occurrences_chunk_entries(uint64_t tiles, uint64_t limit_bytes);
+size_t occurrences_lds_bytes(uint32_t n_query, uint32_t ne_max);
+// one chunk: `entries` entries from `first_entry`.  d_scratch: occurrences_scratch_bytes(chunk_entries_max, tiles) bytes, the SAME
+// block and chunk_entries_max for every chunk of a call -- its first word carries the total from chunk to chunk (first_chunk
+// starts it at 0) and holds the call's total behind the last chunk.  Four launches on the call's stream, nothing visits the host.
+hipError_t launch_occurrences_chunk(const OccurrencesCall& call, void* d_scratch, uint64_t chunk_entries_max, uint64_t first_entry,
+                                    uint64_t entries, uint32_t first_chunk);
+constexpr uint64_t kJoinScratchDefault = 256ull << 20;   // LBAudioDetectiveCorpusSetJoinScratchLimit's 0
+
 // removal (k_remove.hip): the index of a call -- which entries go and where the others land -- and the moves of a chunk.
 // The index block of a corpus of `count` entries (remove_index_layout places it in d_block, 16-byte aligned, `words` words):
 // head (entries kept, lowest removed index or 0xFFFFFFFF, two zero words), tiles + 1 tile offsets (kept entries below the

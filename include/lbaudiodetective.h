@@ -702,6 +702,51 @@ OSStatus LBAudioDetectiveCorpusQueryPackedOccurrencesKeysDevice(LBAudioDetective
 OSStatus LBAudioDetectiveCorpusQueryOccurrences(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
                                                 UInt32 inRange, Float32 inThreshold, UInt32 inPeaksOnly, UInt64 inCapacity,
                                                 SInt64* outIndices, Float32* outScores, SInt32* outLags, UInt64* outCount);
+/* Recording scores: how well EVERY entry of a RAGGED corpus matches ONE query of any length -- a long recording above all --
+ * and where, with the occurrences pass' pair loop: a pair whose entry is the shorter side takes as many steps as the entry has
+ * sub-fingerprints, not as many as the query (the ragged scan behind LBAudioDetectiveCorpusScoresDevice was built for queries of
+ * about a hundred sub-fingerprints).  The cells of the occurrences calls above are folded per entry on the device.
+ * SCORES: outScores[j] is, bit for bit, what LBAudioDetectiveCorpusScoresDevice writes for entry j with the same query and
+ * range: the largest cell q_o of the pair's profile (cells are >= +0, which is the scan's max(0, .)).
+ * LAGS: outLags[j] (may be NULL; the scores do not depend on it) is what LBAudioDetectiveCorpusAlignKeysDevice gives for that
+ * entry: the LOWEST offset o whose cell equals the score, +o when the entry is longer than the query and -o otherwise (equal
+ * lengths included).  A score of 0 means every cell is 0: the lag is 0.
+ * LBAudioDetectiveCorpusRecordingScoresDevice / ...RecordingPackedScoresDevice write one Float32 and one SInt32 per entry to
+ * device pointers.  The key forms run the same pass into the corpus' scores scratch, then the selections of the top-K and
+ * threshold queries as they are, then gather the selected entries' lags:
+ * ...QueryPackedRecordingTopKKeysDevice writes inK keys (and lags) that equal LBAudioDetectiveCorpusQueryPackedTopKKeysDevice's
+ * with one query -- K = 1 is the top-1 query's answer --, ...QueryPackedRecordingThresholdKeysDevice inCapacity keys (and lags)
+ * and one UInt64 count that equal LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice's with one query; a zero key has lag 0.
+ * LBAudioDetectiveCorpusQueryRecordingTopK returns (index, score, lag) of the inK best entries to host arrays of inK elements
+ * (outLags may be NULL), unused slots -1 / 0 / 0, and *outCount = min(inK, entries with score > 0).
+ * The restrictions are the occurrences calls': the corpus is ragged (a uniform corpus is kLBAudioDetectiveArgumentInvalid) with
+ * no entry above LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS; the query has the corpus' sub-fingerprint length and 1 .. 2^31 - 1
+ * sub-fingerprints, short ones included; inRange == 0 means the sub-fingerprint length; 1 <= inK <= LBAD_TOPK_MAX; inThreshold
+ * is finite and > 0, 1 <= inCapacity <= 2^31, inIndexBase + entries <= 2^32; NULL handles and pointers but outLags are
+ * kLBAudioDetectiveArgumentInvalid.  What needs no handle is refused first, then kLBAudioDetectiveDeviceUnavailable, then what
+ * needs the corpus.  An empty corpus is noErr: the scores forms write nothing, the key forms zero keys, lags and count.
+ * The Device forms are asynchronous on inStream, which they never await, and wait ON THE DEVICE for the corpus' latest append.
+ * The Packed forms take the query as inSubfingerprints x LBAD_PACKED_BYTES bytes on the device (4-byte aligned, bits at or above
+ * the sub-fingerprint length ignored; nothing of it visits the host); packed, handle and host forms agree bit for bit.  Bound
+ * pruning and LBAudioDetectiveCorpusSetKernelVariant do not apply.  Results do not depend on launch order, grid or chunking.
+ * The scratch is the corpus' join scratch, under LBAudioDetectiveCorpusSetJoinScratchLimit: the entries go through in chunks of
+ * a multiple of 64 with nothing visiting the host in between, entries x tiles x 8 bytes for a chunk, tiles = ceil(most offsets
+ * of any pair / 126); a limit below one chunk of 64 entries is kLBAudioDetectiveArgumentInvalid at the call. */
+OSStatus LBAudioDetectiveCorpusRecordingScoresDevice(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                                     UInt32 inRange, Float32* outScores, SInt32* outLags, void* inStream);
+OSStatus LBAudioDetectiveCorpusRecordingPackedScoresDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQuery,
+                                                           UInt32 inSubfingerprints, UInt32 inRange, Float32* outScores,
+                                                           SInt32* outLags, void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryRecordingTopK(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                                  UInt32 inRange, UInt32 inK, SInt64* outIndices, Float32* outScores,
+                                                  SInt32* outLags, UInt32* outCount);
+OSStatus LBAudioDetectiveCorpusQueryPackedRecordingTopKKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQuery,
+                                                                  UInt32 inSubfingerprints, UInt32 inRange, UInt32 inK,
+                                                                  UInt64 inIndexBase, void* outKeys, void* outLags, void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryPackedRecordingThresholdKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQuery,
+                                                                       UInt32 inSubfingerprints, UInt32 inRange, Float32 inThreshold,
+                                                                       UInt64 inCapacity, UInt64 inIndexBase, void* outKeys,
+                                                                       void* outCount, void* outLags, void* inStream);
 /* Removal: entries taken out of a corpus on the device, the other half of the corpus life cycle -- the take-down of one
  * recording, or the action behind a join's duplicate pairs.  Both forms, both kinds of corpus (uniform of any shape, ragged):
  * the named entries go, the others keep their relative order and close up -- the entry at old index i gets the new index

@@ -943,6 +943,88 @@ class Corpus:
             "CorpusQueryPackedOccurrencesKeysDevice")
         return keys_out, lags_out, count_out
 
+    # ---- recording scores: every entry's score and lag for ONE query of any length (a long recording above all) against a
+    # ragged corpus, with the occurrences pass' pair loop (n_entry steps per pass); scores_device's scores and
+    # align_keys_device's lags, bit for bit
+    def recording_scores_device(self, fp: Fingerprint = None, packed=None, per_query: int = 0, range_: int = 0, scores_out=None,
+                                lags_out=None, want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusRecordingScoresDevice (fp) / ...RecordingPackedScoresDevice (packed: per_query packed
+        sub-fingerprints already on the device): (scores float32 [len(self)], lags int32 [len(self)] or None) on the device,
+        asynchronously on `stream`.  lags[j] is +offset when entry j is longer than the query, -offset otherwise: the lowest
+        offset that reaches scores[j].  want_lags=False (and no lags_out) passes NULL: the scores are the same."""
+        if (fp is None) == (packed is None):
+            raise ValueError("give either fp or packed")
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        n = len(self)
+        if scores_out is None or (want_lags and lags_out is None):
+            import torch
+            if scores_out is None:
+                scores_out = torch.empty(max(1, n), dtype=torch.float32, device=dev)[:n]
+            if want_lags and lags_out is None:
+                lags_out = torch.empty(max(1, n), dtype=torch.int32, device=dev)[:n]
+        _out_ok(scores_out, n, "scores_out")
+        if lags_out is not None:
+            _out_ok(lags_out, n, "lags_out")
+        lp = _dev_ptr(lags_out) if lags_out is not None else None
+        if fp is not None:
+            _check(self._L.LBAudioDetectiveCorpusRecordingScoresDevice(self._ref, fp._ref, range_, _dev_ptr(scores_out), lp,
+                                                                      _stream_ptr(stream)), "CorpusRecordingScoresDevice")
+        else:
+            _packed_ok(packed, 1, per_query)
+            _check(self._L.LBAudioDetectiveCorpusRecordingPackedScoresDevice(self._ref, _dev_ptr(packed), per_query, range_,
+                                                                            _dev_ptr(scores_out), lp, _stream_ptr(stream)),
+                   "CorpusRecordingPackedScoresDevice")
+        return scores_out, lags_out
+
+    def query_recording_topk(self, fp: Fingerprint, k: int, range_: int = 0):
+        """LBAudioDetectiveCorpusQueryRecordingTopK: (indices int64[n], scores float32[n], lags int32[n]) of the k best entries,
+        query_topk's order, n = min(k, entries scoring above 0)."""
+        idx = np.full(max(1, k), -1, dtype=np.int64)
+        sc = np.zeros(max(1, k), dtype=np.float32)
+        lags = np.zeros(max(1, k), dtype=np.int32)
+        cnt = N.UInt32(0)
+        _check(self._L.LBAudioDetectiveCorpusQueryRecordingTopK(self._ref, fp._ref, range_, k, idx.ctypes.data_as(C.POINTER(N.SInt64)),
+                                                               sc.ctypes.data_as(C.POINTER(N.Float32)),
+                                                               lags.ctypes.data_as(C.POINTER(N.SInt32)), C.byref(cnt)),
+               "CorpusQueryRecordingTopK")
+        return idx[:cnt.value].copy(), sc[:cnt.value].copy(), lags[:cnt.value].copy()
+
+    def query_packed_recording_topk_keys_device(self, packed, per_query: int, k: int, range_: int = 0, index_base: int = 0,
+                                                keys_out=None, lags_out=None, want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedRecordingTopKKeysDevice: (keys int64 [k], lags int32 [k] or None) on the device for ONE
+        query of per_query packed sub-fingerprints already on the device: query_packed_topk_keys_device's keys and aligned lags
+        (descending, 0-padded; a zero key has lag 0).  Asynchronous on `stream`, nothing visits the host."""
+        _packed_ok(packed, 1, per_query)
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        if keys_out is None or (want_lags and lags_out is None):
+            import torch
+            if keys_out is None:
+                keys_out = torch.empty(max(1, k), dtype=torch.int64, device=dev)
+            if want_lags and lags_out is None:
+                lags_out = torch.empty(max(1, k), dtype=torch.int32, device=dev)
+        _out_ok(keys_out, k, "keys_out")
+        if lags_out is not None:
+            _out_ok(lags_out, k, "lags_out")
+        _check(self._L.LBAudioDetectiveCorpusQueryPackedRecordingTopKKeysDevice(
+            self._ref, _dev_ptr(packed), per_query, range_, k, index_base, _dev_ptr(keys_out),
+            _dev_ptr(lags_out) if lags_out is not None else None, _stream_ptr(stream)), "CorpusQueryPackedRecordingTopKKeysDevice")
+        return keys_out, lags_out
+
+    def query_packed_recording_threshold_keys_device(self, packed, per_query: int, threshold: float, capacity: int, range_: int = 0,
+                                                     index_base: int = 0, keys_out=None, lags_out=None, count_out=None,
+                                                     want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedRecordingThresholdKeysDevice: (keys int64 [capacity], lags int32 [capacity] or None,
+        count int64 [1]) on the device for ONE query of per_query packed sub-fingerprints already on the device:
+        query_packed_threshold_keys_device's keys (ascending index, 0-padded), true count and aligned lags.  Asynchronous on
+        `stream`, nothing visits the host."""
+        _packed_ok(packed, 1, per_query)
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        keys_out, lags_out, count_out = _occurrences_out(capacity, keys_out, lags_out, count_out, want_lags, dev)
+        _check(self._L.LBAudioDetectiveCorpusQueryPackedRecordingThresholdKeysDevice(
+            self._ref, _dev_ptr(packed), per_query, range_, threshold, capacity, index_base, _dev_ptr(keys_out), _dev_ptr(count_out),
+            _dev_ptr(lags_out) if lags_out is not None else None, _stream_ptr(stream)), "CorpusQueryPackedRecordingThresholdKeysDevice")
+        return keys_out, lags_out, count_out
+
     def set_join_scratch_limit(self, n_bytes: int):
         """bytes of device memory the join's scratch may take, and thereby the rows per chunk; 0 restores the default"""
         _check(self._L.LBAudioDetectiveCorpusSetJoinScratchLimit(self._ref, n_bytes), "CorpusSetJoinScratchLimit")

@@ -411,6 +411,31 @@ hipError_t launch_occurrences_chunk(const OccurrencesCall& call, void* d_scratch
                                     uint64_t entries, uint32_t first_chunk);
 constexpr uint64_t kJoinScratchDefault = 256ull << 20;   // LBAudioDetectiveCorpusSetJoinScratchLimit's 0
 
+// recording scores (k_recording.hip): the occurrences pass' cells of ONE query against a ragged corpus folded per entry to the
+// largest cell -- the ragged scan's score, bit for bit -- and the lowest offset that reaches it as the signed lag.
+struct RecordingCall {
+    const uint4* d_recs = nullptr;       // the corpus: records, record positions
+    const uint32_t* d_off = nullptr;
+    uint32_t ne_min = 0, ne_max = 0;     // its shortest and longest entry (ne_max <= LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS)
+    uint32_t subfp_len = 0, range = 0;
+    const uint32_t* d_qwords = nullptr;  // the query as build_align_query's ragged form, 16-byte aligned, on the device
+    uint32_t n_query = 0;
+    uint64_t tiles = 0;                  // occurrences_tiles(n_query, ne_min, ne_max)
+    float* d_scores = nullptr;           // one per entry of the CORPUS (a chunk writes its own entries')
+    int32_t* d_lags = nullptr;           // optional: likewise
+    hipStream_t stream = nullptr;
+};
+// scratch of a chunk of `entries` entries (one 64-bit partial per entry and tile) and the entries a chunk may have under a limit
+// (a whole number of occurrences_block_entries(); 0: the limit is too small for one block)
+size_t recording_scratch_bytes(uint64_t entries, uint64_t tiles);
+uint64_t recording_chunk_entries(uint64_t tiles, uint64_t limit_bytes);
+// one chunk: `entries` entries from `first_entry`, every word of d_scratch written before it is read.  Two launches on the call's
+// stream, nothing visits the host.
+hipError_t launch_recording_chunk(const RecordingCall& call, void* d_scratch, uint64_t first_entry, uint64_t entries);
+// d_lags[slot] = d_entry_lags[entry that d_keys[slot] names], 0 for a zero key; n <= 2^31 slots, index_base + count <= 2^32
+hipError_t launch_recording_lag_gather(const unsigned long long* d_keys, uint64_t n, uint64_t index_base, uint64_t count,
+                                       const int32_t* d_entry_lags, int32_t* d_lags, hipStream_t stream);
+
 // removal (k_remove.hip): the index of a call -- which entries go and where the others land -- and the moves of a chunk.
 // The index block of a corpus of `count` entries (remove_index_layout places it in d_block, 16-byte aligned, `words` words):
 // head (entries kept, lowest removed index or 0xFFFFFFFF, two zero words), tiles + 1 tile offsets (kept entries below the

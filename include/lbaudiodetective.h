@@ -308,6 +308,15 @@ OSStatus LBAudioDetectiveFingerprintClipsFormat(LBAudioDetectiveRef inDetective,
  *   - register Haar / select for frames of 16, 32 or 64 bands.
  * 3 = like 2 but the register-resident 2048-point kernel instead of the streaming one (measurement). */
 OSStatus LBAudioDetectiveSetKernelVariant(LBAudioDetectiveRef inDetective, UInt32 inVariant);
+/* How the pruned stage 1 (k_rows_pruned.hip) adds a band's power terms: 0 = automatic, 1 = through LDS
+ * (frame_rows_pruned_kernel, any table the pruned kernel accepts), 2 = in the lanes that computed them
+ * (frame_rows_lanes_kernel: the default 44.1 kHz / 1024 / 32-band table at stride 64) -- ArgumentInvalid where the present
+ * settings do not have that form.  Automatic takes form 2 where it exists.  Results never depend on it.
+ * LBAudioDetectiveGetBandSumForm: the form (1 or 2) a call under the present settings would take; it reads the settings, no
+ * device.  Form 2 that was set under other settings is checked again by every call: where the settings have lost the form,
+ * the getter says 1 and the batch call returns ArgumentInvalid until the form is set anew. */
+OSStatus LBAudioDetectiveSetBandSumForm(LBAudioDetectiveRef inDetective, UInt32 inForm);
+OSStatus LBAudioDetectiveGetBandSumForm(LBAudioDetectiveRef inDetective, UInt32* outForm);
 /* Measurement knobs of the generic stage-1 kernel (the LDS-tile sizing sweep of tools/sweep_lds_tiles.py):
  * waves per workgroup (0 = automatic; a value the window size has no instance for, or that does not fit the LDS with the
  * cache as asked, falls back to the smallest workgroup without the cache) and whether the shared per-lane twiddle cache is

@@ -127,6 +127,8 @@ _SIGNATURES = {
     "LBAudioDetectiveFingerprintClips": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p]),
     "LBAudioDetectiveFingerprintClipsFormat": (OSStatus, [Ref, C.c_void_p, UInt32, UInt64, UInt64, C.c_void_p]),
     "LBAudioDetectiveSetKernelVariant": (OSStatus, [Ref, UInt32]),
+    "LBAudioDetectiveSetBandSumForm": (OSStatus, [Ref, UInt32]),
+    "LBAudioDetectiveGetBandSumForm": (OSStatus, [Ref, _P(UInt32)]),
     "LBAudioDetectiveSetScratchLimit": (OSStatus, [Ref, UInt64]),
     "LBAudioDetectiveSetStageTiming": (OSStatus, [Ref, UInt32]),
     "LBAudioDetectiveGetStageTimes": (OSStatus, [Ref, _P(Float32), _P(Float32), _P(UInt32)]),

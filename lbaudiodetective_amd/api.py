@@ -278,6 +278,16 @@ class Detective:
     def set_kernel_variant(self, variant: int):
         _check(self._L.LBAudioDetectiveSetKernelVariant(self._ref, variant), "SetKernelVariant")
 
+    def set_band_sum_form(self, form: int):
+        """Band sums of the pruned stage 1: 0 automatic, 1 through LDS, 2 in lanes (an error where the settings have no such form)."""
+        _check(self._L.LBAudioDetectiveSetBandSumForm(self._ref, form), "SetBandSumForm")
+
+    def band_sum_form(self) -> int:
+        """The form (1 or 2) a call under the present settings would take."""
+        form = N.UInt32(0)
+        _check(self._L.LBAudioDetectiveGetBandSumForm(self._ref, C.byref(form)), "GetBandSumForm")
+        return int(form.value)
+
     def set_scratch_limit(self, n_bytes: int):
         _check(self._L.LBAudioDetectiveSetScratchLimit(self._ref, n_bytes), "SetScratchLimit")
 

@@ -25,6 +25,7 @@ static void free_plan(Plan& p) { p = Plan(); }
 // stride-dependent part of a plan, host half: which specialised stage-1 kernels apply
 static void plan_kernels_host(Plan& p) {
     p.pruned_ok = rows_pruned_supported(p);
+    p.lanes_ok = p.pruned_ok && rows_lanes_supported(p);
     p.full_ok = rows_full_supported(p);
     p.stream_ok = rows_stream_supported(p);
     p.stream2_ok = rows_stream2_supported(p);
@@ -101,7 +102,7 @@ OSStatus ensure_plan(LBAudioDetective* d) {
     // multiplier and offset (w * mult + off): for rows of `bands` floats, and for the compact frame of plan.sparse
     // (off 0xFFFFFFFF: not stored); then the first word of the band's power terms in LDS (BandTable::term_at) and, one word,
     // the end of the last band's; then, from word 9 * bands on, RN(1 / divisor) and whether the short division of
-    // const_div.hpp is proven for the divisor (zero, non-integer and unchecked divisors are not)
+    // const_div.hpp is proven for the divisor (zero, non-integer and unchecked divisors are not); then rows_lanes_table's rows
     std::vector<uint32_t> tbl(11 * (size_t)p.bands);
     for (uint32_t b = 0; b < p.bands; ++b) {
         tbl[b] = p.table.lo[b];
@@ -123,6 +124,7 @@ OSStatus ensure_plan(LBAudioDetective* d) {
         tbl[10 * p.bands + b] = band_div_proven(div) ? 1u : 0u;
     }
     tbl[8 * (size_t)p.bands] = p.table.term_end;
+    rows_lanes_table(p, tbl);            // the per-task rows of frame_rows_lanes_kernel, where the table is the one it is compiled for
     st = p.d_bands.reserve(tbl.size());
     if (st != noErr) return st;
     LBAD_HIP(hipMemcpy(p.d_bands, tbl.data(), tbl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -260,6 +262,7 @@ OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, ui
     call.raw_tap = d_raw != nullptr; call.tail = tail != nullptr;
     const Stage1Choice ch = stage1_choose(p, call);
     if (ch.status != noErr || !ch.launches) return ch.status;
+    if (d->band_form == 2 && !p.lanes_ok) return kLBAudioDetectiveArgumentInvalid;   // the settings changed since the setter
     const uint64_t per = ch.per;
     StreamOrder order{d, stream};
     LBAD_HIP(order.begin());
@@ -267,7 +270,8 @@ OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, ui
     auto stage1 = [&](const void* pcm_in, uint64_t nc, float* frames_out) -> hipError_t {
         switch (ch.family) {
             case Stage1Family::Pruned:
-                return launch_rows_pruned(p, p.d_bin_const, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream, compact);
+                return launch_rows_pruned(p, p.d_bin_const, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream, compact,
+                                          d->band_form);
             case Stage1Family::Stream2: return launch_rows_stream2(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
             case Stage1Family::Full: return launch_rows_full(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
             case Stage1Family::Stream: return launch_rows_stream(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
@@ -552,6 +556,31 @@ OSStatus LBAudioDetectiveSetKernelVariant(LBAudioDetectiveRef d, UInt32 inVarian
     if (inVariant > 4) return kLBAudioDetectiveArgumentInvalid;   // 4: variant 2 with full rows between the stages (measurement)
     d->variant = inVariant;
     return noErr;
+}
+
+// the band-sum form of the pruned stage 1 under the detective's present settings (host half of a plan: no device)
+static bool band_lanes_now(LBAudioDetectiveRef d) {
+    lbad::Plan p;
+    return lbad::plan_host(p, d->format.mSampleRate, d->window, d->stride, d->bands, d->subfp_len) == noErr && p.lanes_ok;
+}
+
+OSStatus LBAudioDetectiveSetBandSumForm(LBAudioDetectiveRef d, UInt32 inForm) {
+    LBAD_GUARD_BEGIN
+    LBAD_LOCK(d);
+    if (!d || inForm > 2) return kLBAudioDetectiveArgumentInvalid;
+    if (inForm == 2 && !band_lanes_now(d)) return kLBAudioDetectiveArgumentInvalid;
+    d->band_form = inForm;
+    return noErr;
+    LBAD_GUARD_END
+}
+
+OSStatus LBAudioDetectiveGetBandSumForm(LBAudioDetectiveRef d, UInt32* outForm) {
+    LBAD_GUARD_BEGIN
+    LBAD_LOCK(d);
+    if (!d || !outForm) return kLBAudioDetectiveArgumentInvalid;
+    *outForm = d->band_form != 1 && band_lanes_now(d) ? 2u : 1u;
+    return noErr;
+    LBAD_GUARD_END
 }
 
 OSStatus LBAudioDetectiveSetKernelTuning(LBAudioDetectiveRef d, UInt32 inWavesPerWorkgroup, UInt32 inTwiddleCache) {

@@ -88,6 +88,7 @@ struct Plan {
     DeviceBuffer<uint32_t> d_bands;  // [bands] lo, [bands] hi, [bands] divisor as float bits, ... (api_detective.cpp: eight rows + 1 word, then RN(1 / divisor) and "short division proven" from word 9 * bands)
     DeviceBuffer<float> d_bin_const; // per-bin twiddles of the pruned kernel (only when pruned_ok)
     bool pruned_ok = false;
+    bool lanes_ok = false;        // ... and its band-sums-in-lanes form (rows_lanes_supported: the default 44.1 kHz table)
     bool full_ok = false;         // k_rows_full.hip applies
     bool stream_ok = false;       // k_rows_stream.hip applies (also uses d_claim)
     bool stream2_ok = false;      // k_rows_stream2.hip applies (preferred over k_rows_full.hip when the clip length is even)
@@ -148,7 +149,13 @@ void rows_pruned_constants(std::vector<float>& out);
 // compact: rows of 16 floats (plan.sparse), else rows of 32
 hipError_t launch_rows_pruned(const Plan& plan, const float* d_bin_const, const void* d_pcm, uint32_t fmt,
                               uint64_t n_clips, uint64_t samples_per_clip, uint32_t frames_per_clip, float* d_frames,
-                              hipStream_t stream, bool compact = false);
+                              hipStream_t stream, bool compact = false, uint32_t band_form = 0);
+// its second kernel, frame_rows_lanes_kernel: every band's bins in one lane, band sums in registers.  Applies where
+// rows_pruned_supported holds and the plan's non-empty bands are exactly the compiled table's (44.1 kHz / 1024 / 32 bands);
+// band_form of launch_rows_pruned: 0 takes it where it applies, 1 never, 2 takes it or fails.  rows_lanes_table appends its
+// per-task rows to the band table (nothing for another table).
+bool rows_lanes_supported(const Plan& plan);
+void rows_lanes_table(const Plan& plan, std::vector<uint32_t>& band_tbl);
 
 // specialised stage 1 without pruning (k_rows_full.hip): 1024- and 2048-sample windows, any band table
 bool rows_full_supported(const Plan& plan);
@@ -696,6 +703,7 @@ struct LBAudioDetective {
     uint32_t stride;
     uint32_t bands;
     uint32_t variant = 0;
+    uint32_t band_form = 0;   // LBAudioDetectiveSetBandSumForm
     uint32_t tune_waves = 0;  // copied into the plan
     bool tune_cache = true;
     uint32_t hop_mode = 1;   // file entry points: 0 = hop in processing-rate samples, 1 = upstream's file-frame hop

@@ -24,7 +24,14 @@
 // bit-identical because every surviving butterfly is evaluated exactly as in the full network.  The band means
 // divide by a per-band constant: three instructions per quotient behind a guard (const_div.hpp), the IEEE
 // sequence only in the waves whose guard trips.
+//
+// Two kernels share everything up to the split pass.  frame_rows_pruned_kernel adds a band's power terms through LDS (band =
+// lane) and takes any table whose bands read bins 0..21; frame_rows_lanes_kernel (further down) is compiled for the default
+// 44.1 kHz table, deals the bins out so that every band lies in one lane and adds in registers (tests/test_isa_rows_lanes.py
+// pins its loop).  launch_rows_pruned takes the second where rows_lanes_supported holds.
 #include "internal.hpp"
+
+#include <cstring>
 #include "const_div.hpp"
 #include "fft64_lane.hpp"
 
@@ -465,6 +472,322 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
     if (claimer) claims_done(claim_ctr);
 }
 
+// ---- band sums in lanes ---------------------------------------------------------------------------------------------
+// The default 44.1 kHz table has 15 live bands over bins 0..21, none wider than three bins, and the eight lanes of a window
+// evaluate three bins each: dealt out as below, every band lies wholly inside one lane and its sum is two adds in
+// registers.  Lane j of a window takes kLaneBin[j] (the two-bin lanes come last); the stage-6 row of bin k goes to
+// transpose position 8 rd + j, where k is lane j's rd-th bin, so that every lane still reads positions j, j + 8, j + 16.
+constexpr int kLaneBands = 15;
+constexpr int kLaneBandLo[kLaneBands] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 14, 17, 19};
+constexpr int kLaneBandHi[kLaneBands] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 14, 17, 19, 22};
+constexpr int kLaneBin[8][3] = {{0, 1, 2}, {3, 4, 5}, {6, 7, 8}, {9, 10, 11}, {14, 15, 16}, {19, 20, 21}, {12, 13, -1}, {17, 18, -1}};
+constexpr int kLanesFirstRow = 11;  // plan.d_bands: the per-task rows start at word kLanesFirstRow * 32 (rows_lanes_table)
+
+constexpr int lanes_pos(int k) {    // transpose position of bin k
+    for (int j = 0; j < 8; ++j)
+        for (int rd = 0; rd < 3; ++rd)
+            if (kLaneBin[j][rd] == k) return 8 * rd + j;
+    return -1;
+}
+constexpr int lanes_band_of(int k) {
+    for (int b = 0; b < kLaneBands; ++b)
+        if (k >= kLaneBandLo[b] && k < kLaneBandHi[b]) return b;
+    return -1;
+}
+// bit j: lane j's rd-th bin continues the band of the bin before it (which is then the bin k - 1: sums stay in bin order)
+constexpr uint32_t lanes_cont_mask(int rd) {
+    uint32_t m = 0;
+    for (int j = 0; j < 8; ++j)
+        if (kLaneBin[j][rd] >= 0 && kLaneBin[j][rd] == kLaneBin[j][rd - 1] + 1 &&
+            lanes_band_of(kLaneBin[j][rd]) == lanes_band_of(kLaneBin[j][rd - 1]))
+            m |= 1u << j;
+    return m;
+}
+// the bins at positions 8 rd + j, j = 0..7, five bits each
+constexpr uint64_t lanes_bin_pack(int rd) {
+    uint64_t v = 0;
+    for (int j = 0; j < 8; ++j) v |= (uint64_t)(kLaneBin[j][rd] >= 0 ? kLaneBin[j][rd] : 0) << (5 * j);
+    return v;
+}
+constexpr bool lanes_table_ok() {
+    for (int k = 0; k < kBins; ++k)
+        if (lanes_pos(k) < 0 || lanes_pos(k) >= kBins || lanes_band_of(k) < 0) return false;
+    for (int b = 0; b < kLaneBands; ++b) {      // a band's bins: one lane, consecutive tasks
+        for (int k = kLaneBandLo[b] + 1; k < kLaneBandHi[b]; ++k)
+            if (lanes_pos(k) != lanes_pos(k - 1) + 8) return false;
+    }
+    return lanes_pos(kBins - 1) == kBins - 1;   // what the tasks without a bin read
+}
+static_assert(lanes_table_ok(), "every bin has one position below 22 and every band lies in one lane, in bin order");
+
+template <int I, int END>
+__device__ __forceinline__ void store_rows_lanes(const cplx (&x)[64], float* trow) {
+    if constexpr (I < END) {
+        *(lds_vf32x2*)(trow + lanes_pos(I) * kRowDw) = stage6_row<I>(x);
+        store_rows_lanes<I + 1, END>(x, trow);
+    }
+}
+// held row I is the mirror of bin 21 - I: it goes where the bin's "+" row was
+template <int I, int N>
+__device__ __forceinline__ void store_held_lanes(const cplx (&h)[kRows - kRowsA], float* trow) {
+    if constexpr (I < N) {
+        *(lds_vf32x2*)(trow + lanes_pos(kBins - 1 - I) * kRowDw) = h[I];
+        store_held_lanes<I + 1, N>(h, trow);
+    }
+}
+
+// frame_rows_pruned_kernel up to and including the split pass; then a lane adds its own power terms.
+//   t_i: the power term of the lane's i-th bin, +0.0 where it is NaN or +inf (the filter of k_fft_bands.hip; a term is a sum
+//   of two squares, so -inf does not occur);  s0 = t0, s1 = (cont1 ? s0 : +0.0) + t1, s2 = (cont2 ? s1 : +0.0) + t2.
+// This is the oracle's `p = 0; p += term` in bin order, bit for bit: a term is a sum of two squares, hence >= +0.0 and never
+// -0.0, so 0 + t = t, p + 0 = p, and a skipped term equals an added +0.0.  A sum that ends a band is divided and stored; the
+// per-task divisor, RN(1 / divisor), "proven" flag and the band's place in a row come from the plan (rows_lanes_table), a task
+// that ends no band has the place 0xFFFFFFFF, divisor 1, and stores nothing.  The guard of const_div.hpp looks at all three
+// sums of every lane (more than the stored ones: never less safe).  With full rows (the tap) the lanes also store the +0.0
+// of the structurally empty bands, dealt out by the same table; compact rows have no such band.
+template <int FMT>
+__global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_lanes_kernel(const void* __restrict__ pcm_raw,
+                                                                        uint64_t samples_per_clip,
+                                                                        uint32_t frames_per_clip, uint64_t n_units,
+                                                                        uint64_t units_per_xcd,
+                                                                        const float* __restrict__ bin_const,
+                                                                        const uint32_t* __restrict__ band_tbl,
+                                                                        uint32_t* __restrict__ claim_ctr,
+                                                                        float* __restrict__ frames, uint32_t frame_dw,
+                                                                        uint32_t row_dw, uint32_t place_row) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* span = smem;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    float* tbuf = smem + kSpanDw + wave * (8 * kWinDw);
+    float* cbuf = smem + kSpanDw + kTDw;
+    static_assert((kSpanDw + kTDw + kConstDw) % 2 == 0, "the slot behind the constants is 8-byte aligned");
+    typedef __attribute__((address_space(3))) volatile uint64_t lds_vu64;
+    lds_vu64* next_slot = (lds_vu64*)(cbuf + kConstDw);
+
+    const uint32_t wg_per_xcd = gridDim.x >> 3;
+    const uint64_t xcd_begin = (uint64_t)(blockIdx.x & 7) * units_per_xcd;     // units_per_xcd is a multiple of 4
+    const uint64_t xcd_end = xcd_begin + units_per_xcd < n_units ? xcd_begin + units_per_xcd : n_units;
+    uint64_t unit = xcd_begin + 4 * (uint64_t)(blockIdx.x >> 3);
+    if (unit >= xcd_end) {
+        if (threadIdx.x == 0) claims_done(claim_ctr);
+        return;
+    }
+
+    auto span_start = [&](uint64_t u) {
+        const uint32_t frame = (uint32_t)(u >> 2);          // the launcher keeps unit numbers below 2^31
+        const uint32_t clip = frame / frames_per_clip;
+        const uint32_t fi = frame - clip * frames_per_clip;
+        return (uint64_t)clip * samples_per_clip + (uint64_t)(fi * 128 + (uint32_t)(u & 3) * kUnitWindows) * kStride;
+    };
+    uint32_t* my_ctr = claim_ctr + (blockIdx.x & 7);
+    asm volatile("" : "+v"(my_ctr));
+    const bool claimer = threadIdx.x == 0;
+    uint32_t claimed = 0;
+    // the unit of claim 0, one scalar pair over the loop (the empty asm keeps it from being taken apart into two again)
+    uint64_t claim_base = xcd_begin + 4 * (uint64_t)wg_per_xcd;
+    asm volatile("" : "+s"(claim_base));
+
+    span_to_lds<FMT>(pcm_raw, span_start(unit), span, wave, lane);
+    // block p of the constants holds those of the bin at position p: a lane then picks the blocks j, j + 8, j + 16 as it picks the
+    // rows, and both the fill and the picks touch LDS exactly as in frame_rows_pruned_kernel (a task without a bin evaluates bin
+    // 21, whose row it reads)
+    for (int i = threadIdx.x; i < kBins * kBinConst; i += kThreads) {
+        const int p = i / kBinConst;
+        constexpr uint64_t kBin0 = lanes_bin_pack(0), kBin1 = lanes_bin_pack(1), kBin2 = lanes_bin_pack(2);
+        const int k = (int)(((p < 8 ? kBin0 : p < 16 ? kBin1 : kBin2) >> (5 * (p & 7))) & 31u);
+        cbuf[p * kConstStride + (i % kBinConst)] = bin_const[k * kBinConst + (i % kBinConst)];
+    }
+
+    const int w8 = lane >> 3, r = lane & 7;
+    const float inv_norm = 1.0f / (float)(kW / 4);
+    // rr: the lane's place j among the eight of its window (the swap of round 5 stays, see frame_rows_pruned_kernel)
+    const int rr = r ^ ((((w8 + 1) >> 1) & 1) << 2);
+    int tk[3];      // transpose positions read, as before: j, j + 8, j + 16 (clamped to a valid row)
+#pragma unroll
+    for (int rd = 0; rd < 3; ++rd) tk[rd] = rr + 8 * rd < kBins ? rr + 8 * rd : kBins - 1;
+
+    // per-task constants: divisor, RN(1 / divisor), place in a row; one "proven" word per lane
+    const uint32_t* task_tbl = band_tbl + kLanesFirstRow * kBands;
+    float t_div[3], t_rcp[3];
+    uint32_t t_off = 0, z_off = 0;      // three places of a row, eight bits each (0xFF: none): band means, empty bands
+    bool proven = true;
+#pragma unroll
+    for (int rd = 0; rd < 3; ++rd) {
+        t_div[rd] = __uint_as_float(task_tbl[8 * rd + rr]);
+        t_rcp[rd] = __uint_as_float(task_tbl[kBands + 8 * rd + rr]);
+        proven = proven && task_tbl[2 * kBands + 8 * rd + rr] != 0u;
+        t_off |= (task_tbl[place_row * kBands + 8 * rd + rr] & 0xFFu) << (8 * rd);
+        z_off |= (task_tbl[5 * kBands + 8 * rd + rr] & 0xFFu) << (8 * rd);
+    }
+    const int t_fast_hi = proven ? (int)kBandDivHi : -1;   // compared as bit patterns
+    constexpr uint32_t kCont1 = lanes_cont_mask(1), kCont2 = lanes_cont_mask(2);
+    const uint32_t m_cont1 = (kCont1 >> rr) & 1u ? 0xFFFFFFFFu : 0u;
+    const uint32_t m_cont2 = (kCont2 >> rr) & 1u ? 0xFFFFFFFFu : 0u;
+    const bool is_dc = rr == 0;                   // the lane whose first bin is bin 0
+
+    __syncthreads();
+    TreeTw twp[3], twm[3];
+    f32x2 ws[3];
+#pragma unroll
+    for (int rd = 0; rd < 3; ++rd) {
+        const float* c = cbuf + tk[rd] * kConstStride;
+        twp[rd] = tree_twiddles(c);
+        twm[rd] = tree_twiddles(c + 6);
+        ws[rd] = *reinterpret_cast<const f32x2*>(c + 12);
+    }
+
+    float out[3] = {0.0f, 0.0f, 0.0f};   // band means of the previous quarter frame, stored one iteration late
+    float* out_row = nullptr;
+#ifdef LBAD_EXP_TIMELINE
+    long long ts[8];
+#define STAMP(i) ts[i] = __builtin_readcyclecounter()
+#else
+#define STAMP(i)
+#endif
+    // the places are unpacked at every store (the empty asm hides that they never change): six loop-invariant lane masks are
+    // more than the scalar file has left, they were spilled to vector lanes
+    auto store_out = [&]() {
+        if (!out_row) return;
+        uint32_t places = t_off;
+        asm volatile("" : "+v"(places));
+#pragma unroll
+        for (int rd = 0; rd < 3; ++rd) {
+            const uint32_t o = (places >> (8 * rd)) & 0xFFu;
+            if (o != 0xFFu) out_row[o] = out[rd];
+        }
+        uint32_t layout = place_row;                // (likewise: no 64-bit mask of "full rows" kept over the loop)
+        asm volatile("" : "+s"(layout));
+        if (layout == 3u) {                         // full rows
+            places = z_off;
+            asm volatile("" : "+v"(places));
+#pragma unroll
+            for (int rd = 0; rd < 3; ++rd) {
+                const uint32_t o = (places >> (8 * rd)) & 0xFFu;
+                if (o != 0xFFu) out_row[o] = 0.0f;
+            }
+        }
+    };
+    for (;;) {
+        STAMP(0);
+#ifdef LBAD_EXP_TIMELINE
+        const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+        // ---- A: this quarter frame's span has landed (own loads: vmcnt, the other waves': barrier) ----
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+        const uint32_t quarter = (uint32_t)(unit & 3);
+        // (claimed three iterations ago; the slot holds the unit the claim stands for, 64 bits as every unit number)
+        if (quarter == 3 && claimer) *next_slot = claim_base + 4 * (uint64_t)claimed;
+        __syncthreads();
+        STAMP(1);
+
+        // ---- B1: 64 points of this lane; once every wave has its points the span buffer is free -------
+        cplx x[64];
+        load_points<0>(x, span + 80 * (8 * wave + w8) + 2 * r);
+        const uint64_t next = quarter == 3 ? *next_slot : unit + 1;
+        __syncthreads();
+        if (next < xcd_end) span_to_lds<FMT>(pcm_raw, span_start(next), span, wave, lane);
+        if (quarter == 0 && claimer) claimed = atomicAdd(my_ctr, 1u);
+#ifndef LBAD_EXP_TIMELINE
+        store_out();
+#endif
+        STAMP(2);
+
+        // ---- B2: DIT stages 1..5 in registers ---------------------------------------------------------
+        __builtin_amdgcn_s_setprio(0);
+        stage_blocks<1, 0>(x);
+        stage_blocks<2, 0>(x);
+        stage_blocks<3, 0>(x);
+        stage_blocks<4, 0>(x);
+        stage_blocks<5, 0>(x);
+        STAMP(3);
+        __builtin_amdgcn_s_setprio(3);
+
+        // ---- B3/B4: stage 6, the "+" rows to their positions; the mirror rows wait in registers ------
+        store_rows_lanes<0, kRowsA>(x, tbuf + w8 * kWinDw + 2 * r);
+        cplx held[kRows - kRowsA];
+        hold_rows<kRowsA, kRows, kRowsA>(x, held);
+        cplx za[3];
+        {
+            TreeIn in[3];
+#pragma unroll
+            for (int rd = 0; rd < 3; ++rd) in[rd] = tree_load(tbuf + w8 * kWinDw + tk[rd] * kRowDw);
+            // pass 2: the mirror row of a bin takes the bin's position (bin 0 has none: its position keeps the stale "+" row,
+            // whose tree is dropped below)
+            store_held_lanes<0, kRows - kRowsA>(held, tbuf + w8 * kWinDw + 2 * r);
+#pragma unroll
+            for (int rd = 0; rd < 3; ++rd) za[rd] = tree_eval(in[rd], twp[rd]);
+        }
+        STAMP(4);
+        float pw[3];
+        {
+            TreeIn in[3];
+#pragma unroll
+            for (int rd = 0; rd < 3; ++rd) in[rd] = tree_load(tbuf + w8 * kWinDw + tk[rd] * kRowDw);
+#pragma unroll
+            for (int rd = 0; rd < 3; ++rd) {
+                const cplx b = tree_eval(in[rd], twm[rd]);
+                const cplx a = za[rd];
+                float re, im;
+                if (rd == 0 && is_dc) {
+                    const float sm = a.x + a.y, df = a.x - a.y;
+                    re = sm + sm;
+                    im = df + df;
+                } else {
+                    const float sr = a.x + b.x, si = a.y - b.y;
+                    const float dr = a.x - b.x, di = a.y + b.y;
+                    const float wr = ws[rd].x, wi = ws[rd].y;
+                    re = __fmaf_rn(wr, di, __fmaf_rn(wi, dr, sr));
+                    im = __fmaf_rn(-wr, dr, __fmaf_rn(wi, di, si));
+                }
+                if (re > 0.0f) re = __fmul_rn(re, inv_norm);
+                if (im > 0.0f) im = __fmul_rn(im, inv_norm);
+                pw[rd] = __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im));
+            }
+        }
+        STAMP(5);
+
+        // ---- B5: band sums in registers, in bin order ------------------------------------------------------------------
+        float s[3];
+#pragma unroll
+        for (int rd = 0; rd < 3; ++rd) s[rd] = pw[rd] < INFINITY ? pw[rd] : 0.0f;     // NaN and +inf are skipped
+        s[1] = __fadd_rn(__uint_as_float(__float_as_uint(s[0]) & m_cont1), s[1]);
+        s[2] = __fadd_rn(__uint_as_float(__float_as_uint(s[1]) & m_cont2), s[2]);
+        DivGuard g;
+        g.dividends(s[0], s[1]);
+        g.dividends(s[2], s[2]);
+        const int s_max = max(max((int)__float_as_uint(s[0]), (int)__float_as_uint(s[1])), (int)__float_as_uint(s[2]));
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(g.lo < 2u * kBandDivLo - 1u || s_max > t_fast_hi) == 0, 1)) {
+#pragma unroll
+            for (int rd = 0; rd < 3; ++rd) out[rd] = div_c<true>(s[rd], t_div[rd], t_rcp[rd]);
+        } else {
+#pragma unroll
+            for (int rd = 0; rd < 3; ++rd) out[rd] = div_c<false>(s[rd], t_div[rd], t_rcp[rd]);
+        }
+        // row = quarter * 32 + 8 * wave + window of the wave
+        out_row = frames + (unit >> 2) * frame_dw + (quarter * kUnitWindows + 8 * wave + w8) * row_dw;
+#ifdef LBAD_EXP_TIMELINE
+        asm volatile("" ::"v"(out[0]), "v"(out[1]), "v"(out[2]));   // nothing stores the means in this build: keep their work
+        STAMP(6);
+        if (lane == 0) {
+            float* o = frames + ((unit >> 2) * 128 + quarter * kUnitWindows + 8 * wave) * kBands;
+            for (int i = 1; i < 7; ++i) o[i - 1] = (float)(ts[i] - ts[i - 1]);
+            o[6] = (float)(ts[0] & 0xFFFFFF);
+            o[7] = (float)__builtin_amdgcn_s_getreg(((16 - 1) << 11) | 4);
+            o[8] = (float)(ts[0] >> 24 & 0xFFFFFF);
+            o[9] = (float)(__builtin_amdgcn_s_memrealtime() - rt0);
+        }
+#endif
+        if (next >= xcd_end) break;
+        unit = next;
+    }
+#ifndef LBAD_EXP_TIMELINE
+    store_out();
+#endif
+    if (claimer) claims_done(claim_ctr);
+}
+#undef STAMP
+
 }  // namespace
 
 bool rows_pruned_supported(const Plan& p) {
@@ -500,13 +823,77 @@ void rows_pruned_constants(std::vector<float>& out) {
     }
 }
 
+// the band table's part of rows_lanes_supported: 32 bands whose non-empty ones are exactly the compiled table's, and empty
+// bands whose mean is +0.0 (a zero divisor would make it NaN)
+static bool lanes_bands_match(const Plan& p) {
+    if (p.window != (uint32_t)kW || p.bands != (uint32_t)kBands || p.table.lo.size() != (size_t)kBands ||
+        p.table.indices.size() != (size_t)kBands + 1)
+        return false;
+    int n = 0;
+    for (int b = 0; b < kBands; ++b) {
+        if (p.table.lo[b] >= p.table.hi[b]) {
+            if (p.table.indices[b + 1] == p.table.indices[b]) return false;
+            continue;
+        }
+        if (n == kLaneBands || p.table.lo[b] != (uint32_t)kLaneBandLo[n] || p.table.hi[b] != (uint32_t)kLaneBandHi[n]) return false;
+        ++n;
+    }
+    return n == kLaneBands;
+}
+
+bool rows_lanes_supported(const Plan& p) { return rows_pruned_supported(p) && lanes_bands_match(p); }
+
+// Six rows of 32 words behind the eleven of the band table, indexed by task 8 rd + j (lane j's rd-th bin): the divisor of the
+// bin's band, RN(1 / divisor), whether the short division is proven for it, the band's word inside a full row and inside a
+// compact row of plan.sparse (0xFFFFFFFF: the task does not end a band, or the band is not stored), and, by the same index, the
+// words of a full row that belong to structurally empty bands (0xFFFFFFFF: none), which the lanes set to +0.0.
+void rows_lanes_table(const Plan& p, std::vector<uint32_t>& tbl) {
+    if (!lanes_bands_match(p)) return;
+    tbl.resize((size_t)(kLanesFirstRow + 6) * kBands, 0u);
+    uint32_t* t = &tbl[(size_t)kLanesFirstRow * kBands];
+    const float one = 1.0f;
+    for (int i = 0; i < kBands; ++i) {
+        std::memcpy(&t[i], &one, 4);
+        std::memcpy(&t[kBands + i], &one, 4);
+        t[2 * kBands + i] = 1u;
+        t[3 * kBands + i] = t[4 * kBands + i] = t[5 * kBands + i] = 0xFFFFFFFFu;
+    }
+    int empty = 0;
+    for (uint32_t b = 0; b < (uint32_t)kBands; ++b) {
+        if (p.table.lo[b] >= p.table.hi[b]) {           // dealt out over the 24 task slots: 17 empty bands at most three a lane
+            if (empty < 24) t[5 * kBands + empty] = b;
+            ++empty;
+            continue;
+        }
+        const float div = (float)(p.table.indices[b + 1] - p.table.indices[b]);
+        const float rcp = 1.0f / div;
+        for (uint32_t k = p.table.lo[b]; k < p.table.hi[b]; ++k) {
+            const int at = lanes_pos((int)k);
+            std::memcpy(&t[at], &div, 4);
+            std::memcpy(&t[kBands + at], &rcp, 4);
+            t[2 * kBands + at] = band_div_proven(div) ? 1u : 0u;
+            if (k + 1 != p.table.hi[b]) continue;       // the band's last bin: its task holds the whole sum
+            t[3 * kBands + at] = b;
+            if (p.sparse.ok) {
+                const uint32_t pos = b >= 16 ? p.sparse.pos_right[b - 16] : (b == p.sparse.left ? p.sparse.pos_left : 0xFFu);
+                if (pos != 0xFFu) t[4 * kBands + at] = pos;
+            }
+        }
+    }
+}
+
 template <int FMT>
 static hipError_t launch_rows_fmt(const Plan& plan, const float* d_bin_const, const void* d_pcm, uint64_t n_frames,
                                   uint64_t samples_per_clip, uint32_t frames_per_clip, float* d_frames,
-                                  hipStream_t stream, bool compact) {
-    static PerDevice attr;
-    if (attr.changed(kLdsBytes)) {
+                                  hipStream_t stream, bool compact, bool lanes) {
+    static PerDevice attr, attr_lanes;
+    if (!lanes && attr.changed(kLdsBytes)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(frame_rows_pruned_kernel<FMT>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+        if (e != hipSuccess) return e;
+    }
+    if (lanes && attr_lanes.changed(kLdsBytes)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(frame_rows_lanes_kernel<FMT>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
         if (e != hipSuccess) return e;
     }
@@ -517,24 +904,33 @@ static hipError_t launch_rows_fmt(const Plan& plan, const float* d_bin_const, co
     uint64_t wg_per_xcd = ((uint64_t)n_cu * kWgPerCu + 7) / 8;
     if (wg_per_xcd > units_per_xcd / 4) wg_per_xcd = units_per_xcd / 4;
     uint32_t* claim = reinterpret_cast<uint32_t*>(const_cast<float*>(d_bin_const)) + kClaimOffset;
-    hipLaunchKernelGGL(frame_rows_pruned_kernel<FMT>, dim3((uint32_t)(wg_per_xcd * 8)), dim3(kThreads), kLdsBytes,
-                       stream, d_pcm, samples_per_clip, frames_per_clip, n_units, units_per_xcd, d_bin_const,
-                       plan.d_bands, claim, d_frames, compact ? plan.sparse.frame_dw() : 128u * kBands, compact ? 5u : 3u);
+    if (lanes)
+        hipLaunchKernelGGL(frame_rows_lanes_kernel<FMT>, dim3((uint32_t)(wg_per_xcd * 8)), dim3(kThreads), kLdsBytes,
+                           stream, d_pcm, samples_per_clip, frames_per_clip, n_units, units_per_xcd, d_bin_const,
+                           plan.d_bands, claim, d_frames, compact ? plan.sparse.frame_dw() : 128u * kBands,
+                           compact ? plan.sparse.n_stored : (uint32_t)kBands, compact ? 4u : 3u);
+    else
+        hipLaunchKernelGGL(frame_rows_pruned_kernel<FMT>, dim3((uint32_t)(wg_per_xcd * 8)), dim3(kThreads), kLdsBytes,
+                           stream, d_pcm, samples_per_clip, frames_per_clip, n_units, units_per_xcd, d_bin_const,
+                           plan.d_bands, claim, d_frames, compact ? plan.sparse.frame_dw() : 128u * kBands, compact ? 5u : 3u);
     return hipGetLastError();
 }
 
+// band_form: 0 the band sums in lanes where the plan allows (rows_lanes_supported), 1 through LDS, 2 in lanes or an error
 hipError_t launch_rows_pruned(const Plan& plan, const float* d_bin_const, const void* d_pcm, uint32_t fmt,
                               uint64_t n_clips, uint64_t samples_per_clip, uint32_t frames_per_clip, float* d_frames,
-                              hipStream_t stream, bool compact) {
+                              hipStream_t stream, bool compact, uint32_t band_form) {
     if (compact && !plan.sparse.ok) return hipErrorInvalidValue;
+    if (band_form > 2 || (band_form == 2 && !plan.lanes_ok)) return hipErrorInvalidValue;
+    const bool lanes = band_form != 1 && plan.lanes_ok;
     const uint64_t n_frames = n_clips * frames_per_clip;
     if (n_frames == 0) return hipSuccess;
     if (n_frames > 0x7fffffffull) return hipErrorInvalidValue;
     if (n_frames * 4 + 8 > 0x7fffffffull) return hipErrorInvalidValue;
     switch (fmt) {
-        case 0: return launch_rows_fmt<0>(plan, d_bin_const, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream, compact);
-        case 1: return launch_rows_fmt<1>(plan, d_bin_const, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream, compact);
-        case 2: return launch_rows_fmt<2>(plan, d_bin_const, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream, compact);
+        case 0: return launch_rows_fmt<0>(plan, d_bin_const, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream, compact, lanes);
+        case 1: return launch_rows_fmt<1>(plan, d_bin_const, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream, compact, lanes);
+        case 2: return launch_rows_fmt<2>(plan, d_bin_const, d_pcm, n_frames, samples_per_clip, frames_per_clip, d_frames, stream, compact, lanes);
         default: return hipErrorInvalidValue;
     }
 }

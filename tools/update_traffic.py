@@ -118,8 +118,9 @@ def sliding(entry, label, pattern, note, queries=1):
 
 
 # reps = 3 in tools/prof_all.sh for the stage kernels
-stage("stage1_pruned", "B_headline", r"frame_rows_pruned_kernel", 100000 * 3, 176525, "headline: 1 s clips at 44.1 kHz, 1024-sample windows, compact frames out",
-      "k_rows_pruned.hip", r"frame_rows_pruned_kernelILi0E", 640)
+# (the headline runs frame_rows_lanes_kernel where the band table is the default 44.1 kHz one, frame_rows_pruned_kernel before round 8)
+stage("stage1_pruned", "B_headline", r"frame_rows_(lanes|pruned)_kernel", 100000 * 3, 176525, "headline: 1 s clips at 44.1 kHz, 1024-sample windows, compact frames out",
+      "k_rows_pruned.hip", r"frame_rows_lanes_kernelILi0E" if rnd >= 8 else r"frame_rows_pruned_kernelILi0E", 640)
 stage("stage2_select32", "B_headline", r"haar_select32_kernel", 100000 * 3, 176525, "stage 2 of the headline (sparse form, compact frames in)")
 stage("stage1_stream_2048", "A_stream2", r"rows_stream2_kernel", 20000 * 3, 198557, "configs[0] settings: 9 s clips at 5512 Hz, 2048-sample windows",
       "k_rows_stream2.hip", r"rows_stream2_kernelILi0E", 640)

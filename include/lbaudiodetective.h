@@ -756,6 +756,47 @@ OSStatus LBAudioDetectiveCorpusQueryPackedRecordingThresholdKeysDevice(LBAudioDe
                                                                        UInt32 inSubfingerprints, UInt32 inRange, Float32 inThreshold,
                                                                        UInt64 inCapacity, UInt64 inIndexBase, void* outKeys,
                                                                        void* outCount, void* outLags, void* inStream);
+/* Recording timeline: what was playing at each moment of ONE query -- a long recording -- against a RAGGED corpus: the cells of
+ * the occurrences calls above folded per OFFSET of the query over the entries, on the device.  The output is bounded by the
+ * recording, one 64-bit key per sub-fingerprint offset, whatever the corpus size.
+ * Entry j of n_j sub-fingerprints TAKES PART when n_j <= n_q, the query's sub-fingerprints (the query is fingerprint1, equal
+ * lengths included); a longer entry has no position inside the recording and is skipped.  The cells of a participating entry are
+ * the n_q - n_j + 1 values q_o(j) that LBAudioDetectiveCorpusMatchProfile(inCorpus, inQuery, inRange, j) returns, bit for bit; o
+ * is the sub-fingerprint of the recording at which the entry starts.  A cell COUNTS when q_o(j) >= inThreshold as Float32.
+ * KEYS: outKeys[o], for every o in [0, n_q), is the unsigned maximum over the counting cells of
+ * q_o(j) bits << 32 | 0xFFFFFFFF - (inIndexBase + j), the key format of every other call (LBAudioDetectiveCorpusDecodeKey,
+ * ...GatherKeysDevice and ...RemoveKeysDevice accept it): the best score, ties to the LOWEST entry index; 0 where no cell counts.
+ * All n_q words are written.
+ * LENGTHS: outLengths[o] (n_q UInt32, may be NULL; the keys do not depend on it) is n_j of the winning entry -- it spans
+ * [o, o + n_j) of the recording --, 0 for a zero key.
+ * Shards that hold contiguous index ranges merge by the element-wise unsigned maximum of their key arrays (the lengths follow
+ * the winning shard's).
+ * The restrictions are the occurrences calls': the corpus is ragged (a uniform corpus is kLBAudioDetectiveArgumentInvalid) with
+ * no entry above LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS; the query has the corpus' sub-fingerprint length and 1 .. 2^31 - 1
+ * sub-fingerprints; inThreshold is finite and > 0 (a zero cell never counts; above 1 is legal and matches nothing), inIndexBase +
+ * entries <= 2^32, inRange == 0 means the sub-fingerprint length; NULL handles and pointers but outLengths are
+ * kLBAudioDetectiveArgumentInvalid.  What needs no handle is refused first, then kLBAudioDetectiveDeviceUnavailable, then what
+ * needs the corpus.  An empty corpus, and a corpus without a participating entry, are noErr with zero keys and lengths.
+ * The Device forms are asynchronous on inStream, which they never await, and wait ON THE DEVICE for the corpus' latest append.
+ * The Packed form takes the query as inSubfingerprints x LBAD_PACKED_BYTES bytes on the device (4-byte aligned, bits at or above
+ * the sub-fingerprint length ignored; nothing of it visits the host); packed, handle and host forms agree bit for bit.
+ * LBAudioDetectiveCorpusQueryRecordingTimeline returns (index, score, length) per offset to host arrays of n_q elements
+ * (outLengths may be NULL), -1 / 0 / 0 where nothing counts, and *outCount = the offsets with a winner.  Results do not depend
+ * on launch order, grid, chunking or outLengths; there is no early exit: every cell of every participating pair is computed.
+ * The scratch is the corpus' join scratch, under LBAudioDetectiveCorpusSetJoinScratchLimit: the entries go through in chunks of
+ * a multiple of 128 with nothing visiting the host in between, ceil(entries / 128) x tiles x 126 x 8 bytes for a chunk, tiles =
+ * ceil((n_q - min(n_q, shortest entry) + 1) / 126); a limit below one chunk of 128 entries is kLBAudioDetectiveArgumentInvalid at
+ * the call. */
+OSStatus LBAudioDetectiveCorpusRecordingTimelineKeysDevice(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                                           UInt32 inRange, Float32 inThreshold, UInt64 inIndexBase, void* outKeys,
+                                                           void* outLengths, void* inStream);
+OSStatus LBAudioDetectiveCorpusRecordingPackedTimelineKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQuery,
+                                                                 UInt32 inSubfingerprints, UInt32 inRange, Float32 inThreshold,
+                                                                 UInt64 inIndexBase, void* outKeys, void* outLengths,
+                                                                 void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryRecordingTimeline(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
+                                                      UInt32 inRange, Float32 inThreshold, SInt64* outIndices, Float32* outScores,
+                                                      UInt32* outLengths, UInt64* outCount);
 /* Removal: entries taken out of a corpus on the device, the other half of the corpus life cycle -- the take-down of one
  * recording, or the action behind a join's duplicate pairs.  Both forms, both kinds of corpus (uniform of any shape, ragged):
  * the named entries go, the others keep their relative order and close up -- the entry at old index i gets the new index

@@ -1035,6 +1035,68 @@ class Corpus:
             _dev_ptr(lags_out) if lags_out is not None else None, _stream_ptr(stream)), "CorpusQueryPackedRecordingThresholdKeysDevice")
         return keys_out, lags_out, count_out
 
+    # ---- recording timeline: the best entry at every offset of ONE query (a long recording) against a ragged corpus -- the
+    # occurrences cells folded per offset over the entries not longer than the query.  One key per sub-fingerprint of the query,
+    # whatever the corpus size.  Shards of contiguous index ranges merge by the element-wise maximum of their keys AS UNSIGNED
+    # (score bits of a positive float leave the sign bit clear, so torch.maximum on the int64 tensors is that maximum).
+    def recording_timeline_keys_device(self, fp: Fingerprint = None, packed=None, per_query: int = 0, threshold: float = 0.0,
+                                       range_: int = 0, index_base: int = 0, keys_out=None, lengths_out=None,
+                                       want_lengths: bool = True, stream=None):
+        """LBAudioDetectiveCorpusRecordingTimelineKeysDevice (fp) / ...RecordingPackedTimelineKeysDevice (packed: per_query packed
+        sub-fingerprints already on the device): (keys int64 [n_q], lengths int32 [n_q] or None) on the device, asynchronously on
+        `stream`, n_q = the query's sub-fingerprints.  keys[o] is the best cell at or above `threshold` among the entries that
+        start at offset o and lie inside the query (score bits << 32 | 0xFFFFFFFF - (index_base + entry), ties to the lower
+        entry), 0 where there is none; lengths[o] the winner's sub-fingerprints (the bits of a UInt32; 0 for a zero key).
+        want_lengths=False (and no lengths_out) passes NULL: the keys are the same.  Decode with decode_timeline_keys."""
+        if (fp is None) == (packed is None):
+            raise ValueError("give either fp or packed")
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        n = fp.number_of_subfingerprints if fp is not None else int(per_query)
+        if keys_out is None or (want_lengths and lengths_out is None):
+            import torch
+            if keys_out is None:
+                keys_out = torch.empty(max(1, n), dtype=torch.int64, device=dev)[:n]
+            if want_lengths and lengths_out is None:
+                lengths_out = torch.empty(max(1, n), dtype=torch.int32, device=dev)[:n]
+        _out_ok(keys_out, n, "keys_out")
+        if lengths_out is not None:
+            _out_ok(lengths_out, n, "lengths_out")
+        lp = _dev_ptr(lengths_out) if lengths_out is not None else None
+        if fp is not None:
+            _check(self._L.LBAudioDetectiveCorpusRecordingTimelineKeysDevice(self._ref, fp._ref, range_, threshold, index_base,
+                                                                            _dev_ptr(keys_out), lp, _stream_ptr(stream)),
+                   "CorpusRecordingTimelineKeysDevice")
+        else:
+            _packed_ok(packed, 1, per_query)
+            _check(self._L.LBAudioDetectiveCorpusRecordingPackedTimelineKeysDevice(self._ref, _dev_ptr(packed), per_query, range_,
+                                                                                  threshold, index_base, _dev_ptr(keys_out), lp,
+                                                                                  _stream_ptr(stream)),
+                   "CorpusRecordingPackedTimelineKeysDevice")
+        return keys_out, lengths_out
+
+    def recording_timeline(self, fp: Fingerprint, threshold: float, range_: int = 0):
+        """LBAudioDetectiveCorpusQueryRecordingTimeline: (indices int64[n_q], scores float32[n_q], lengths uint32[n_q]) per offset
+        of the query: the best entry at or above `threshold` that starts there and lies inside the query, its score and its
+        sub-fingerprints; -1 / 0 / 0 where there is none."""
+        n = fp.number_of_subfingerprints
+        idx = np.full(max(1, n), -1, dtype=np.int64)
+        sc = np.zeros(max(1, n), dtype=np.float32)
+        ln = np.zeros(max(1, n), dtype=np.uint32)
+        cnt = N.UInt64(0)
+        _check(self._L.LBAudioDetectiveCorpusQueryRecordingTimeline(self._ref, fp._ref, range_, threshold,
+                                                                   idx.ctypes.data_as(C.POINTER(N.SInt64)),
+                                                                   sc.ctypes.data_as(C.POINTER(N.Float32)),
+                                                                   ln.ctypes.data_as(C.POINTER(N.UInt32)), C.byref(cnt)),
+               "CorpusQueryRecordingTimeline")
+        return idx[:n].copy(), sc[:n].copy(), ln[:n].copy()
+
+    def recording_segments(self, fp: Fingerprint, threshold: float, range_: int = 0):
+        """What played when: (start, index, score, length) arrays of non-overlapping spans [start, start + length) of the query,
+        sorted by start -- timeline_segments of recording_timeline's result.  GREEDY over the per-offset WINNERS, not over all
+        cells: an entry that is second best at its offset is never reported, even where the winner there is later suppressed by
+        an overlapping better span."""
+        return timeline_segments(*self.recording_timeline(fp, threshold, range_))
+
     def set_join_scratch_limit(self, n_bytes: int):
         """bytes of device memory the join's scratch may take, and thereby the rows per chunk; 0 restores the default"""
         _check(self._L.LBAudioDetectiveCorpusSetJoinScratchLimit(self._ref, n_bytes), "CorpusSetJoinScratchLimit")
@@ -1497,6 +1559,41 @@ def decode_occurrence_keys(keys, lags=None, count=None):
     if lags is not None:
         lg = np.asarray(lags.cpu().numpy() if hasattr(lags, "cpu") else lags, dtype=np.int32).reshape(-1)[:m].copy()
     return ((0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32), lg)
+
+
+def decode_timeline_keys(keys, lengths=None, index_base: int = 0):
+    """(indices int64[n], scores float32[n], lengths uint32[n] or None) of a timeline call's keys (any int64 sequence), one per
+    offset of the query: -1 / 0 / 0 for a zero key, the entry's index (global minus index_base) otherwise."""
+    k = np.asarray(keys.cpu().numpy() if hasattr(keys, "cpu") else keys, dtype=np.int64).astype(np.uint64).reshape(-1)
+    idx = np.where(k != 0, (0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64) - int(index_base), -1).astype(np.int64)
+    sc = (k >> np.uint64(32)).astype(np.uint32).view(np.float32)
+    ln = None
+    if lengths is not None:
+        ln = np.asarray(lengths.cpu().numpy() if hasattr(lengths, "cpu") else lengths).reshape(-1).astype(np.int64).astype(np.uint32)
+    return idx, sc, ln
+
+
+def timeline_segments(indices, scores, lengths):
+    """Non-overlapping spans from a timeline's per-offset winners (indices -1 where there is none): the winners are visited in
+    descending key order (higher score, then lower index), ties to the lower offset, and a winner at offset o is accepted when
+    [o, o + length) meets no accepted span.  Returns (start int64[m], index int64[m], score float32[m], length uint32[m]) sorted
+    by start.  Greedy over the WINNERS, not over all cells."""
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    sc = np.asarray(scores, dtype=np.float32).reshape(-1)
+    ln = np.asarray(lengths, dtype=np.uint32).reshape(-1)
+    at = np.flatnonzero(idx >= 0)
+    # (descending score, ascending index, ascending offset; lexsort's last key is the primary one)
+    order = at[np.lexsort((at, idx[at], -sc[at].astype(np.float64)))]
+    taken = np.zeros(len(idx) + 1, dtype=bool)
+    kept = []
+    for o in order:
+        end = min(int(o) + int(ln[o]), len(idx))
+        if ln[o] == 0 or taken[o:end].any():
+            continue
+        taken[o:end] = True
+        kept.append(int(o))
+    kept = np.asarray(sorted(kept), dtype=np.int64)
+    return kept, idx[kept], sc[kept], ln[kept]
 
 
 def decode_join_keys(keys, offsets, first: int = 0):

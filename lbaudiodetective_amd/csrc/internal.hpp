@@ -443,6 +443,36 @@ hipError_t launch_recording_chunk(const RecordingCall& call, void* d_scratch, ui
 hipError_t launch_recording_lag_gather(const unsigned long long* d_keys, uint64_t n, uint64_t index_base, uint64_t count,
                                        const int32_t* d_entry_lags, int32_t* d_lags, hipStream_t stream);
 
+// recording timeline (k_timeline.hip): the occurrences pass' cells of ONE query against a ragged corpus folded per OFFSET of the
+// query over the entries not longer than it: the largest key  q_o bits << 32 | 0xFFFFFFFF - (index base + entry)  of the cells
+// at or above the threshold, 0 where there is none.
+struct TimelineCall {
+    const uint4* d_recs = nullptr;       // the corpus: records, record positions
+    const uint32_t* d_off = nullptr;
+    uint32_t ne_min = 0, ne_max = 0;     // its shortest (<= n_query) and longest entry (<= LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS)
+    uint32_t subfp_len = 0, range = 0;
+    const uint32_t* d_qwords = nullptr;  // the query as build_align_query's ragged form, 16-byte aligned, on the device
+    uint32_t n_query = 0;
+    uint64_t tiles = 0;                  // timeline_tiles(n_query, ne_min)
+    float threshold = 0.0f;
+    uint64_t index_base = 0;
+    unsigned long long* d_keys = nullptr;    // n_query words, zeroed by the caller in front of the first chunk
+    hipStream_t stream = nullptr;
+};
+uint32_t timeline_block_entries();       // entries a chunk is a whole number of
+// tiles of 126 offsets that hold every offset an entry not longer than the query can start at
+uint64_t timeline_tiles(uint32_t n_query, uint32_t ne_min);
+// scratch of a chunk of `entries` entries (one 64-bit partial per block of timeline_block_entries() entries and offset of a tile)
+// and the entries a chunk may have under a limit (a whole number of blocks; 0: the limit is too small for one)
+size_t timeline_scratch_bytes(uint64_t entries, uint64_t tiles);
+uint64_t timeline_chunk_entries(uint64_t tiles, uint64_t limit_bytes);
+// one chunk: `entries` entries from `first_entry` folded into d_keys, every word of d_scratch written before it is read.  Two or
+// three launches on the call's stream, nothing visits the host.
+hipError_t launch_timeline_chunk(const TimelineCall& call, void* d_scratch, uint64_t first_entry, uint64_t entries);
+// d_lengths[o] = sub-fingerprints of the entry d_keys[o] names, 0 for a zero key; n < 2^31 offsets, index_base + count <= 2^32
+hipError_t launch_timeline_lengths(const unsigned long long* d_keys, uint32_t n, uint64_t index_base, uint64_t count,
+                                   const uint32_t* d_off, uint32_t* d_lengths, hipStream_t stream);
+
 // removal (k_remove.hip): the index of a call -- which entries go and where the others land -- and the moves of a chunk.
 // The index block of a corpus of `count` entries (remove_index_layout places it in d_block, 16-byte aligned, `words` words):
 // head (entries kept, lowest removed index or 0xFFFFFFFF, two zero words), tiles + 1 tile offsets (kept entries below the

@@ -1,120 +1,61 @@
 // api_timeline.cpp -- the recording timeline (k_timeline.hip): the best entry of a ragged corpus at every offset of ONE query, a
 // long recording above all, as keys and lengths on the device, from a handle or from packed sub-fingerprints on the device, and
-// the host-returning form.
+// the host-returning form.  The plan, the query's staging, the events and the key block are recording_pass.cpp's.
 #include "internal.hpp"
 
 #include <cmath>
-#include <cstring>
 
 namespace lbad {
 namespace {
 
-// the query of a call: a handle (staged through the alignment's pair, under its event) or packed sub-fingerprints on the device
-// (through the builder of k_query.hip, under the packed calls' event)
-struct TlQuery {
-    const LBAudioDetectiveFingerprint* fp = nullptr;
-    const uint32_t* d_rows = nullptr;
-    uint32_t per = 0;
-};
+const PassFamily kFamily = {[](uint32_t n_query, uint32_t ne_min, uint32_t) { return timeline_tiles(n_query, ne_min); }, timeline_chunk_entries,
+                            timeline_block_entries};
 
 // what needs neither handle nor device: a finite threshold above 0, an index base a corpus can lie behind
 bool timeline_args_ok(float threshold, uint64_t index_base) {
     return std::isfinite(threshold) && threshold > 0.0f && index_base <= 0x100000000ull;
 }
 
-// what the corpus decides, before anything is reserved or launched (the occurrences calls' own restrictions): a ragged corpus
-// of the query's sub-fingerprint length with no entry above the cap, the indices in range, the entries per chunk under the
-// limit.  *out_any: an entry takes part (the shortest is not longer than the query).
-OSStatus timeline_plan(const LBAudioDetectiveCorpus* c, uint32_t q_length, uint32_t n_query, uint64_t index_base, uint64_t* out_tiles,
-                       uint64_t* out_chunk, bool* out_any) {
-    if (!c->ragged || q_length != c->subfp_len || n_query == 0 || n_query > 0x7FFFFFFFu ||
-        c->ne_max > LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS || index_base + c->count > 0x100000000ull)
-        return kLBAudioDetectiveArgumentInvalid;
-    *out_tiles = 1;
-    *out_chunk = 0;
-    *out_any = false;
-    if (c->count == 0) return noErr;
-    const uint32_t ne_min = c->len_hist.begin()->first;
-    const uint64_t tiles = timeline_tiles(n_query, ne_min);
-    const uint64_t limit = c->join_scratch_limit ? c->join_scratch_limit : kJoinScratchDefault;
-    const uint64_t chunk = timeline_chunk_entries(tiles, limit);
-    if (chunk == 0) return kLBAudioDetectiveArgumentInvalid;          // the limit holds no block of entries at this query length
-    const uint64_t block = timeline_block_entries();
-    *out_tiles = tiles;
-    *out_chunk = chunk < c->count ? chunk : (c->count + block - 1) / block * block;
-    *out_any = ne_min <= n_query;
-    return noErr;
-}
-
-// everything behind the staging of the query, on `stream`: the pass chunk by chunk into the keys, then the lengths
-OSStatus timeline_launch(LBAudioDetectiveCorpus* c, const uint32_t* d_qwords, uint32_t n_query, uint32_t range, float threshold,
-                         uint64_t index_base, uint64_t tiles, uint64_t chunk, unsigned long long* keys, uint32_t* lengths,
-                         hipStream_t stream) {
-    // the corpus' latest append, awaited on the device
-    if (c->append_event.ev) LBAD_HIP(hipStreamWaitEvent(stream, c->append_event, 0));
-    TimelineCall call;
-    call.d_recs = c->d_recs; call.d_off = c->d_off; call.ne_min = c->len_hist.begin()->first; call.ne_max = c->ne_max;
-    call.subfp_len = c->subfp_len; call.range = range ? range : c->subfp_len; call.d_qwords = d_qwords; call.n_query = n_query;
-    call.tiles = tiles; call.threshold = threshold; call.index_base = index_base; call.d_keys = keys; call.stream = stream;
-    hipError_t e = hipSuccess;
-    for (uint64_t e0 = 0; e0 < c->count && e == hipSuccess; e0 += chunk)
-        e = launch_timeline_chunk(call, c->d_join_scratch, e0, c->count - e0 < chunk ? c->count - e0 : chunk);
-    LBAD_HIP(e);
-    if (lengths) LBAD_HIP(launch_timeline_lengths(keys, n_query, index_base, c->count, c->d_off, lengths, stream));
+// everything behind the staging of the query, on the call's stream: the pass chunk by chunk into the keys, then the lengths
+OSStatus timeline_launch(LBAudioDetectiveCorpus* c, const TimelineCall& call, uint64_t chunk, uint32_t* lengths) {
+    LBAD_HIP(pass_chunks(c->count, chunk, [&](uint64_t e0, uint64_t n) { return launch_timeline_chunk(call, c->d_join_scratch, e0, n); }));
+    if (lengths) LBAD_HIP(launch_timeline_lengths(call.d_keys, call.n_query, call.index_base, c->count, c->d_off, lengths, call.stream));
     return noErr;
 }
 
 // One call.  The caller has checked what needs no handle, and the device.
-OSStatus timeline_impl(LBAudioDetectiveCorpus* c, const TlQuery& q, uint32_t range, float threshold, uint64_t index_base,
-                       unsigned long long* keys, uint32_t* lengths, hipStream_t stream) {
-    const uint32_t n_query = q.fp ? q.fp->count : q.per;
-    uint64_t tiles = 0, chunk = 0;
-    bool any = false;
-    OSStatus st = timeline_plan(c, q.fp ? q.fp->length : c->subfp_len, n_query, index_base, &tiles, &chunk, &any);
+OSStatus timeline_impl(LBAudioDetectiveCorpus* c, const PassQuery& q, float threshold, uint64_t index_base, unsigned long long* keys,
+                       uint32_t* lengths, hipStream_t stream) {
+    PassPlan plan;
+    OSStatus st = pass_plan(c, q, index_base, kFamily, &plan);
     if (st != noErr) return st;
+    const uint32_t n_query = plan.call.n_query;
     // the keys carry the running maximum from chunk to chunk: zeros in front of the first.  Where no entry takes part these
     // zeros (and the lengths') are the answer.
     LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n_query * sizeof(unsigned long long), stream));
-    if (!any) {
+    if (!plan.any) {
         if (lengths) LBAD_HIP(hipMemsetAsync(lengths, 0, (size_t)n_query * sizeof(uint32_t), stream));
         return noErr;
     }
-    // the scratch is the previous call's until its event: the partials (join_ev), the query's words (align_ev / pq_ev)
-    Event& q_ev = q.fp ? c->align_ev : c->pq_ev;
-    st = c->join_ev.wait_or_create();
-    if (st == noErr) st = q_ev.wait_or_create();
-    if (st == noErr) st = c->d_join_scratch.reserve(timeline_scratch_bytes(chunk, tiles));
+    PassGuard guard(c, q, false);
+    st = guard.wait();                                     // (the scratch is the previous call's until then)
+    if (st == noErr) st = c->d_join_scratch.reserve(timeline_scratch_bytes(plan.chunk, plan.call.tiles));
     if (st != noErr) return st;
-    const uint32_t* d_qwords = nullptr;
-    if (q.fp) {
-        std::vector<uint32_t> words;
-        build_align_query(q.fp, true, words);
-        st = c->align_q.reserve(words.size());
-        if (st != noErr) return st;
-        std::memcpy(c->align_q.host, words.data(), words.size() * sizeof(uint32_t));
-        d_qwords = c->align_q.dev;
-        st = hip_status(hipMemcpyAsync(c->align_q.dev, c->align_q.host, words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream),
-                        "query words", __LINE__);
-    } else {
-        st = c->d_pq.reserve((size_t)q.per * kPackedWords);
-        if (st != noErr) return st;
-        d_qwords = c->d_pq;
-        st = hip_status(launch_build_query_rows(q.d_rows, 1, q.per, c->subfp_len, true, c->d_pq, nullptr, stream), "query words", __LINE__);
-    }
-    if (st == noErr) st = timeline_launch(c, d_qwords, n_query, range, threshold, index_base, tiles, chunk, keys, lengths, stream);
-    // behind whatever was launched, also after a failure: the scratch and the staged words are in use until then
-    const OSStatus rec = q_ev.record(stream);
-    const OSStatus rec2 = c->join_ev.record(stream);
-    return st != noErr ? st : (rec != noErr ? rec : rec2);
+    TimelineCall call;
+    static_cast<OcPassCall&>(call) = plan.call;
+    call.threshold = threshold; call.index_base = index_base; call.d_keys = keys;
+    st = pass_stage_query(c, q, stream, &call);
+    if (st == noErr) st = timeline_launch(c, call, plan.chunk, lengths);
+    return guard.finish(stream, st);
 }
 
 OSStatus timeline_handle_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprint* q, uint32_t range, float threshold,
                               uint64_t index_base, unsigned long long* keys, uint32_t* lengths, hipStream_t stream) {
     if (!c || !q || !keys || !timeline_args_ok(threshold, index_base)) return kLBAudioDetectiveArgumentInvalid;
     if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    TlQuery tq;
-    tq.fp = q;
-    return timeline_impl(c, tq, range, threshold, index_base, keys, lengths, stream);
+    PassQuery pq;
+    pq.fp = q; pq.range = range;
+    return timeline_impl(c, pq, threshold, index_base, keys, lengths, stream);
 }
 
 OSStatus timeline_packed_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t per, uint32_t range, float threshold,
@@ -122,9 +63,9 @@ OSStatus timeline_packed_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows,
     if (!c || !d_rows || !keys || per == 0 || per > 0x7FFFFFFFu || !timeline_args_ok(threshold, index_base))
         return kLBAudioDetectiveArgumentInvalid;
     if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    TlQuery tq;
-    tq.d_rows = d_rows; tq.per = per;
-    return timeline_impl(c, tq, range, threshold, index_base, keys, lengths, stream);
+    PassQuery pq;
+    pq.d_rows = d_rows; pq.per = per; pq.range = range;
+    return timeline_impl(c, pq, threshold, index_base, keys, lengths, stream);
 }
 
 // host-returning form: keys and (out_lengths given) lengths in ONE block of the corpus' key buffer on the null stream, then
@@ -133,24 +74,20 @@ OSStatus timeline_host_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFin
                             SInt64* out_idx, Float32* out_scores, UInt32* out_lengths, UInt64* out_count) {
     if (!c || !q || !out_idx || !out_scores || !out_count || !timeline_args_ok(threshold, 0)) return kLBAudioDetectiveArgumentInvalid;
     if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    uint64_t tiles = 0, chunk = 0;
-    bool any = false;
-    OSStatus st = timeline_plan(c, q->length, q->count, 0, &tiles, &chunk, &any);      // (a refused call reserves nothing)
+    PassQuery pq;
+    pq.fp = q; pq.range = range;
+    PassPlan plan;
+    OSStatus st = pass_plan(c, pq, 0, kFamily, &plan);     // (a refused call reserves nothing)
     if (st != noErr) return st;
     const size_t n = q->count;
-    st = c->topk_ev.wait();             // (the key buffer is the previous top-K, threshold or join call's until then)
-    const size_t words = n + (out_lengths ? (n + 1) / 2 : 0);
-    if (st == noErr) st = c->d_topk_keys.reserve(words);
+    KeyBlock b;
+    st = key_block_reserve(c, n, out_lengths ? n : 0, &b);
     if (st != noErr) return st;
-    unsigned long long* d_keys = c->d_topk_keys;
-    uint32_t* d_lengths = out_lengths ? reinterpret_cast<uint32_t*>(d_keys + n) : nullptr;
-    st = timeline_handle_impl(c, q, range, threshold, 0, d_keys, d_lengths, nullptr);
-    if (st != noErr) {
-        (void)hipStreamSynchronize(nullptr);       // whatever was launched has left the key buffer before its next user
-        return st;
-    }
-    std::vector<unsigned long long> host(words);
-    LBAD_HIP(hipMemcpy(host.data(), d_keys, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    st = timeline_impl(c, pq, threshold, 0, b.d_keys, b.d_words, nullptr);
+    if (st != noErr) return key_block_failed(st);
+    std::vector<unsigned long long> host;
+    st = key_block_read(b, n, &host);
+    if (st != noErr) return st;
     const uint32_t* lengths = reinterpret_cast<const uint32_t*>(host.data() + n);
     UInt64 got = 0;
     for (size_t o = 0; o < n; ++o) {

@@ -385,23 +385,27 @@ uint64_t join_ragged_chunk_rows(uint64_t n_entries, uint64_t limit_bytes);
 hipError_t launch_join_ragged_chunk(const JoinRaggedCall& call, void* d_scratch, uint32_t chunk_rows_max, uint64_t first_row,
                                     uint32_t rows, uint32_t first_chunk, unsigned long long* out_offsets);
 
-// occurrences (k_occurrences.hip): every cell (entry, sliding offset) of ONE query against a ragged corpus whose quotient q_o --
-// LBAudioDetectiveCorpusMatchProfile's value -- is >= threshold (with `peaks`: and a local peak of its profile), in (entry,
-// offset) order: keys and, where given, signed lags to the slots below the capacity.
-struct OccurrencesCall {
+// what a call of the occurrences pass is, whichever family folds its cells (k_occurrences.hip, k_recording.hip, k_timeline.hip)
+struct OcPassCall {
     const uint4* d_recs = nullptr;       // the corpus: records, record positions
     const uint32_t* d_off = nullptr;
     uint32_t ne_min = 0, ne_max = 0;     // its shortest and longest entry (ne_max <= LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS)
     uint32_t subfp_len = 0, range = 0;
     const uint32_t* d_qwords = nullptr;  // the query as build_align_query's ragged form, 16-byte aligned, on the device
     uint32_t n_query = 0;
-    uint64_t tiles = 0;                  // occurrences_tiles(n_query, ne_min, ne_max)
+    uint64_t tiles = 0;                  // tiles per entry, the family's bound over every pair of the call (stated at its struct)
+    hipStream_t stream = nullptr;
+};
+
+// occurrences (k_occurrences.hip): every cell (entry, sliding offset) of ONE query against a ragged corpus whose quotient q_o --
+// LBAudioDetectiveCorpusMatchProfile's value -- is >= threshold (with `peaks`: and a local peak of its profile), in (entry,
+// offset) order: keys and, where given, signed lags to the slots below the capacity.
+struct OccurrencesCall : OcPassCall {    // tiles: occurrences_tiles(n_query, ne_min, ne_max)
     float threshold = 0.0f;
     bool peaks = false;
     uint64_t capacity = 0, index_base = 0;
     unsigned long long* d_keys = nullptr;    // `capacity` slots, zeroed by the caller
     int32_t* d_lags = nullptr;               // optional: `capacity` slots, zeroed by the caller
-    hipStream_t stream = nullptr;
 };
 uint32_t occurrences_block_entries();    // entries a chunk is a whole number of
 // tiles per entry: a bound over every pair of the call
@@ -420,17 +424,9 @@ constexpr uint64_t kJoinScratchDefault = 256ull << 20;   // LBAudioDetectiveCorp
 
 // recording scores (k_recording.hip): the occurrences pass' cells of ONE query against a ragged corpus folded per entry to the
 // largest cell -- the ragged scan's score, bit for bit -- and the lowest offset that reaches it as the signed lag.
-struct RecordingCall {
-    const uint4* d_recs = nullptr;       // the corpus: records, record positions
-    const uint32_t* d_off = nullptr;
-    uint32_t ne_min = 0, ne_max = 0;     // its shortest and longest entry (ne_max <= LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS)
-    uint32_t subfp_len = 0, range = 0;
-    const uint32_t* d_qwords = nullptr;  // the query as build_align_query's ragged form, 16-byte aligned, on the device
-    uint32_t n_query = 0;
-    uint64_t tiles = 0;                  // occurrences_tiles(n_query, ne_min, ne_max)
+struct RecordingCall : OcPassCall {      // tiles: occurrences_tiles(n_query, ne_min, ne_max)
     float* d_scores = nullptr;           // one per entry of the CORPUS (a chunk writes its own entries')
     int32_t* d_lags = nullptr;           // optional: likewise
-    hipStream_t stream = nullptr;
 };
 // scratch of a chunk of `entries` entries (one 64-bit partial per entry and tile) and the entries a chunk may have under a limit
 // (a whole number of occurrences_block_entries(); 0: the limit is too small for one block)
@@ -446,18 +442,10 @@ hipError_t launch_recording_lag_gather(const unsigned long long* d_keys, uint64_
 // recording timeline (k_timeline.hip): the occurrences pass' cells of ONE query against a ragged corpus folded per OFFSET of the
 // query over the entries not longer than it: the largest key  q_o bits << 32 | 0xFFFFFFFF - (index base + entry)  of the cells
 // at or above the threshold, 0 where there is none.
-struct TimelineCall {
-    const uint4* d_recs = nullptr;       // the corpus: records, record positions
-    const uint32_t* d_off = nullptr;
-    uint32_t ne_min = 0, ne_max = 0;     // its shortest (<= n_query) and longest entry (<= LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS)
-    uint32_t subfp_len = 0, range = 0;
-    const uint32_t* d_qwords = nullptr;  // the query as build_align_query's ragged form, 16-byte aligned, on the device
-    uint32_t n_query = 0;
-    uint64_t tiles = 0;                  // timeline_tiles(n_query, ne_min)
+struct TimelineCall : OcPassCall {       // tiles: timeline_tiles(n_query, ne_min); ne_min <= n_query
     float threshold = 0.0f;
     uint64_t index_base = 0;
     unsigned long long* d_keys = nullptr;    // n_query words, zeroed by the caller in front of the first chunk
-    hipStream_t stream = nullptr;
 };
 uint32_t timeline_block_entries();       // entries a chunk is a whole number of
 // tiles of 126 offsets that hold every offset an entry not longer than the query can start at
@@ -472,6 +460,64 @@ hipError_t launch_timeline_chunk(const TimelineCall& call, void* d_scratch, uint
 // d_lengths[o] = sub-fingerprints of the entry d_keys[o] names, 0 for a zero key; n < 2^31 offsets, index_base + count <= 2^32
 hipError_t launch_timeline_lengths(const unsigned long long* d_keys, uint32_t n, uint64_t index_base, uint64_t count,
                                    const uint32_t* d_off, uint32_t* d_lengths, hipStream_t stream);
+
+// The host side the three families above share (recording_pass.cpp; DESIGN.md 4.4n states the protocol).
+// The query of a call: a handle (staged through the alignment's pair, under its event) or packed sub-fingerprints on the device
+// (through the builder of k_query.hip, under the packed calls' event), and the range it is compared over (0: the whole length)
+struct PassQuery {
+    const struct ::LBAudioDetectiveFingerprint* fp = nullptr;
+    const uint32_t* d_rows = nullptr;
+    uint32_t per = 0;
+    uint32_t range = 0;
+};
+// a family as the plan sees it: its tiles (ne_max may go unused), the entries of a chunk under a limit, the entries a chunk is
+// a whole number of
+struct PassFamily {
+    uint64_t (*tiles)(uint32_t n_query, uint32_t ne_min, uint32_t ne_max);
+    uint64_t (*chunk_entries)(uint64_t tiles, uint64_t limit_bytes);
+    uint32_t (*block_entries)();
+};
+struct PassPlan {
+    OcPassCall call;                     // the shared fields of the family's call, all but the query's words and the stream
+    uint64_t chunk = 0;                  // entries per chunk: the scratch limit's, or the whole corpus rounded up to a block
+    bool any = false;                    // an entry takes part: the shortest is not longer than the query
+};
+// What the corpus decides, before anything is reserved or launched: a ragged corpus of the query's sub-fingerprint length with no
+// entry above the cap (ne_max: the host knows it), the indices in range, a scratch limit that holds a block of entries.  An
+// empty corpus gives tiles 1, chunk 0.
+OSStatus pass_plan(const struct ::LBAudioDetectiveCorpus* c, const PassQuery& q, uint64_t index_base, const PassFamily& fam, PassPlan* plan);
+// The events a call takes: join_ev (the partials), the query's (align_ev or pq_ev: the staged words) and, with `topk`, topk_ev
+// (the score row and the selection's words).  wait() before the scratch is touched; then every way out goes through finish(),
+// which records them all on the stream behind whatever was launched, also after a failure -- the scratch and the staged words
+// are in use until then -- and gives the call's status, else the first record's that failed.
+struct PassGuard {
+    Event* ev[3] = {nullptr, nullptr, nullptr};
+    PassGuard(struct ::LBAudioDetectiveCorpus* c, const PassQuery& q, bool topk);
+    OSStatus wait();
+    OSStatus finish(hipStream_t stream, OSStatus st);
+};
+// the query's words onto the device on `stream` (call->d_qwords, call->stream), and behind them the corpus' latest append awaited
+// on the stream.  The caller holds the query's event.
+OSStatus pass_stage_query(struct ::LBAudioDetectiveCorpus* c, const PassQuery& q, hipStream_t stream, OcPassCall* call);
+// the chunks of a corpus of `count` entries in turn, until one fails: launch(first entry, entries)
+template <typename Launch>
+hipError_t pass_chunks(uint64_t count, uint64_t chunk, Launch launch) {
+    hipError_t e = hipSuccess;
+    for (uint64_t e0 = 0; e0 < count && e == hipSuccess; e0 += chunk) e = launch(e0, count - e0 < chunk ? count - e0 : chunk);
+    return e;
+}
+// The block of a host-returning form in the corpus' key buffer, for the null stream: n_keys keys and, behind them, n_words 32-bit
+// values, once the buffer's previous user (a top-K, threshold or join call) has left it.
+struct KeyBlock {
+    unsigned long long* d_keys = nullptr;
+    uint32_t* d_words = nullptr;         // nullptr: n_words == 0
+    size_t n_keys = 0;
+};
+OSStatus key_block_reserve(struct ::LBAudioDetectiveCorpus* c, size_t n_keys, size_t n_words, KeyBlock* b);
+// the first m keys and, where there are any, m values behind them (host[m] onwards) read back; the whole block is one copy
+OSStatus key_block_read(const KeyBlock& b, size_t m, std::vector<unsigned long long>* host);
+// after a failure behind the reservation: whatever was launched has left the key buffer before its next user
+OSStatus key_block_failed(OSStatus st);
 
 // removal (k_remove.hip): the index of a call -- which entries go and where the others land -- and the moves of a chunk.
 // The index block of a corpus of `count` entries (remove_index_layout places it in d_block, 16-byte aligned, `words` words):

@@ -38,8 +38,7 @@ constexpr uint32_t kOcGroup = kOcWaves * kOcKeep;      // offsets of one entry a
 constexpr uint32_t kOcBlock = 64;                      // entries a workgroup walks with one window: what a chunk is a multiple of
 static_assert(kOcKeep == kOcTile && kOcBlock == kOcEntries, "occurrences_common.hpp's tile and entry block are these");
 
-// Unit u = (entry block u / groups, tile group u % groups): workgroups that run at the same time share their entries' records.
-// counts[entry][tile] for every tile below a.tiles; any[u]: the unit has a match.
+// Units of kOcBlock entries (oc_unit).  counts[entry][tile] for every tile below a.tiles; any[u]: the unit has a match.
 template <bool FULL>
 __global__ __launch_bounds__(kOcThreads) void occurrences_count_kernel(const OcArgs a, uint32_t* __restrict__ counts,
                                                                        uint32_t* __restrict__ any) {
@@ -47,29 +46,26 @@ __global__ __launch_bounds__(kOcThreads) void occurrences_count_kernel(const OcA
     __shared__ uint32_t s_any;
     const OcLds s = oc_lds(s_dyn, a.win);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t i = threadIdx.x; i < kTriSize; i += kOcThreads) s.tri[i] = a.tri[i];
-    const uint32_t units = ((a.entries + kOcBlock - 1u) / kOcBlock) * a.groups;
+    oc_load_tri(a, s);
+    const uint32_t units = oc_units(a, kOcBlock);
     for (uint32_t u = blockIdx.x; u < units; u += gridDim.x) {
-        const uint32_t eb = u / a.groups, g = u - eb * a.groups;
-        const uint32_t wb = g * kOcGroup - 1u;
+        const OcUnit n = oc_unit(a, u, kOcBlock, wave);
         __syncthreads();                                       // (the unit before has left the window and s_any)
-        oc_stage(a, s, wb);
+        oc_stage(a, s, n.wb);
         if (threadIdx.x == 0u) s_any = 0u;
         __syncthreads();
-        const uint32_t tile = g * kOcWaves + wave;
-        const uint32_t e0 = eb * kOcBlock, e1 = a.entries - e0 < kOcBlock ? a.entries : e0 + kOcBlock;
         uint32_t some = 0u;
-        if (tile < a.tiles) {
-            const uint32_t first = tile * kOcKeep;
-            for (uint32_t e = e0; e < e1; ++e) {
+        if (n.tile < a.tiles) {
+            const uint32_t first = n.tile * kOcKeep;
+            for (uint32_t e = n.e0; e < n.e1; ++e) {
                 uint32_t rec0, ne, c = 0u;
                 oc_entry(a, e, &rec0, &ne);
                 if (first < oc_offsets(a, ne)) {
                     float q0, q1;
-                    const uint32_t m = oc_cells<FULL>(a, s, wb, rec0, ne, first - 1u + 2u * lane, &q0, &q1);
+                    const uint32_t m = oc_cells<FULL>(a, s, n.wb, rec0, ne, first - 1u + 2u * lane, &q0, &q1);
                     c = (uint32_t)__popcll(__ballot(m & 1u)) + (uint32_t)__popcll(__ballot(m & 2u));
                 }
-                if (lane == 0u) counts[e * a.tiles + tile] = c;
+                if (lane == 0u) counts[e * a.tiles + n.tile] = c;
                 some |= c;
             }
         }
@@ -91,22 +87,17 @@ __global__ __launch_bounds__(kOcThreads) void occurrences_scatter_kernel(const O
     extern __shared__ uint4 s_dyn[];
     const OcLds s = oc_lds(s_dyn, a.win);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t i = threadIdx.x; i < kTriSize; i += kOcThreads) s.tri[i] = a.tri[i];
-    const uint32_t units = ((a.entries + kOcBlock - 1u) / kOcBlock) * a.groups;
+    oc_load_tri(a, s);
+    const uint32_t units = oc_units(a, kOcBlock);
     for (uint32_t u = blockIdx.x; u < units; u += gridDim.x) {
         if (any[u] == 0u) continue;                            // (the same word for the whole workgroup) nothing is loaded
-        const uint32_t eb = u / a.groups, g = u - eb * a.groups;
-        const uint32_t e0 = eb * kOcBlock, e1 = a.entries - e0 < kOcBlock ? a.entries : e0 + kOcBlock;
-        if (row_base[e0] >= capacity) continue;                // the list is full in front of this block
-        const uint32_t wb = g * kOcGroup - 1u;
-        __syncthreads();
-        oc_stage(a, s, wb);
-        __syncthreads();
-        const uint32_t tile = g * kOcWaves + wave;
-        if (tile >= a.tiles) continue;                         // (this wave meets no barrier of the unit any more)
-        const uint32_t first = tile * kOcKeep;
-        for (uint32_t e = e0; e < e1; ++e) {
-            const uint32_t item = e * a.tiles + tile;
+        const OcUnit n = oc_unit(a, u, kOcBlock, wave);
+        if (row_base[n.e0] >= capacity) continue;              // the list is full in front of this block
+        oc_stage_unit(a, s, n.wb);
+        if (n.tile >= a.tiles) continue;                       // (this wave meets no barrier of the unit any more)
+        const uint32_t first = n.tile * kOcKeep;
+        for (uint32_t e = n.e0; e < n.e1; ++e) {
+            const uint32_t item = e * a.tiles + n.tile;
             if (__builtin_amdgcn_readfirstlane(counts[item]) == 0u) continue;
             const unsigned long long at = row_base[e] + tile_at[item];
             if (at >= capacity) continue;
@@ -114,7 +105,7 @@ __global__ __launch_bounds__(kOcThreads) void occurrences_scatter_kernel(const O
             oc_entry(a, e, &rec0, &ne);
             const uint32_t o = first - 1u + 2u * lane;
             float q0, q1;
-            const uint32_t m = oc_cells<FULL>(a, s, wb, rec0, ne, o, &q0, &q1);
+            const uint32_t m = oc_cells<FULL>(a, s, n.wb, rec0, ne, o, &q0, &q1);
             const unsigned long long b0 = __ballot(m & 1u), b1 = __ballot(m & 2u);
             const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u)) +
                                    __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u));
@@ -158,23 +149,10 @@ OcScratch oc_carve(void* d_scratch, uint64_t entries, uint64_t tiles) {
 
 template <bool FULL>
 hipError_t launch_oc(const OccurrencesCall& c, const OcScratch& s, const OcArgs& a, size_t lds, uint32_t first_chunk) {
-    // (the largest size both kernels of this instance were set up for on each device, recorded once BOTH calls have succeeded)
-    // (not PerDevice: that helper records before the set-up has succeeded.  Unsynchronised like it; two host threads that race
-    // here set the attribute twice at worst)
-    static size_t ready[kMaxDevices] = {};
-    const int dev = current_device();
-    if (dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;
-    if (lds > 48 * 1024 && lds > ready[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(occurrences_count_kernel<FULL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(occurrences_scatter_kernel<FULL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        ready[dev] = lds;
-    }
-    const uint64_t units = oc_blocks(a.entries) * a.groups;
-    const dim3 grid((uint32_t)(units < kOcMaxGrid ? units : kOcMaxGrid));
+    static size_t ready[kMaxDevices] = {};                     // (both kernels of this instance)
+    const hipError_t e = oc_allow_lds(ready, lds, occurrences_count_kernel<FULL>, occurrences_scatter_kernel<FULL>);
+    if (e != hipSuccess) return e;
+    const dim3 grid = oc_grid(oc_blocks(a.entries) * a.groups);
     hipLaunchKernelGGL(occurrences_count_kernel<FULL>, grid, dim3(kOcThreads), lds, c.stream, a, s.counts, s.any);
     launch_join_scans(s.counts, a.tiles, a.entries, s.tile_at, s.row_base, s.state, first_chunk, s.offsets, c.stream);
     hipLaunchKernelGGL(occurrences_scatter_kernel<FULL>, grid, dim3(kOcThreads), lds, c.stream, a, s.counts, s.any, s.tile_at,
@@ -215,24 +193,15 @@ uint64_t occurrences_chunk_entries(uint64_t tiles, uint64_t limit_bytes) {
 hipError_t launch_occurrences_chunk(const OccurrencesCall& c, void* d_scratch, uint64_t chunk_entries_max, uint64_t first_entry,
                                     uint64_t entries, uint32_t first_chunk) {
     if (entries == 0) return hipSuccess;
-    // (the caller has checked the call; what is checked here ties the launch to the LDS window and to the carved scratch)
-    if (entries > chunk_entries_max || c.n_query == 0 || c.n_query > 0x7FFFFFFFu || c.ne_max == 0 || c.ne_max > kOcCap ||
-        c.tiles == 0 || c.tiles != occurrences_tiles(c.n_query, c.ne_min, c.ne_max) || entries * c.tiles > kOcMaxItems ||
-        first_entry + entries > kMaxRaggedEntries || c.index_base + first_entry + entries > 0x100000000ull)
+    // (oc_call_ok's, and what ties the launch to the carved scratch and to the keys)
+    if (!oc_call_ok(c, occurrences_tiles(c.n_query, c.ne_min, c.ne_max), first_entry, entries) || entries > chunk_entries_max ||
+        c.index_base + first_entry + entries > 0x100000000ull)
         return hipErrorInvalidValue;
-    const float* tri = sliding_tri_table();
-    if (!tri) return hipErrorOutOfMemory;
+    size_t lds = 0;
+    const OcArgs a = oc_args(c, first_entry, entries, c.threshold, c.peaks, &lds);
+    if (!a.tri) return hipErrorOutOfMemory;
     const OcScratch s = oc_carve(d_scratch, chunk_entries_max, c.tiles);
-    const bool full = c.range >= c.subfp_len;
-    const uint4 m = pair_mask(full ? c.subfp_len : c.range);
-    const uint32_t ne_b = c.ne_max < c.n_query ? c.ne_max : c.n_query;
-    OcArgs a;
-    a.recs = c.d_recs; a.off = c.d_off; a.first = (uint32_t)first_entry; a.entries = (uint32_t)entries;
-    a.tiles = (uint32_t)c.tiles; a.groups = (uint32_t)oc_groups(c.tiles); a.ne_max = c.ne_max;
-    a.q = reinterpret_cast<const uint4*>(c.d_qwords); a.nq = c.n_query; a.win = kOcGroup + 2u + ne_b;
-    a.m[0] = m.x; a.m[1] = m.y; a.m[2] = m.z; a.m[3] = m.w; a.tri = tri; a.t = c.threshold; a.peaks = c.peaks ? 1u : 0u;
-    const size_t lds = occurrences_lds_bytes(c.n_query, c.ne_max);
-    return full ? launch_oc<true>(c, s, a, lds, first_chunk) : launch_oc<false>(c, s, a, lds, first_chunk);
+    return c.range >= c.subfp_len ? launch_oc<true>(c, s, a, lds, first_chunk) : launch_oc<false>(c, s, a, lds, first_chunk);
 }
 
 }  // namespace lbad

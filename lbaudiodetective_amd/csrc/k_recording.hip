@@ -47,41 +47,36 @@ __device__ __forceinline__ unsigned long long rec_wave_max(unsigned long long v)
     return best;
 }
 
-// Unit u = (entry block u / groups, tile group u % groups), as in occurrences_count_kernel.  partials[entry][tile] for every
+// Units of kOcEntries entries (oc_unit), as in occurrences_count_kernel.  partials[entry][tile] for every
 // tile below a.tiles.
 template <bool FULL>
 __global__ __launch_bounds__(kOcThreads) void recording_maxima_kernel(const OcArgs a, unsigned long long* __restrict__ partials) {
     extern __shared__ uint4 s_dyn[];
     const OcLds s = oc_lds(s_dyn, a.win);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t i = threadIdx.x; i < kTriSize; i += kOcThreads) s.tri[i] = a.tri[i];
-    const uint32_t units = ((a.entries + kOcEntries - 1u) / kOcEntries) * a.groups;
+    oc_load_tri(a, s);
+    const uint32_t units = oc_units(a, kOcEntries);
     for (uint32_t u = blockIdx.x; u < units; u += gridDim.x) {
-        const uint32_t eb = u / a.groups, g = u - eb * a.groups;
-        const uint32_t wb = g * kOcTileGroup - 1u;
-        __syncthreads();                                       // (the unit before has left the window)
-        oc_stage(a, s, wb);
-        __syncthreads();
-        const uint32_t tile = g * kOcWaves + wave;
-        if (tile >= a.tiles) continue;                         // (this wave meets no barrier of the unit any more)
-        const uint32_t e0 = eb * kOcEntries, e1 = a.entries - e0 < kOcEntries ? a.entries : e0 + kOcEntries;
-        const uint32_t first = tile * kOcTile;
+        const OcUnit n = oc_unit(a, u, kOcEntries, wave);
+        oc_stage_unit(a, s, n.wb);
+        if (n.tile >= a.tiles) continue;                       // (this wave meets no barrier of the unit any more)
+        const uint32_t first = n.tile * kOcTile;
         const uint32_t o = first - 1u + 2u * lane;
-        for (uint32_t e = e0; e < e1; ++e) {
+        for (uint32_t e = n.e0; e < n.e1; ++e) {
             uint32_t rec0, ne;
             oc_entry(a, e, &rec0, &ne);
             const uint32_t n_off = oc_offsets(a, ne);
             unsigned long long best = 0ull;
             if (first < n_off) {
                 float q0, q1;
-                (void)oc_cells<FULL>(a, s, wb, rec0, ne, o, &q0, &q1);
+                (void)oc_cells<FULL>(a, s, n.wb, rec0, ne, o, &q0, &q1);
                 // (lane 0's first and lane 63's second cell are the neighbouring tiles')
                 const unsigned long long v0 = lane != 0u && o < n_off ? ((unsigned long long)__float_as_uint(q0) << 32) | (0xFFFFFFFFu - o) : 0ull;
                 const unsigned long long v1 =
                     lane != 63u && o + 1u < n_off ? ((unsigned long long)__float_as_uint(q1) << 32) | (0xFFFFFFFFu - (o + 1u)) : 0ull;
                 best = rec_wave_max(v0 > v1 ? v0 : v1);
             }
-            if (lane == 0u) partials[(size_t)e * a.tiles + tile] = best;
+            if (lane == 0u) partials[(size_t)e * a.tiles + n.tile] = best;
         }
     }
 }
@@ -129,19 +124,10 @@ __global__ __launch_bounds__(kFoldThreads) void recording_lag_gather_kernel(cons
 
 template <bool FULL>
 hipError_t launch_maxima(const OcArgs& a, size_t lds, unsigned long long* partials, hipStream_t stream) {
-    // (the largest size this instance was set up for on each device, recorded once the call has succeeded; as launch_oc)
-    static size_t ready[kMaxDevices] = {};
-    const int dev = current_device();
-    if (dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;
-    if (lds > 48 * 1024 && lds > ready[dev]) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(recording_maxima_kernel<FULL>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        ready[dev] = lds;
-    }
-    const uint64_t units = oc_blocks(a.entries) * a.groups;
-    const dim3 grid((uint32_t)(units < kOcMaxGrid ? units : kOcMaxGrid));
-    hipLaunchKernelGGL(recording_maxima_kernel<FULL>, grid, dim3(kOcThreads), lds, stream, a, partials);
+    static size_t ready[kMaxDevices] = {};                     // (this instance)
+    const hipError_t e = oc_allow_lds(ready, lds, recording_maxima_kernel<FULL>);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(recording_maxima_kernel<FULL>, oc_grid(oc_blocks(a.entries) * a.groups), dim3(kOcThreads), lds, stream, a, partials);
     return hipGetLastError();
 }
 
@@ -160,24 +146,13 @@ uint64_t recording_chunk_entries(uint64_t tiles, uint64_t limit_bytes) {
 
 hipError_t launch_recording_chunk(const RecordingCall& c, void* d_scratch, uint64_t first_entry, uint64_t entries) {
     if (entries == 0) return hipSuccess;
-    // (the caller has checked the call; what is checked here ties the launch to the LDS window and to the scratch)
-    if (c.n_query == 0 || c.n_query > 0x7FFFFFFFu || c.ne_max == 0 || c.ne_max > kOcCap || c.tiles == 0 ||
-        c.tiles != occurrences_tiles(c.n_query, c.ne_min, c.ne_max) || entries * c.tiles > kOcMaxItems ||
-        first_entry + entries > kMaxRaggedEntries || !c.d_scores)
-        return hipErrorInvalidValue;
-    const float* tri = sliding_tri_table();
-    if (!tri) return hipErrorOutOfMemory;
-    const bool full = c.range >= c.subfp_len;
-    const uint4 m = pair_mask(full ? c.subfp_len : c.range);
-    const uint32_t ne_b = c.ne_max < c.n_query ? c.ne_max : c.n_query;
-    OcArgs a;
-    a.recs = c.d_recs; a.off = c.d_off; a.first = (uint32_t)first_entry; a.entries = (uint32_t)entries;
-    a.tiles = (uint32_t)c.tiles; a.groups = (uint32_t)oc_groups(c.tiles); a.ne_max = c.ne_max;
-    a.q = reinterpret_cast<const uint4*>(c.d_qwords); a.nq = c.n_query; a.win = kOcTileGroup + 2u + ne_b;
-    a.m[0] = m.x; a.m[1] = m.y; a.m[2] = m.z; a.m[3] = m.w; a.tri = tri; a.t = 0.0f; a.peaks = 0u;     // (no cell is tested here)
-    const size_t lds = occurrences_lds_bytes(c.n_query, c.ne_max);
+    if (!oc_call_ok(c, occurrences_tiles(c.n_query, c.ne_min, c.ne_max), first_entry, entries) || !c.d_scores) return hipErrorInvalidValue;
+    size_t lds = 0;
+    const OcArgs a = oc_args(c, first_entry, entries, 0.0f, false, &lds);          // (no cell is tested here)
+    if (!a.tri) return hipErrorOutOfMemory;
     unsigned long long* partials = static_cast<unsigned long long*>(d_scratch);
-    const hipError_t e = full ? launch_maxima<true>(a, lds, partials, c.stream) : launch_maxima<false>(a, lds, partials, c.stream);
+    const hipError_t e =
+        c.range >= c.subfp_len ? launch_maxima<true>(a, lds, partials, c.stream) : launch_maxima<false>(a, lds, partials, c.stream);
     if (e != hipSuccess) return e;
     uint32_t lanes = 1;
     while (lanes < 64u && lanes < c.tiles) lanes <<= 1;

@@ -35,7 +35,7 @@ constexpr uint32_t kTlFoldRows = 32;                   // rows a workgroup of th
 constexpr uint32_t kTlFoldSlices = 1024;               // slices of the first level at most (the second level's rows)
 static_assert(kTlEntries % kOcEntries == 0 && kTlEntries != 0, "a unit is whole entry blocks of the occurrences pass");
 
-// Unit u = (entry block u / groups, tile group u % groups), entry blocks of kTlEntries.  key_low - e is the low word of chunk
+// Units of kTlEntries entries (oc_unit).  key_low - e is the low word of chunk
 // entry e's key.  partials[entry block][a.tiles x kOcTile].
 template <bool FULL>
 __global__ __launch_bounds__(kOcThreads) void timeline_maxima_kernel(const OcArgs a, uint32_t key_low,
@@ -43,27 +43,22 @@ __global__ __launch_bounds__(kOcThreads) void timeline_maxima_kernel(const OcArg
     extern __shared__ uint4 s_dyn[];
     const OcLds s = oc_lds(s_dyn, a.win);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t i = threadIdx.x; i < kTriSize; i += kOcThreads) s.tri[i] = a.tri[i];
-    const uint32_t units = ((a.entries + kTlEntries - 1u) / kTlEntries) * a.groups;
+    oc_load_tri(a, s);
+    const uint32_t units = oc_units(a, kTlEntries);
     for (uint32_t u = blockIdx.x; u < units; u += gridDim.x) {
-        const uint32_t eb = u / a.groups, g = u - eb * a.groups;
-        const uint32_t wb = g * kOcTileGroup - 1u;
-        __syncthreads();                                       // (the unit before has left the window)
-        oc_stage(a, s, wb);
-        __syncthreads();
-        const uint32_t tile = g * kOcWaves + wave;
-        if (tile >= a.tiles) continue;                         // (this wave meets no barrier of the unit any more)
-        const uint32_t e0 = eb * kTlEntries, e1 = a.entries - e0 < kTlEntries ? a.entries : e0 + kTlEntries;
-        const uint32_t first = tile * kOcTile;
+        const OcUnit n = oc_unit(a, u, kTlEntries, wave);
+        oc_stage_unit(a, s, n.wb);
+        if (n.tile >= a.tiles) continue;                       // (this wave meets no barrier of the unit any more)
+        const uint32_t first = n.tile * kOcTile;
         const uint32_t o = first - 1u + 2u * lane;
         unsigned long long best0 = 0ull, best1 = 0ull;
-        for (uint32_t e = e0; e < e1; ++e) {
+        for (uint32_t e = n.e0; e < n.e1; ++e) {
             uint32_t rec0, ne;
             oc_entry(a, e, &rec0, &ne);
             if (ne > a.nq || first >= a.nq - ne + 1u) continue;            // (wave-uniform: no place inside the query, or none in this tile)
             float q0, q1;
             // (bit 0 / 1: the cell is the wave's own, o < n_off and q >= t)
-            const uint32_t bits = oc_cells<FULL>(a, s, wb, rec0, ne, o, &q0, &q1);
+            const uint32_t bits = oc_cells<FULL>(a, s, n.wb, rec0, ne, o, &q0, &q1);
             const uint32_t low = key_low - e;
             const unsigned long long v0 = bits & 1u ? ((unsigned long long)__float_as_uint(q0) << 32) | low : 0ull;
             const unsigned long long v1 = bits & 2u ? ((unsigned long long)__float_as_uint(q1) << 32) | low : 0ull;
@@ -71,7 +66,7 @@ __global__ __launch_bounds__(kOcThreads) void timeline_maxima_kernel(const OcArg
             best1 = v1 > best1 ? v1 : best1;
         }
         // (cell o is the tile's 2 x lane - 1, cell o + 1 its 2 x lane; lane 0's first and lane 63's second are the neighbours')
-        unsigned long long* __restrict__ row = partials + ((size_t)eb * a.tiles + tile) * kOcTile;
+        unsigned long long* __restrict__ row = partials + ((size_t)n.eb * a.tiles + n.tile) * kOcTile;
         if (lane != 0u) row[2u * lane - 1u] = best0;
         if (lane != 63u) row[2u * lane] = best1;
     }
@@ -116,25 +111,17 @@ __global__ __launch_bounds__(kTlFoldThreads) void timeline_lengths_kernel(const 
     lengths[o] = key != 0ull && j < count ? off[j + 1u] - off[j] : 0u;
 }
 
+inline uint64_t tl_blocks(uint64_t entries) { return (entries + kTlEntries - 1) / kTlEntries; }
+
 template <bool FULL>
 hipError_t launch_tl_maxima(const OcArgs& a, size_t lds, uint32_t key_low, unsigned long long* partials, hipStream_t stream) {
-    // (the largest size this instance was set up for on each device, recorded once the call has succeeded; as launch_oc)
-    static size_t ready[kMaxDevices] = {};
-    const int dev = current_device();
-    if (dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;
-    if (lds > 48 * 1024 && lds > ready[dev]) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(timeline_maxima_kernel<FULL>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        ready[dev] = lds;
-    }
-    const uint64_t units = (uint64_t)((a.entries + kTlEntries - 1u) / kTlEntries) * a.groups;
-    const dim3 grid((uint32_t)(units < kOcMaxGrid ? units : kOcMaxGrid));
-    hipLaunchKernelGGL(timeline_maxima_kernel<FULL>, grid, dim3(kOcThreads), lds, stream, a, key_low, partials);
+    static size_t ready[kMaxDevices] = {};                     // (this instance)
+    const hipError_t e = oc_allow_lds(ready, lds, timeline_maxima_kernel<FULL>);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(timeline_maxima_kernel<FULL>, oc_grid(tl_blocks(a.entries) * a.groups), dim3(kOcThreads), lds, stream, a, key_low,
+                       partials);
     return hipGetLastError();
 }
-
-inline uint64_t tl_blocks(uint64_t entries) { return (entries + kTlEntries - 1) / kTlEntries; }
 
 }  // namespace
 
@@ -158,26 +145,17 @@ uint64_t timeline_chunk_entries(uint64_t tiles, uint64_t limit_bytes) {
 
 hipError_t launch_timeline_chunk(const TimelineCall& c, void* d_scratch, uint64_t first_entry, uint64_t entries) {
     if (entries == 0) return hipSuccess;
-    // (the caller has checked the call; what is checked here ties the launch to the LDS window, to the scratch and to the keys)
-    if (c.n_query == 0 || c.n_query > 0x7FFFFFFFu || c.ne_max == 0 || c.ne_max > kOcCap || c.ne_min > c.n_query || c.tiles == 0 ||
-        c.tiles != timeline_tiles(c.n_query, c.ne_min) || entries * c.tiles > kOcMaxItems || first_entry + entries > kMaxRaggedEntries ||
+    // (oc_call_ok's, and what ties the launch to the entries that take part and to the keys)
+    if (!oc_call_ok(c, timeline_tiles(c.n_query, c.ne_min), first_entry, entries) || c.ne_min > c.n_query ||
         c.index_base + first_entry + entries > 0x100000000ull || !c.d_keys)
         return hipErrorInvalidValue;
-    const float* tri = sliding_tri_table();
-    if (!tri) return hipErrorOutOfMemory;
-    const bool full = c.range >= c.subfp_len;
-    const uint4 m = pair_mask(full ? c.subfp_len : c.range);
-    const uint32_t ne_b = c.ne_max < c.n_query ? c.ne_max : c.n_query;
-    OcArgs a;
-    a.recs = c.d_recs; a.off = c.d_off; a.first = (uint32_t)first_entry; a.entries = (uint32_t)entries;
-    a.tiles = (uint32_t)c.tiles; a.groups = (uint32_t)oc_groups(c.tiles); a.ne_max = c.ne_max;
-    a.q = reinterpret_cast<const uint4*>(c.d_qwords); a.nq = c.n_query; a.win = kOcTileGroup + 2u + ne_b;
-    a.m[0] = m.x; a.m[1] = m.y; a.m[2] = m.z; a.m[3] = m.w; a.tri = tri; a.t = c.threshold; a.peaks = 0u;
-    const size_t lds = occurrences_lds_bytes(c.n_query, c.ne_max);
+    size_t lds = 0;
+    const OcArgs a = oc_args(c, first_entry, entries, c.threshold, false, &lds);
+    if (!a.tri) return hipErrorOutOfMemory;
     unsigned long long* partials = static_cast<unsigned long long*>(d_scratch);
     const uint32_t key_low = 0xFFFFFFFFu - (uint32_t)c.index_base - a.first;
-    const hipError_t e =
-        full ? launch_tl_maxima<true>(a, lds, key_low, partials, c.stream) : launch_tl_maxima<false>(a, lds, key_low, partials, c.stream);
+    const hipError_t e = c.range >= c.subfp_len ? launch_tl_maxima<true>(a, lds, key_low, partials, c.stream)
+                                                : launch_tl_maxima<false>(a, lds, key_low, partials, c.stream);
     if (e != hipSuccess) return e;
     // the offsets a pair reaches lie below tiles x 126; the words of out beyond them stay the caller's zeros
     const uint64_t stride = c.tiles * kOcTile;

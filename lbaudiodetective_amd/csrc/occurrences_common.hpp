@@ -1,5 +1,6 @@
 // occurrences_common.hpp -- the pair loop of the occurrences pass, shared by the files whose kernels run it: k_occurrences.hip
-// (the cells at or above a score as a list) and k_recording.hip (the cells folded to a maximum per entry).  k_occurrences.hip's
+// (the cells at or above a score as a list), k_recording.hip (the cells folded to a maximum per entry) and k_timeline.hip (to
+// the best entry per offset) -- its device side, the head of their kernels and the launch side of a chunk.  k_occurrences.hip's
 // head states the loop: a work item is (entry, tile of kOcTile offsets), a wave computes the tile's cells and one more on each
 // side, a lane owns two neighbouring offsets, the query's window is prepared once per block of kOcEntries entries into LDS and
 // fingerprint2's record of a step comes through the scalar unit.  Everything here is per file (an unnamed namespace), as in
@@ -194,8 +195,72 @@ __device__ __forceinline__ void oc_entry(const OcArgs& a, uint32_t e, uint32_t* 
 // offsets of the pair (query, entry of ne sub-fingerprints)
 __device__ __forceinline__ uint32_t oc_offsets(const OcArgs& a, uint32_t ne) { return a.nq < ne ? ne - a.nq + 1u : a.nq - ne + 1u; }
 
+// The head of a pair-loop kernel.  The table into LDS (a unit's first barrier stands between this and the first read):
+__device__ __forceinline__ void oc_load_tri(const OcArgs& a, const OcLds& s) {
+    for (uint32_t i = threadIdx.x; i < kTriSize; i += kOcThreads) s.tri[i] = a.tri[i];
+}
+// units of a kernel whose units walk `walk` entries: unit u = (entry block u / groups, tile group u % groups), so workgroups
+// that run at the same time share their entries' records
+__device__ __forceinline__ uint32_t oc_units(const OcArgs& a, uint32_t walk) { return ((a.entries + walk - 1u) / walk) * a.groups; }
+struct OcUnit {
+    uint32_t eb, wb;              // the entry block; the window's first record (the group's first offset - 1, wrapping below 0)
+    uint32_t tile;                // this wave's tile (`wave` is the kernel's threadIdx.x >> 6): it takes part when tile < a.tiles
+    uint32_t e0, e1;              // the block's entries of the chunk
+};
+__device__ __forceinline__ OcUnit oc_unit(const OcArgs& a, uint32_t u, uint32_t walk, uint32_t wave) {
+    OcUnit n;
+    n.eb = u / a.groups;
+    const uint32_t g = u - n.eb * a.groups;
+    n.wb = g * kOcTileGroup - 1u;
+    n.tile = g * kOcWaves + wave;
+    n.e0 = n.eb * walk;
+    n.e1 = a.entries - n.e0 < walk ? a.entries : n.e0 + walk;
+    return n;
+}
+// the window of a unit staged once the unit before has left it
+__device__ __forceinline__ void oc_stage_unit(const OcArgs& a, const OcLds& s, uint32_t wb) {
+    __syncthreads();
+    oc_stage(a, s, wb);
+    __syncthreads();
+}
+
 inline uint64_t oc_groups(uint64_t tiles) { return (tiles + kOcWaves - 1) / kOcWaves; }
 inline uint64_t oc_blocks(uint64_t entries) { return (entries + kOcEntries - 1) / kOcEntries; }
+inline dim3 oc_grid(uint64_t units) { return dim3((uint32_t)(units < kOcMaxGrid ? units : kOcMaxGrid)); }
+
+// The launch side of a chunk.  What every family checks of a call (the caller has checked it; this ties the launch to the LDS
+// window and to the scratch): `tiles` is the family's bound for the call
+inline bool oc_call_ok(const OcPassCall& c, uint64_t tiles, uint64_t first_entry, uint64_t entries) {
+    return c.n_query != 0 && c.n_query <= 0x7FFFFFFFu && c.ne_max != 0 && c.ne_max <= kOcCap && c.tiles != 0 && c.tiles == tiles &&
+           entries * c.tiles <= kOcMaxItems && first_entry + entries <= kMaxRaggedEntries;
+}
+// the kernels' arguments for `entries` entries from `first_entry` (a.tri == nullptr: no table), and the LDS of a workgroup
+inline OcArgs oc_args(const OcPassCall& c, uint64_t first_entry, uint64_t entries, float threshold, bool peaks, size_t* lds) {
+    const uint4 m = pair_mask(c.range >= c.subfp_len ? c.subfp_len : c.range);
+    const uint32_t ne_b = c.ne_max < c.n_query ? c.ne_max : c.n_query;
+    OcArgs a;
+    a.recs = c.d_recs; a.off = c.d_off; a.first = (uint32_t)first_entry; a.entries = (uint32_t)entries;
+    a.tiles = (uint32_t)c.tiles; a.groups = (uint32_t)oc_groups(c.tiles); a.ne_max = c.ne_max;
+    a.q = reinterpret_cast<const uint4*>(c.d_qwords); a.nq = c.n_query; a.win = kOcTileGroup + 2u + ne_b;
+    a.m[0] = m.x; a.m[1] = m.y; a.m[2] = m.z; a.m[3] = m.w; a.tri = sliding_tri_table(); a.t = threshold; a.peaks = peaks ? 1u : 0u;
+    *lds = occurrences_lds_bytes(c.n_query, c.ne_max);
+    return a;
+}
+// Dynamic LDS above 48 KiB has to be allowed per kernel and device.  `ready`: the largest size every kernel of the set was set
+// up for on each device -- the caller's static, one per kernel set -- recorded once EVERY call has succeeded (not PerDevice:
+// that helper records before the set-up has succeeded.  Unsynchronised like it; two host threads that race here set the
+// attribute twice at worst)
+template <typename... Kernels>
+hipError_t oc_allow_lds(size_t (&ready)[kMaxDevices], size_t lds, Kernels... kernels) {
+    const int dev = current_device();
+    if (dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;
+    if (lds <= 48 * 1024 || lds <= ready[dev]) return hipSuccess;
+    hipError_t e = hipSuccess;
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...})
+        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) ready[dev] = lds;
+    return e;
+}
 
 }  // namespace
 }  // namespace lbad

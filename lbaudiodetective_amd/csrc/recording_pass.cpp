@@ -1,0 +1,99 @@
+// recording_pass.cpp -- the host side that the three families of the occurrences pass share (api_occurrences.cpp,
+// api_recording.cpp, api_timeline.cpp): the plan of a call, the staging of its query, the events that keep one call's scratch
+// from the next call on another stream, and the key block of the host-returning forms.  internal.hpp states each piece.
+#include "internal.hpp"
+
+#include <cstring>
+
+namespace lbad {
+
+OSStatus pass_plan(const LBAudioDetectiveCorpus* c, const PassQuery& q, uint64_t index_base, const PassFamily& fam, PassPlan* plan) {
+    const uint32_t n_query = q.fp ? q.fp->count : q.per;
+    if (!c->ragged || (q.fp ? q.fp->length : c->subfp_len) != c->subfp_len || n_query == 0 || n_query > 0x7FFFFFFFu ||
+        c->ne_max > LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS || index_base + c->count > 0x100000000ull)
+        return kLBAudioDetectiveArgumentInvalid;
+    *plan = PassPlan();
+    OcPassCall& call = plan->call;
+    call.d_recs = c->d_recs; call.d_off = c->d_off; call.ne_max = c->ne_max; call.subfp_len = c->subfp_len;
+    call.range = q.range ? q.range : c->subfp_len; call.n_query = n_query; call.tiles = 1;
+    if (c->count == 0) return noErr;
+    call.ne_min = c->len_hist.begin()->first;
+    call.tiles = fam.tiles(n_query, call.ne_min, c->ne_max);
+    const uint64_t limit = c->join_scratch_limit ? c->join_scratch_limit : kJoinScratchDefault;
+    const uint64_t chunk = fam.chunk_entries(call.tiles, limit), block = fam.block_entries();
+    if (chunk == 0) return kLBAudioDetectiveArgumentInvalid;          // the limit holds no block of entries at this query length
+    plan->chunk = chunk < c->count ? chunk : (c->count + block - 1) / block * block;
+    plan->any = call.ne_min <= n_query;
+    return noErr;
+}
+
+PassGuard::PassGuard(LBAudioDetectiveCorpus* c, const PassQuery& q, bool topk) {
+    ev[0] = &c->join_ev;
+    ev[1] = q.fp ? &c->align_ev : &c->pq_ev;
+    ev[2] = topk ? &c->topk_ev : nullptr;
+}
+
+OSStatus PassGuard::wait() {
+    OSStatus st = noErr;
+    for (Event* e : ev)
+        if (e && st == noErr) st = e->wait_or_create();
+    return st;
+}
+
+OSStatus PassGuard::finish(hipStream_t stream, OSStatus st) {
+    for (Event* e : ev) {
+        const OSStatus rec = e ? e->record(stream) : noErr;
+        if (st == noErr) st = rec;
+    }
+    return st;
+}
+
+OSStatus pass_stage_query(LBAudioDetectiveCorpus* c, const PassQuery& q, hipStream_t stream, OcPassCall* call) {
+    OSStatus st;
+    if (q.fp) {
+        std::vector<uint32_t> words;
+        build_align_query(q.fp, true, words);
+        st = c->align_q.reserve(words.size());
+        if (st != noErr) return st;
+        std::memcpy(c->align_q.host, words.data(), words.size() * sizeof(uint32_t));
+        call->d_qwords = c->align_q.dev;
+        st = hip_status(hipMemcpyAsync(c->align_q.dev, c->align_q.host, words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream),
+                        "query words", __LINE__);
+    } else {
+        st = c->d_pq.reserve((size_t)q.per * kPackedWords);
+        if (st != noErr) return st;
+        call->d_qwords = c->d_pq;
+        st = hip_status(launch_build_query_rows(q.d_rows, 1, q.per, c->subfp_len, true, c->d_pq, nullptr, stream), "query words", __LINE__);
+    }
+    call->stream = stream;
+    if (st == noErr && c->append_event.ev) LBAD_HIP(hipStreamWaitEvent(stream, c->append_event, 0));
+    return st;
+}
+
+OSStatus key_block_reserve(LBAudioDetectiveCorpus* c, size_t n_keys, size_t n_words, KeyBlock* b) {
+    OSStatus st = c->topk_ev.wait();
+    if (st == noErr) st = c->d_topk_keys.reserve(n_keys + (n_words + 1) / 2);
+    if (st != noErr) return st;
+    b->d_keys = c->d_topk_keys;
+    b->d_words = n_words ? reinterpret_cast<uint32_t*>(b->d_keys + n_keys) : nullptr;
+    b->n_keys = n_keys;
+    return noErr;
+}
+
+OSStatus key_block_read(const KeyBlock& b, size_t m, std::vector<unsigned long long>* host) {
+    host->assign(m + (b.d_words ? (m + 1) / 2 : 0), 0ull);
+    if (m == b.n_keys) {
+        LBAD_HIP(hipMemcpy(host->data(), b.d_keys, host->size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    } else if (m) {
+        LBAD_HIP(hipMemcpy(host->data(), b.d_keys, m * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (b.d_words) LBAD_HIP(hipMemcpy(host->data() + m, b.d_words, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return noErr;
+}
+
+OSStatus key_block_failed(OSStatus st) {
+    (void)hipStreamSynchronize(nullptr);
+    return st;
+}
+
+}  // namespace lbad

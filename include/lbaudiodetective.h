@@ -1033,6 +1033,16 @@ OSStatus LBAudioDetectiveDebugSlidingChoice(const UInt32* inEntryLengths, const 
  * single calls included.  The process-wide contexts of the pair compare, the Frame API and the sharded query, and what
  * LBAudioDetectiveDeviceMalloc hands out, are not counted.  Needs no device. */
 OSStatus LBAudioDetectiveDebugLiveBytes(UInt64* outDevice, UInt64* outPinned);
+/* Debug / TESTS ONLY: a process-wide ceiling on the workgroups of every launch whose workgroups walk work items beyond their
+ * grid with a stride and carry state in LDS from one item to the next -- the occurrences, recording and timeline passes, both
+ * joins and their row scan, the alignment's three launches and the threshold list's count and scatter.  Each of them launches
+ * min(its work, its built-in ceiling, inWorkgroups) workgroups, never fewer than 1; 0 (the default) restores the built-in
+ * ceilings alone.  Results NEVER depend on the value: it only decides how many work items one workgroup takes, which is how a
+ * test of seconds reaches the trips that otherwise need a corpus of a million entries.  The second call reports the ceiling
+ * and how many launches of this process so far had a grid below their work (it never decreases); it fails with
+ * kLBAudioDetectiveArgumentInvalid when a pointer is NULL.  Neither needs a device. */
+OSStatus LBAudioDetectiveDebugSetGridCeiling(UInt32 inWorkgroups);
+OSStatus LBAudioDetectiveDebugGridCeiling(UInt32* outWorkgroups, UInt64* outStridedLaunches);
 /* Binary corpus file ("LBADCRP1" header + the stored entries' planes; a ragged corpus: "LBADCRP2" header + the
  * entries' sub-fingerprint counts + the records); Load recognises both, reserves max(inCapacity, stored count)
  * entries and, for a ragged corpus, records in proportion. */

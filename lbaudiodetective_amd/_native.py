@@ -235,6 +235,8 @@ _SIGNATURES = {
     "LBAudioDetectiveDebugSlidingChoice": (OSStatus, [_P(UInt32), _P(UInt64), UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, UInt32, UInt32,
                                                       UInt32, UInt32, UInt32, _P(UInt32), UInt32]),
     "LBAudioDetectiveDebugLiveBytes": (OSStatus, [_P(UInt64), _P(UInt64)]),
+    "LBAudioDetectiveDebugSetGridCeiling": (OSStatus, [UInt32]),
+    "LBAudioDetectiveDebugGridCeiling": (OSStatus, [_P(UInt32), _P(UInt64)]),
     "LBAudioDetectiveCorpusSetKernelVariant": (OSStatus, [Ref, UInt32]),
     "LBAudioDetectiveCorpusSave": (OSStatus, [Ref, C.c_char_p]),
     "LBAudioDetectiveCorpusLoad": (Ref, [C.c_char_p, UInt64]),

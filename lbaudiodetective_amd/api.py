@@ -1420,6 +1420,19 @@ def debug_live_bytes():
     return dev.value, pinned.value
 
 
+def debug_set_grid_ceiling(workgroups: int) -> None:
+    """LBAudioDetectiveDebugSetGridCeiling (tests only): at most `workgroups` workgroups for every launch that walks its work
+    items with a grid stride and LDS state carried between them; 0 restores the built-in ceilings.  Results never depend on it."""
+    _check(N.lib().LBAudioDetectiveDebugSetGridCeiling(int(workgroups)), "DebugSetGridCeiling")
+
+
+def debug_grid_ceiling():
+    """LBAudioDetectiveDebugGridCeiling (tests): (the ceiling, launches of this process so far whose grid was below their work)."""
+    n, strided = N.UInt32(0), N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveDebugGridCeiling(C.byref(n), C.byref(strided)), "DebugGridCeiling")
+    return n.value, strided.value
+
+
 class Comm:
     """An RCCL communicator made through the library's helpers (ncclCommInitRank with the current device).
     `unique_id()` on rank 0, the 128 bytes travel to the other ranks by whatever means the host has, then every

@@ -1131,6 +1131,16 @@ OSStatus LBAudioDetectiveDebugLiveBytes(UInt64* outDevice, UInt64* outPinned) {
     *outPinned = lbad::g_live_bytes[1].load();
     return noErr;
 }
+OSStatus LBAudioDetectiveDebugSetGridCeiling(UInt32 inWorkgroups) {
+    lbad::g_grid_ceiling.store(inWorkgroups);
+    return noErr;
+}
+OSStatus LBAudioDetectiveDebugGridCeiling(UInt32* outWorkgroups, UInt64* outStridedLaunches) {
+    if (!outWorkgroups || !outStridedLaunches) return kLBAudioDetectiveArgumentInvalid;
+    *outWorkgroups = lbad::g_grid_ceiling.load();
+    *outStridedLaunches = lbad::g_strided_launches.load();
+    return noErr;
+}
 OSStatus LBAudioDetectiveDeviceSynchronize(void) {
     LBAD_HIP(hipDeviceSynchronize());
     return noErr;

@@ -50,6 +50,20 @@ struct PerDevice {
     }
 };
 
+// The grid of a launch whose workgroups carry state in LDS from one work item to the next (w += gridDim.x): the work, at most
+// the launcher's own ceiling, at most the tests' ceiling where one is set (LBAudioDetectiveDebugSetGridCeiling; 0: none) --
+// never 0 for work > 0.  Results do not depend on the grid; a launch that really strides (a grid below its work) is counted.
+inline std::atomic<uint32_t> g_grid_ceiling{0};
+inline std::atomic<uint64_t> g_strided_launches{0};
+inline uint32_t strided_grid(uint64_t work, uint32_t built_in_ceiling) {
+    uint64_t grid = work < built_in_ceiling ? work : built_in_ceiling;
+    const uint32_t tests = g_grid_ceiling.load(std::memory_order_relaxed);
+    if (tests != 0 && grid > tests) grid = tests;
+    if (grid == 0 && work > 0) grid = 1;
+    if (grid < work) g_strided_launches.fetch_add(1, std::memory_order_relaxed);
+    return (uint32_t)grid;
+}
+
 // ---- per-configuration device plan ---------------------------------------------------------
 struct BandTable {
     std::vector<uint32_t> indices;  // bands + 1

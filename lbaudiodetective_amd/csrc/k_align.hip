@@ -318,7 +318,7 @@ hipError_t launch_align_keys(const AlignSource& src, const uint32_t* d_qwords, c
     if (parts > 1 && !d_best) return hipErrorInvalidValue;
     const AlignArgs a = make_args(src, index_base);
     const uint64_t work = pairs * parts;
-    const dim3 grid((uint32_t)(work < kAlMaxGrid ? work : kAlMaxGrid));
+    const dim3 grid(strided_grid(work, kAlMaxGrid));
     if (parts > 1) {
         const hipError_t e = hipMemsetAsync(d_best, 0, pairs * sizeof(unsigned long long), stream);
         if (e != hipSuccess) return e;
@@ -331,7 +331,7 @@ hipError_t launch_align_keys(const AlignSource& src, const uint32_t* d_qwords, c
                            d_best, d_lags, d_scores);
     if (parts > 1) {
         const uint64_t blocks = (pairs + kFinishThreads - 1) / kFinishThreads;
-        const dim3 fgrid((uint32_t)(blocks < kAlMaxGrid ? blocks : kAlMaxGrid));
+        const dim3 fgrid(strided_grid(blocks, kAlMaxGrid));
         if (src.ragged)
             hipLaunchKernelGGL(align_finish_kernel<true>, fgrid, dim3(kFinishThreads), 0, stream, a, d_qwords, d_qdesc, d_keys, k, pairs,
                                d_best, d_lags, d_scores);
@@ -347,7 +347,7 @@ hipError_t launch_align_profile(const AlignSource& src, const uint32_t* d_qwords
     if (n_offsets == 0) return hipSuccess;
     const AlignArgs a = make_args(src, 0);
     const uint64_t tiles = tiles_of(n_offsets);
-    const dim3 grid((uint32_t)(tiles < kAlMaxGrid ? tiles : kAlMaxGrid));
+    const dim3 grid(strided_grid(tiles, kAlMaxGrid));
     if (src.ragged)
         hipLaunchKernelGGL(align_profile_kernel<true>, grid, dim3(kAlThreads), 0, stream, a, d_qwords, n_query, entry, d_out);
     else

@@ -397,7 +397,7 @@ JoinScratch join_carve(void* d_scratch, uint64_t n_entries, uint32_t rows) {
 // count -> offsets: the row scan and the offsets kernel, for this file's join and for k_join_ragged.hip's (the same counts layout)
 void launch_join_scans(const uint32_t* counts, uint64_t etiles, uint32_t rows, uint32_t* tile_at, unsigned long long* row_base,
                        unsigned long long* state, uint32_t first_chunk, unsigned long long* out_offsets, hipStream_t stream) {
-    hipLaunchKernelGGL(join_row_scan_kernel, dim3(rows < kJoinScanMaxGrid ? rows : kJoinScanMaxGrid), dim3(kJoinScanThreads), 0, stream,
+    hipLaunchKernelGGL(join_row_scan_kernel, dim3(strided_grid(rows, kJoinScanMaxGrid)), dim3(kJoinScanThreads), 0, stream,
                        counts, etiles, rows, tile_at, row_base);
     hipLaunchKernelGGL(join_offsets_kernel, dim3(1), dim3(kJoinScanThreads), 0, stream, row_base, rows, state, first_chunk, out_offsets);
 }
@@ -407,7 +407,7 @@ namespace {
 template <int NSUB>
 hipError_t launch_join_n(const JoinCall& c, const JoinScratch& s, const JoinPairs& a, uint64_t items, uint32_t first_chunk,
                          unsigned long long* out_offsets) {
-    const dim3 grid((uint32_t)(items < kJoinMaxGrid ? items : kJoinMaxGrid));
+    const dim3 grid(strided_grid(items, kJoinMaxGrid));
     hipLaunchKernelGGL(join_count_kernel<NSUB>, grid, dim3(kJoinThreads), 0, c.stream, a, s.counts, s.any);
     launch_join_scans(s.counts, a.etiles, a.rows, s.tile_at, s.row_base, s.state, first_chunk, out_offsets, c.stream);
     hipLaunchKernelGGL(join_scatter_kernel<NSUB>, grid, dim3(kJoinThreads), 0, c.stream, a, s.counts, s.any, s.tile_at, s.row_base,

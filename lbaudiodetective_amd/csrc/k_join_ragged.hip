@@ -385,7 +385,7 @@ JrScratch jr_carve(void* d_scratch, uint64_t n_entries, uint32_t rows) {
 template <bool FULL>
 hipError_t launch_jr(const JoinRaggedCall& c, const JrScratch& s, const JrArgs& a, uint32_t items, uint32_t first_chunk,
                      unsigned long long* out_offsets) {
-    const dim3 grid((uint32_t)(items < kJrMaxGrid ? items : kJrMaxGrid));
+    const dim3 grid(strided_grid(items, kJrMaxGrid));
     const size_t row_bytes = ((size_t)a.row_cap + 1u) * 32u;
     hipLaunchKernelGGL(join_ragged_count_kernel<FULL>, grid, dim3(kJrThreads), row_bytes, c.stream, a, s.counts, s.any);
     launch_join_scans(s.counts, a.etiles, a.rows, s.tile_at, s.row_base, s.state, first_chunk, out_offsets, c.stream);

@@ -222,7 +222,7 @@ hipError_t launch_threshold_keys(const float* d_scores, uint64_t n, uint32_t row
     const uint64_t tiles = th_tiles(n), items = tiles * rows;
     unsigned long long* offsets = static_cast<unsigned long long*>(d_scratch);
     uint32_t* counts = reinterpret_cast<uint32_t*>(offsets + items);
-    const dim3 grid((uint32_t)(items < kThMaxGrid ? items : kThMaxGrid));
+    const dim3 grid(strided_grid(items, kThMaxGrid));
     hipLaunchKernelGGL(threshold_count_kernel, grid, dim3(kThThreads), 0, stream, d_scores, n, rows, tiles, threshold, counts);
     hipLaunchKernelGGL(threshold_offsets_kernel, dim3(rows), dim3(kThThreads), 0, stream, counts, tiles, offsets, d_counts);
     hipLaunchKernelGGL(threshold_scatter_kernel, grid, dim3(kThThreads), 0, stream, d_scores, n, rows, tiles, threshold, capacity,

@@ -226,7 +226,7 @@ __device__ __forceinline__ void oc_stage_unit(const OcArgs& a, const OcLds& s, u
 
 inline uint64_t oc_groups(uint64_t tiles) { return (tiles + kOcWaves - 1) / kOcWaves; }
 inline uint64_t oc_blocks(uint64_t entries) { return (entries + kOcEntries - 1) / kOcEntries; }
-inline dim3 oc_grid(uint64_t units) { return dim3((uint32_t)(units < kOcMaxGrid ? units : kOcMaxGrid)); }
+inline dim3 oc_grid(uint64_t units) { return dim3(strided_grid(units, kOcMaxGrid)); }
 
 // The launch side of a chunk.  What every family checks of a call (the caller has checked it; this ties the launch to the LDS
 // window and to the scratch): `tiles` is the family's bound for the call

@@ -10,9 +10,10 @@
 //   * column pass: eight threads per column, 16 values each, levels 1..4 in registers, levels
 //     5..7 with three lane exchanges; every thread ends up owning 16 final coefficients whose
 //     flat positions are known in closed form, so the select works on registers;
-//   * select: bisect the |v| bit patterns for a threshold that leaves [keep, 128] candidates
-//     (one workgroup reduction per step), then rank only the candidates by the composite key
-//     (|v| bits, lower flat index first) and emit the sign pairs of ranks < keep.
+//   * select: a histogram over the 11 leading bits of |v| (then, rarely, a bisection of the bit patterns) finds a threshold
+//     that leaves [keep, 128] candidates; the candidates are gathered BY BUCKET, highest first, and each is ranked by the
+//     composite key (|v| bits, lower flat index first) against its own bucket's segment only -- all pairs where a bucket
+//     is crowded -- and the sign pairs of ranks < keep are emitted.
 //
 // Every arithmetic operation is the reference's: x / sqrtf(n) pre-scale, (a +- b) / sqrtf(2)
 // butterflies, correctly rounded divisions.
@@ -31,6 +32,22 @@ constexpr int kChunkDw = 20;        // 16 floats + 4 pad: conflict-free ds_read_
 // caller redoes a whole line with true divisions when a lane saw a dividend outside the proven range.
 
 constexpr uint32_t kHistBuckets = 2048;   // |v| bits >> 20
+
+// The candidate list is laid out BY BUCKET (the gather takes a key's slot from its own bucket's word), and a candidate is
+// ranked against its bucket's segment only.  A frame with a segment longer than kSegCap keeps the all-pairs ranking.
+// 64: tools/stage2_bucket_study.py (profiles/stage2_bucket_study.json) finds the longest segment of a frame at 21 keys on
+// average and never above 50 (bench clips, bird fixtures at two configurations), so no ordinary frame leaves the segment
+// loop; and 64 is where that loop stops being the cheaper one -- four keys and eleven vector instructions a trip: sixteen
+// trips = 176 instructions on the two waves that hold candidates, against five trips of 36 on every wave for all pairs, whose
+// five LDS round trips a wave with such a segment would wait for more than three times over.
+constexpr uint32_t kSegCap = 64;
+constexpr uint32_t kCursorStep = 8;                     // a bucket's cursor counts the bytes of its keys in the list
+#if defined(LBAD_EXP_NO_HISTOGRAM) || defined(LBAD_EXP_GATHER_BALLOT)
+#define LBAD_ONE_CURSOR 1
+constexpr bool kBucketList = false;       // these experiments fill the list through ONE cursor: all-pairs ranking only
+#else
+constexpr bool kBucketList = true;
+#endif
 
 // inclusive prefix sum over the 64 lanes of a wave (full EXEC): four row shifts, two row broadcasts (gfx9 DPP)
 __device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t x) {
@@ -416,13 +433,17 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
     constexpr int H = COLS / 16;                     // threads per row in the row pass
     constexpr uint32_t kIdxBits = COLS == 16 ? 11 : COLS == 32 ? 12 : 13;   // flat index of a coefficient
     __shared__ __attribute__((aligned(16))) float s_t[(SPARSE ? kSparseCols : kCols) * 8 * kChunkDw];   // [col (sparse: slot)][chunk][20]
-    __shared__ __attribute__((aligned(16))) unsigned long long s_cand[kCand];
-    __shared__ uint32_t s_rank[kCand];
+    // the candidate list; behind it the all-pairs fallback's 128 rank counters, whose first words the segment ranking uses as
+    // the zero keys that end the list (it reads four keys a trip, up to three past its segment)
+    __shared__ __attribute__((aligned(16))) unsigned long long s_cand[kCand + kCand / 2];
+    uint32_t* const s_rank = reinterpret_cast<uint32_t*>(s_cand + kCand);
     __shared__ uint32_t s_red[16];
+#ifdef LBAD_ONE_CURSOR
     __shared__ uint32_t s_ncand;
+#endif
     __shared__ uint32_t s_bits[kPackedWords];
     __shared__ uint8_t s_pos[128];   // [i][j]: row position of coefficient i of the thread that owns chunk j (column pass)
-    __shared__ uint32_t s_sel[4];    // the histogram's bracket: lo, hi, keys >= lo
+    __shared__ uint32_t s_sel[4];    // the histogram's bracket: lo, hi, keys >= lo; and whether the frame ranks by all pairs
     static_assert(sizeof(s_t) >= kHistBuckets * sizeof(uint32_t), "the histogram lives in the transposed coefficients' LDS");
 
     const int t = threadIdx.x;
@@ -499,16 +520,14 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
     bool first_read = true;
 
     if (t < (int)kPackedWords) s_bits[t] = 0;
-    if (t < (int)kCand) s_rank[t] = 0;
+#ifdef LBAD_ONE_CURSOR
     if (t == 0) s_ncand = 0;
+#endif
     if (t < 128) {   // the closed form of pos[] below, as a table for step (b) of the gather
         const int i = t >> 3, jj = t & 7;
         const int cross = (jj & 1) ? 4 + (jj >> 1) : (jj & 2) ? 2 + (jj >> 2) : (jj ? 1 : 0);
         s_pos[t] = (uint8_t)(i < 8 ? 64 + 8 * jj + i : i < 12 ? 32 + 4 * jj + (i - 8) : i < 14 ? 16 + 2 * jj + (i - 12) : i == 14 ? 8 + jj : cross);
     }
-    for (int i = t; i < 2 * (int)kCand; i += kThreads)
-        reinterpret_cast<uint32_t*>(s_cand)[i] = 0;   // zero keys pad the list to a multiple of 8 for the ranking loop
-
     // ---- row pass, sparse form: thread = row (waves 0 and 1) ----------------------------------------------------
     if constexpr (SPARSE) {
         if (t < (int)kRowsPerFrame) {
@@ -705,6 +724,8 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
     uint32_t lo = 0, hi = 0x80000000u, cnt_lo = kRowsPerFrame * kCols;
     uint32_t idx_bound = kRowsPerFrame * kCols;
     int parity = 0;
+    bool all_pairs = true;           // (workgroup-uniform) rank by all pairs: no bucket list, or a segment longer than kSegCap
+    uint32_t* const hist = reinterpret_cast<uint32_t*>(s_t);
 #ifndef LBAD_EXP_NO_HISTOGRAM
     // First by HISTOGRAM (round 4): 2048 counters over the 11 leading bits of |v| (exponent + 3 mantissa bits: an eighth of
     // a binade each) in the LDS the transposed coefficients have just left; one wave sums them from the top and finds the
@@ -713,8 +734,16 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
     // compares and a barrier (measured on synthetic and bird frames: 106-109 keys on average, never more than 126).  A
     // bucket that holds too many (a plateau, a dense cluster) leaves the bracket [b, b + 1) to the bisection below.  Bucket
     // 0 (zeros, denormals below 2^-126) is never counted: a threshold down there is the initial bracket's lower end.
+    //
+    // The same wave then turns the counters into the CURSORS of the candidate list: the word of bucket b becomes
+    // (start << 16) | start with start = 8 bytes x the keys in buckets above b, for every bucket from the highest that holds a
+    // key down to the threshold bucket (the others are never read again; at and above the threshold a start is at most
+    // 8 x 128, and what overflows a half below it is never looked at), and bucket 0 comes out right without having been
+    // counted: its start is every key in buckets >= 1.  The gather adds 8 to the word of a key's bucket and takes the low half
+    // it gets back as the byte offset of the key's slot, so the list is grouped by bucket, highest first; a word ends as
+    // (start << 16) | end.  A bucket at or above the threshold with more than kSegCap keys sends the frame to the all-pairs
+    // ranking, and so does every frame whose threshold the bisection or the plateau path refines.
     {
-        uint32_t* hist = reinterpret_cast<uint32_t*>(s_t);
         __syncthreads();                                   // every wave has read (and, on the slow tiers, re-read) its lines
         for (int i = t; i < (int)(kHistBuckets / 4); i += kThreads) reinterpret_cast<uint4*>(hist)[i] = uint4{0u, 0u, 0u, 0u};
         __syncthreads();
@@ -741,6 +770,7 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
             const uint32_t incl = wave_prefix_sum(own), excl = incl - own;
             const unsigned long long m1 = __ballot(excl < keep && keep <= incl);
             uint32_t out_lo = 0, out_hi = 1u << 20, out_cnt = kRowsPerFrame * kCols;
+            int thr_bucket = 0;              // the threshold bucket (0: none found, the bisection starts in bucket 0)
             if (m1 != 0ull) {                                                       // (wave-uniform)
                 const int L = __ffsll((long long)m1) - 1;
                 const uint32_t before = (uint32_t)__builtin_amdgcn_readlane((int)excl, L);
@@ -754,14 +784,38 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
                     out_lo = b << 20;
                     out_hi = (b + 1u) << 20;
                     out_cnt = (uint32_t)__builtin_amdgcn_readlane((int)p, J);
+                    thr_bucket = (int)b;
                 }
             }
-            if (t == 0) { s_sel[0] = out_lo; s_sel[1] = out_hi; s_sel[2] = out_cnt; }
+            uint32_t crowded = 1u;
+            if constexpr (kBucketList) {
+                // counters -> cursors in rounds of 64 buckets, a bucket per lane (neighbouring words: no bank conflicts, and
+                // about twenty instructions a round on the one wave everybody waits for -- each lane walking its own 32
+                // counters, a hundred instructions, made the whole kernel 8 % slower than without any of this), from the
+                // highest lane of the sum above that holds a key down to the threshold bucket: one round for an ordinary
+                // frame, whose candidates lie within eight binades.  Bucket 0's own count is never added to a cursor.
+                const unsigned long long held = __ballot(own != 0u);
+                const int l0 = held != 0ull ? __ffsll((long long)held) - 1 : 63;
+                uint32_t above = (uint32_t)__builtin_amdgcn_readlane((int)excl, l0);      // keys above the round's buckets
+                unsigned long long wide = 0ull;
+                for (int base = (int)kHistBuckets - 1 - 32 * l0; base >= thr_bucket; base -= 64) {   // (wave-uniform)
+                    const int bkt = base - t;
+                    const uint32_t h = bkt >= 0 ? hist[bkt] : 0u;
+                    const uint32_t upto = wave_prefix_sum(h);
+                    const uint32_t start = (above + upto - h) * kCursorStep;
+                    if (bkt >= 0) hist[bkt] = start + (start << 16);
+                    wide |= __ballot(bkt >= thr_bucket && h > kSegCap);
+                    above += (uint32_t)__builtin_amdgcn_readlane((int)upto, 63);
+                }
+                crowded = out_cnt > kCand || wide != 0ull ? 1u : 0u;
+            }
+            if (t == 0) { s_sel[0] = out_lo; s_sel[1] = out_hi; s_sel[2] = out_cnt; s_sel[3] = crowded; }
         }
         __syncthreads();
         lo = s_sel[0];
         hi = s_sel[1];
         cnt_lo = s_sel[2];
+        all_pairs = s_sel[3] != 0u;
     }
 #endif
     while (cnt_lo > kCand && hi - lo > 1) {
@@ -813,7 +867,7 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
 
     // ---- gather candidates, in two steps ---------------------------------------------------------------------
     // (a) every thread drops (key, where it came from) of its selected coefficients into the list: per coefficient a
-    //     compare, the slot from lane-mask popcounts (one LDS atomic per wave) and one 8-byte store.  A wave holds ~26
+    //     compare, the slot from the cursor of the key's bucket (one returning LDS atomic) and one 8-byte store.  A wave holds ~26
     //     candidates among 1024 coefficients, so whatever else is done per coefficient here runs with one or two lanes
     //     active -- until round 3 that was the whole composite key (16 instructions, 16 times);
     // (b) one thread per CANDIDATE turns its entry into the composite
@@ -821,8 +875,20 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
     {
         const uint32_t origin = ((uint32_t)col << 7) | (uint32_t)j;    // + (i << 3): index into s_pos, column above it
         typedef __attribute__((address_space(3))) void lds_void_t;
-        uint32_t ncand_at = (uint32_t)(uintptr_t)(lds_void_t*)&s_ncand, one = 1u;
-        asm volatile("" : "+v"(ncand_at), "+v"(one));                   // (held in registers, not rebuilt per block)
+#ifdef LBAD_ONE_CURSOR
+        uint32_t step = 1u;
+        uint32_t ncand_at = (uint32_t)(uintptr_t)(lds_void_t*)&s_ncand;
+        asm volatile("" : "+v"(ncand_at));
+        auto cursor_of = [&](uint32_t) { return ncand_at; };
+        auto slot_of = [&](uint32_t got) { return &s_cand[got]; };
+#else
+        // the cursor of a key is the word of its bucket (key >> 21); the low half of what the add returns is the byte offset
+        // of the key's slot in the list
+        uint32_t step = kCursorStep;
+        auto cursor_of = [&](uint32_t k) { return (uint32_t)(uintptr_t)(lds_void_t*)&hist[k >> 21]; };
+        auto slot_of = [&](uint32_t got) { return reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(s_cand) + (got & 0xFFFFu)); };
+#endif
+        asm volatile("" : "+v"(step));                                  // (held in a register, not rebuilt per block)
         auto gather = [&](auto selected) {
 #ifdef LBAD_EXP_GATHER_BALLOT
             // the lane masks are taken once and kept (scalar registers) -- eight at a time, with one LDS atomic per wave and
@@ -853,19 +919,19 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
 #else
             // every selected coefficient takes its slot with ONE returning LDS atomic (inline asm: the compiler's atomic
             // optimiser would rebuild the ballot / mbcnt form around it, and it rematerialises the operands in every
-            // block): the order of the list is whatever the hardware made it, the ranks below do not depend on it.  All
-            // sixteen atomics are in flight before the first slot is used (one wait).
+            // block): the order inside a bucket's segment is whatever the hardware made it, the ranks below do not depend on
+            // it.  All sixteen atomics are in flight before the first slot is used (one wait).
             uint32_t at[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i)
-                if (selected(i)) asm volatile("ds_add_rtn_u32 %0, %1, %2" : "=v"(at[i]) : "v"(ncand_at), "v"(one) : "memory");
+                if (selected(i)) asm volatile("ds_add_rtn_u32 %0, %1, %2" : "=v"(at[i]) : "v"(cursor_of(key[i])), "v"(step) : "memory");
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(at[0]), "+v"(at[1]), "+v"(at[2]), "+v"(at[3]), "+v"(at[4]), "+v"(at[5]), "+v"(at[6]), "+v"(at[7]),
                            "+v"(at[8]), "+v"(at[9]), "+v"(at[10]), "+v"(at[11]), "+v"(at[12]), "+v"(at[13]), "+v"(at[14]), "+v"(at[15])
                          :: "memory");
 #pragma unroll
             for (int i = 0; i < 16; ++i)
-                if (selected(i)) s_cand[at[i]] = ((unsigned long long)key[i] << 32) | (origin + (uint32_t)(i << 3));
+                if (selected(i)) *slot_of(at[i]) = ((unsigned long long)key[i] << 32) | (origin + (uint32_t)(i << 3));
 #endif
         };
         // (workgroup-uniform) without a plateau one compare per key decides; two copies of the loop, so that the masks
@@ -877,20 +943,55 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
         }
     }
     __syncthreads();
+    // the list ends where the threshold bucket's segment ends (the cursor counted the keys that arrived: all of the bucket's,
+    // or those the bisection or the plateau path let through)
+#ifdef LBAD_ONE_CURSOR
     const uint32_t nc = s_ncand;
+#else
+    const uint32_t nc = (hist[lo >> 20] & 0xFFFFu) / kCursorStep;
+#endif
+    unsigned long long own = 0;
+    uint32_t seg = 0;                // the candidate's segment of the list: (start << 16) | end
     if (t < (int)nc) {   // nc <= kCand <= kThreads
         const unsigned long long raw = s_cand[t];
         const uint32_t k = (uint32_t)(raw >> 32), from = (uint32_t)raw;
+        if constexpr (kBucketList) seg = hist[k >> 21];
         const uint32_t idx = (uint32_t)s_pos[from & 127u] * kCols + (from >> 7);
         // |v| bits in [1, 0x7F800000] (not +-0, not NaN: neither v > 0 nor v < 0 holds for those)  <=>  k - 2 < 0xFF000000
         const uint32_t sg = k - 2u < 0xFF000000u ? (k & 1u) + 1u : 0u;
-        s_cand[t] = ((unsigned long long)(k & ~1u) << (kIdxBits + 1)) | ((unsigned long long)(((1u << kIdxBits) - 1u) - idx) << 2) | sg;
+        own = ((unsigned long long)(k & ~1u) << (kIdxBits + 1)) | ((unsigned long long)(((1u << kIdxBits) - 1u) - idx) << 2) | sg;
+        s_cand[t] = own;
     }
-    __syncthreads();
-    STAMP(4);
-
-    // ---- rank: kThreads / 128 threads per candidate, each scans its share of the list --------------------
-    {
+    auto emit = [&](uint32_t rank, uint32_t sg) {
+        if (rank < keep) {
+            const uint32_t b = 2 * rank;
+            if (sg == 1u) atomicOr(&s_bits[b >> 5], 1u << (b & 31));
+            else if (sg == 2u && b + 1 < subfp_len) atomicOr(&s_bits[(b + 1) >> 5], 1u << ((b + 1) & 31));
+        }
+    };
+    if (!all_pairs) {
+        // ---- rank inside the segment: a key of a higher bucket is larger, so a candidate's rank is its segment's start plus
+        // the keys of the segment above it.  Four keys a trip; a trip may run up to three keys past the segment, onto
+        // keys of lower buckets (smaller: they count nothing) or onto the three zero keys behind the list.
+        if (t < 3) s_cand[nc + t] = 0;
+        __syncthreads();
+        STAMP(4);
+        if (t < (int)nc) {
+            const uint32_t end = (seg & 0xFFFFu) / kCursorStep;
+            uint32_t rank = (seg >> 16) / kCursorStep;
+            for (uint32_t i = rank; i < end; i += 4) {
+                const unsigned long long c0 = s_cand[i], c1 = s_cand[i + 1], c2 = s_cand[i + 2], c3 = s_cand[i + 3];
+                rank += (c0 > own ? 1u : 0u) + (c1 > own ? 1u : 0u) + (c2 > own ? 1u : 0u) + (c3 > own ? 1u : 0u);
+            }
+            emit(rank, (uint32_t)own & 3u);
+        }
+    } else {
+        // ---- rank by all pairs: kThreads / 128 threads per candidate, each scans its share of the list ----------------
+        // zero keys pad the list to a multiple of 8 for the ranking loop
+        if (t < (int)kCand) s_rank[t] = 0;
+        if (t >= (int)nc && t < (int)((nc + 7u) & ~7u)) s_cand[t] = 0;
+        __syncthreads();
+        STAMP(4);
         // 192 threads (sparse form): three parts of 64 threads, a thread ranks candidates i and i + 64 over its third of the
         // list -- both against the SAME loaded block of eight keys (round 4: one trip through LDS serves both)
         constexpr uint32_t kGroup = kThreads == 192 ? 64 : 128;                 // threads of a part
@@ -919,16 +1020,8 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
 #pragma unroll
         for (uint32_t k = 0; k < kPer; ++k)
             if (r[k]) atomicAdd(&s_rank[i0 + k * kGroup], r[k]);
-    }
-    __syncthreads();
-    if (t < (int)nc) {
-        const uint32_t rank = s_rank[t];
-        if (rank < keep) {
-            const uint32_t sg = (uint32_t)s_cand[t] & 3u;
-            const uint32_t b = 2 * rank;
-            if (sg == 1u) atomicOr(&s_bits[b >> 5], 1u << (b & 31));
-            else if (sg == 2u && b + 1 < subfp_len) atomicOr(&s_bits[(b + 1) >> 5], 1u << ((b + 1) & 31));
-        }
+        __syncthreads();
+        if (t < (int)nc) emit(s_rank[t], (uint32_t)own & 3u);
     }
     __syncthreads();
     if (t < (int)kPackedWords) packed[frame * kPackedWords + t] = s_bits[t];

@@ -378,6 +378,63 @@ OSStatus LBAudioDetectiveStreamPush(LBAudioDetectiveStreamRef inStream, const Fl
                                     UInt64 inNumberOfSamples, UInt32* outNewSubfingerprints);
 LBAudioDetectiveFingerprintRef LBAudioDetectiveStreamCopyFingerprint(LBAudioDetectiveStreamRef inStream);
 
+/* Stream bank: the same for MANY live channels at once, on the device.  A bank owns, in device memory, the carried partial frame
+ * of each of its channels and each channel's inHistorySubfingerprints most recent sub-fingerprints (a ring) in the packed layout
+ * (LBAD_PACKED_BYTES each) that every ...Packed...Device call reads.  One push takes a ragged block of new samples, fingerprints
+ * every frame that became complete -- all channels in one launch chain -- and files the results.  After a channel has received L
+ * samples in any chunking its sub-fingerprints are those of LBAudioDetectiveProcessPCM on the L samples, bit for bit.
+ *
+ * The bank takes window, stride, pitch steps and sub-fingerprint length from the detective when it is made; a push after any of
+ * them changed returns kLBAudioDetectiveArgumentInvalid.  inFramesPerPass bounds the staging memory (that many frames of window +
+ * 128 x stride samples; 0: one frame per channel): a push that completes more frames runs in several passes, with the same
+ * results.  New returns NULL for a NULL detective, zero channels (more than 2^24), zero history (more than 2^20), without a device
+ * or without memory; per channel the bank holds 2 x (window + 128 x stride) samples and 32 x history bytes.
+ *
+ * The sample counts are HOST memory, and the bank mirrors on the host what every channel carries and has produced: neither
+ * PushDevice nor WindowDevice reads anything back, both are asynchronous on inStream.  A mutex guards the host side; a call on
+ * another stream than the call before it first waits ON THE DEVICE for that call's last launch, so calls take effect in the order
+ * they were made.  Argument checks that need no handle come first (NULL handles and required pointers, inSamples off 4 bytes,
+ * outNewPacked / outPacked off 16 bytes), then kLBAudioDetectiveDeviceUnavailable without a device, then the rest -- a channel
+ * index out of range, inNewCapacity below the push's total where outNewPacked is given, a window longer than the history or than
+ * a listed channel's total -- each kLBAudioDetectiveArgumentInvalid; a refused call changes neither the mirror nor device memory.
+ * A HIP failure behind a call's first launch leaves the device state unknown: the bank is unusable from then on, and every later
+ * call returns kLBAudioDetectiveDeviceError (CopyFingerprint: NULL); only Dispose remains. */
+typedef struct LBAudioDetectiveStreamBank* LBAudioDetectiveStreamBankRef;
+LBAudioDetectiveStreamBankRef LBAudioDetectiveStreamBankNew(LBAudioDetectiveRef inDetective, UInt32 inNumberOfChannels,
+                                                            UInt32 inHistorySubfingerprints, UInt32 inFramesPerPass);
+void LBAudioDetectiveStreamBankDispose(LBAudioDetectiveStreamBankRef inBank);   /* waits for the bank's launches */
+/* inSamples: DEVICE float32, the channels' new samples one after the other in channel order (4-byte aligned; a channel's run may
+ * start at any sample; they are read until the call's launches have run).  inSampleCounts: HOST, one count per channel, 0 =
+ * nothing for this channel.  outNewCounts (HOST, may be NULL): sub-fingerprints each channel completed in this call -- known when
+ * the call returns.  outNewPacked (DEVICE, 16-byte aligned, may be NULL): those sub-fingerprints, 32 bytes each, in channel order
+ * then in time order, written asynchronously on inStream; outNewTotal (may be NULL) their number.  A push that completes more
+ * than the history's frames of a channel keeps the last of them there; all of them appear in outNewPacked and in the totals. */
+OSStatus LBAudioDetectiveStreamBankPushDevice(LBAudioDetectiveStreamBankRef inBank, const Float32* inSamples,
+                                              const UInt32* inSampleCounts, UInt32* outNewCounts, void* outNewPacked,
+                                              UInt64 inNewCapacity, UInt64* outNewTotal, void* inStream);
+/* the same with HOST samples; returns once inSamples may be reused; the outputs as above */
+OSStatus LBAudioDetectiveStreamBankPush(LBAudioDetectiveStreamBankRef inBank, const Float32* inSamples,
+                                        const UInt32* inSampleCounts, UInt32* outNewCounts, void* outNewPacked,
+                                        UInt64 inNewCapacity, UInt64* outNewTotal, void* inStream);
+/* host mirror, no device work: per channel the sub-fingerprints since creation / the last reset, and the samples carried (either
+ * pointer may be NULL, not both) */
+OSStatus LBAudioDetectiveStreamBankGetCounts(LBAudioDetectiveStreamBankRef inBank, UInt64* outTotals, UInt32* outPendingSamples);
+/* the inSubfingerprints (>= 1) most recent sub-fingerprints of each listed channel, oldest first: outPacked = DEVICE
+ * [inNumberOfChannels][inSubfingerprints][32 bytes], asynchronous on inStream.  inChannels: HOST; a channel may be listed more
+ * than once, in any order; at most 2^31 sub-fingerprints per call. */
+OSStatus LBAudioDetectiveStreamBankWindowDevice(LBAudioDetectiveStreamBankRef inBank, const UInt32* inChannels,
+                                                UInt32 inNumberOfChannels, UInt32 inSubfingerprints, void* outPacked, void* inStream);
+/* the min(total, history) most recent sub-fingerprints of one channel as a handle, oldest first (waits for the device) */
+LBAudioDetectiveFingerprintRef LBAudioDetectiveStreamBankCopyFingerprint(LBAudioDetectiveStreamBankRef inBank, UInt32 inChannel);
+/* the listed channels start again: nothing carried, total 0, empty history */
+OSStatus LBAudioDetectiveStreamBankResetChannels(LBAudioDetectiveStreamBankRef inBank, const UInt32* inChannels, UInt32 inNumberOfChannels);
+/* Debug / tests: the host plan of one push, needs no device.  Per channel, from inPending samples carried (below window + 128 x
+ * stride) and inSampleCounts new ones: outReady = LBAudioDetectiveGetSubfingerprintCount's value for their sum, outPendingAfter =
+ * the sum - outReady x 128 x stride, outKept = min(outReady, inHistorySubfingerprints), the frames the ring keeps. */
+OSStatus LBAudioDetectiveDebugStreamBankPlan(UInt32 inWindowSize, UInt32 inAnalysisStride, UInt32 inHistorySubfingerprints,
+                                             UInt32 inNumberOfChannels, const UInt32* inPending, const UInt32* inSampleCounts,
+                                             UInt32* outReady, UInt32* outPendingAfter, UInt32* outKept);
+
 /* Stage 2 alone: inFrames = device pointer to inNumberOfFrames x 128 x bands float32 frame rows (what
  * LBAudioDetectiveFrameSetRow collects upstream) -> packed sub-fingerprints; outFramesHaar (optional)
  * receives the decomposed frames.  Replaces LBAudioDetectiveSynthesizeFingerprint

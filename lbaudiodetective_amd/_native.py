@@ -124,6 +124,16 @@ _SIGNATURES = {
     "LBAudioDetectiveStreamDispose": (None, [Ref]),
     "LBAudioDetectiveStreamPush": (OSStatus, [Ref, C.c_void_p, UInt64, _P(UInt32)]),
     "LBAudioDetectiveStreamCopyFingerprint": (Ref, [Ref]),
+    "LBAudioDetectiveStreamBankNew": (Ref, [Ref, UInt32, UInt32, UInt32]),
+    "LBAudioDetectiveStreamBankDispose": (None, [Ref]),
+    "LBAudioDetectiveStreamBankPushDevice": (OSStatus, [Ref, C.c_void_p, _P(UInt32), _P(UInt32), C.c_void_p, UInt64, _P(UInt64), C.c_void_p]),
+    "LBAudioDetectiveStreamBankPush": (OSStatus, [Ref, C.c_void_p, _P(UInt32), _P(UInt32), C.c_void_p, UInt64, _P(UInt64), C.c_void_p]),
+    "LBAudioDetectiveStreamBankGetCounts": (OSStatus, [Ref, _P(UInt64), _P(UInt32)]),
+    "LBAudioDetectiveStreamBankWindowDevice": (OSStatus, [Ref, _P(UInt32), UInt32, UInt32, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveStreamBankCopyFingerprint": (Ref, [Ref, UInt32]),
+    "LBAudioDetectiveStreamBankResetChannels": (OSStatus, [Ref, _P(UInt32), UInt32]),
+    "LBAudioDetectiveDebugStreamBankPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, _P(UInt32), _P(UInt32), _P(UInt32), _P(UInt32),
+                                                       _P(UInt32)]),
     "LBAudioDetectiveFingerprintClips": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p]),
     "LBAudioDetectiveFingerprintClipsFormat": (OSStatus, [Ref, C.c_void_p, UInt32, UInt64, UInt64, C.c_void_p]),
     "LBAudioDetectiveSetKernelVariant": (OSStatus, [Ref, UInt32]),

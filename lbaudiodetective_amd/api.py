@@ -523,6 +523,142 @@ class Stream:
         return Fingerprint(_ref=self._L.LBAudioDetectiveStreamCopyFingerprint(self._ref))
 
 
+def _u32_list(values):
+    a = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.uint32)
+    return a, (a.ctypes.data_as(C.POINTER(N.UInt32)) if a.size else None)
+
+
+def debug_stream_bank_plan(window: int, stride: int, history: int, pending, counts):
+    """LBAudioDetectiveDebugStreamBankPlan (tests): the host plan of one push -> (ready, pending_after, kept), uint32 arrays with
+    one value per channel.  Needs no GPU."""
+    p, pp = _u32_list(pending)
+    n, np_ = _u32_list(counts)
+    if p.size != n.size:
+        raise ValueError("pending and counts must have one value per channel")
+    out = [np.zeros(max(1, p.size), np.uint32) for _ in range(3)]
+    _check(N.lib().LBAudioDetectiveDebugStreamBankPlan(window, stride, history, p.size, pp, np_,
+                                                       *[o.ctypes.data_as(C.POINTER(N.UInt32)) for o in out]), "DebugStreamBankPlan")
+    return tuple(o[:p.size] for o in out)
+
+
+class StreamBank:
+    """LBAudioDetectiveStreamBankRef: `n_channels` live channels whose carried partial frames and `history` most recent
+    sub-fingerprints stay on the device.  A push takes new samples of any of the channels and fingerprints every frame they
+    complete in one launch chain; `window_device` hands the most recent sub-fingerprints of some channels to the packed queries.
+    frames_per_pass bounds the staging memory (0: one frame per channel); results do not depend on it."""
+
+    def __init__(self, detective: Detective, n_channels: int, history: int, frames_per_pass: int = 0):
+        self._L = N.lib()
+        self._det = detective            # keep the detective alive
+        self.n_channels, self.history = int(n_channels), int(history)
+        self._ref = self._L.LBAudioDetectiveStreamBankNew(detective._ref, n_channels, history, frames_per_pass)
+        if not self._ref:
+            raise LBAudioDetectiveError(1, "StreamBankNew")
+
+    def dispose(self):
+        if self._ref:
+            self._L.LBAudioDetectiveStreamBankDispose(self._ref)
+            self._ref = None
+
+    def __del__(self):
+        try:
+            self.dispose()
+        except Exception:
+            pass
+
+    def _push(self, fn, what, samples_ptr, counts, new_out, stream, device):
+        n, npt = _u32_list(counts)
+        if n.size != self.n_channels:
+            raise ValueError("counts must have one value per channel")
+        if new_out is True:              # sized from the plan, which the host can make alone
+            import torch
+            ready = debug_stream_bank_plan(self._det.window_size, self._det.analysis_stride, self.history, self.pending(), n)[0]
+            new_out = torch.empty((int(ready.sum()), N.PACKED_BYTES), dtype=torch.uint8, device=device)
+        capacity = 0
+        if new_out is not None:
+            if not new_out.is_cuda or not new_out.is_contiguous():
+                raise ValueError("new_out must be a contiguous device tensor")
+            capacity = new_out.numel() * new_out.element_size() // N.PACKED_BYTES
+        new_counts = np.zeros(self.n_channels, np.uint32)
+        total = N.UInt64(0)
+        _check(fn(self._ref, samples_ptr, npt, new_counts.ctypes.data_as(C.POINTER(N.UInt32)),
+                  _dev_ptr(new_out) if new_out is not None and new_out.numel() else None, capacity, C.byref(total), _stream_ptr(stream)), what)
+        if new_out is None:
+            return new_counts, None
+        import torch
+        return new_counts, new_out.view(torch.uint8).reshape(-1, N.PACKED_BYTES)[:total.value]
+
+    def push_device(self, samples, counts, new_out=None, stream=None):
+        """LBAudioDetectiveStreamBankPushDevice: `samples`, a float32 device tensor holding the channels' new samples one after
+        the other in channel order; `counts`, one host integer per channel.  new_out: None, True (a tensor of exactly the new
+        sub-fingerprints is made) or a contiguous device tensor with room for them -> (new_counts uint32 [n_channels] on the host,
+        the new sub-fingerprints uint8 [total, 32] on the device in channel order then time order, or None).  Asynchronous on
+        `stream`; `samples` must stay untouched until the stream has run the call."""
+        import torch
+        assert samples.is_cuda and samples.is_contiguous() and samples.dtype == torch.float32
+        if samples.numel() < int(np.asarray(counts, dtype=np.uint64).sum()):
+            raise ValueError("samples holds fewer values than the counts add up to")
+        return self._push(self._L.LBAudioDetectiveStreamBankPushDevice, "StreamBankPushDevice",
+                          C.c_void_p(samples.data_ptr()) if samples.numel() else None, counts, new_out, stream, samples.device)
+
+    def push(self, chunks, new_out=None, stream=None):
+        """LBAudioDetectiveStreamBankPush: `chunks`, one numpy array of new samples per channel (None or empty: nothing for that
+        channel), from host memory; returns as push_device once the samples have been taken."""
+        if len(chunks) != self.n_channels:
+            raise ValueError("chunks must have one entry per channel")
+        parts = [_f32(c).reshape(-1) if c is not None else np.zeros(0, np.float32) for c in chunks]
+        x = np.concatenate(parts) if parts else np.zeros(0, np.float32)
+        return self._push(self._L.LBAudioDetectiveStreamBankPush, "StreamBankPush", C.c_void_p(x.ctypes.data) if x.size else None,
+                          [p.size for p in parts], new_out, stream, "cuda")
+
+    def totals(self) -> np.ndarray:
+        """sub-fingerprints of every channel since creation / its last reset (uint64, the host mirror)"""
+        out = np.zeros(self.n_channels, np.uint64)
+        _check(self._L.LBAudioDetectiveStreamBankGetCounts(self._ref, out.ctypes.data_as(C.POINTER(N.UInt64)), None), "StreamBankGetCounts")
+        return out
+
+    def pending(self) -> np.ndarray:
+        """samples every channel carries (uint32, the host mirror)"""
+        out = np.zeros(self.n_channels, np.uint32)
+        _check(self._L.LBAudioDetectiveStreamBankGetCounts(self._ref, None, out.ctypes.data_as(C.POINTER(N.UInt32))), "StreamBankGetCounts")
+        return out
+
+    def window_device(self, channels, n: int, out=None, stream=None):
+        """LBAudioDetectiveStreamBankWindowDevice: the n most recent sub-fingerprints of each listed channel, oldest first, as
+        uint8 [len(channels), n, 32] on the device -- the `packed` of the ...packed..._device queries.  Asynchronous on `stream`."""
+        ch, cp = _u32_list(channels)
+        if out is None:
+            import torch
+            with torch.cuda.stream(stream):              # (the block belongs to the stream that fills it)
+                out = torch.empty((ch.size, n, N.PACKED_BYTES), dtype=torch.uint8, device="cuda")
+        if not out.is_cuda or not out.is_contiguous() or out.numel() * out.element_size() < ch.size * n * N.PACKED_BYTES:
+            raise ValueError("out must be a contiguous device tensor of at least len(channels) * n * 32 bytes")
+        _check(self._L.LBAudioDetectiveStreamBankWindowDevice(self._ref, cp, ch.size, n, _dev_ptr(out), _stream_ptr(stream)),
+               "StreamBankWindowDevice")
+        return out
+
+    def fingerprint(self, channel: int) -> Fingerprint:
+        """LBAudioDetectiveStreamBankCopyFingerprint: the min(total, history) most recent sub-fingerprints of one channel."""
+        if not 0 <= channel < self.n_channels:
+            raise IndexError(f"channel {channel} of a bank of {self.n_channels}")
+        ref = self._L.LBAudioDetectiveStreamBankCopyFingerprint(self._ref, channel)
+        if not ref:
+            raise LBAudioDetectiveError(1, "StreamBankCopyFingerprint")
+        return Fingerprint(_ref=ref)
+
+    def reset(self, channels):
+        """LBAudioDetectiveStreamBankResetChannels: the listed channels start again."""
+        ch, cp = _u32_list(channels)
+        _check(self._L.LBAudioDetectiveStreamBankResetChannels(self._ref, cp, ch.size), "StreamBankResetChannels")
+
+    def identify(self, corpus: "Corpus", channels, n: int, k: int = 1, aligned: bool = False, range_: int = 0, stream=None):
+        """The n most recent sub-fingerprints of the listed channels against the corpus: window_device, then
+        Corpus.query_packed_topk_keys_device on its output, on ONE stream with nothing in between.  Returns the [len(channels), k]
+        int64 key tensor, and with aligned=True (keys, lags int32)."""
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.query_packed_topk_keys_device(packed, packed.shape[0], n, k, aligned=aligned, range_=range_, stream=stream)
+
+
 class Corpus:
     """LBAudioDetectiveCorpusRef: device-resident reference fingerprints with a top-1 query."""
 

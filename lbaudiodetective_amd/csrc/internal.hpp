@@ -741,6 +741,34 @@ hipError_t launch_build_sliding_queries(const uint32_t* d_rows, uint32_t n_queri
 hipError_t launch_build_query_rows(const uint32_t* d_rows, uint32_t n_queries, uint32_t per, uint32_t subfp_len, bool pairs,
                                    uint32_t* d_words, uint2* d_desc, hipStream_t stream);
 
+// stream bank (k_stream_bank.hip; api_stream_bank.cpp is its host side).  The bank as its kernels read it:
+struct BankDev {
+    float* carry = nullptr;             // [2 sides][n_channels][carry_stride] carried samples
+    uint64_t carry_stride = 0;          // floats per channel and side: window + hop (a multiple of 16)
+    uint64_t n_channels = 0;
+    uint32_t* ring = nullptr;           // [n_channels][history][8 words] packed sub-fingerprints, number t of a channel at t mod history
+    uint32_t history = 0, window = 0, hop = 0;
+};
+// One channel that received samples in a push (48 bytes; the host plans the push and uploads these, in channel order)
+struct BankRow {
+    uint64_t fresh_at;                  // its first new sample inside the push's sample block
+    uint32_t p, n, ready;               // samples carried, samples new, frames they complete
+    uint32_t first;                     // its first frame among the push's frames (channel order, then time)
+    uint32_t ring_at;                   // ring slot of that frame: the channel's total mod history
+    uint32_t channel, side;             // side: the carried buffer that holds the p samples
+    uint32_t pad[3];
+};
+static_assert(sizeof(BankRow) == 48, "BankRow is uploaded as it is");
+// frames [g0, g0 + nf) of the push as one-frame clips of window + hop samples to d_clips (16-byte aligned)
+hipError_t launch_bank_stage(const BankDev& b, const BankRow* d_rows, uint32_t n_rows, const float* d_fresh, uint32_t g0, uint32_t nf,
+                             float* d_clips, hipStream_t stream);
+// behind the last pass: the push's `total` packed sub-fingerprints at d_packed into the rings and (d_out != null, 16-byte aligned)
+// the caller's block, then what every row's channel carries on -- into the other side where it completed a frame.  Two launches.
+hipError_t launch_bank_commit(const BankDev& b, const BankRow* d_rows, uint32_t n_rows, const float* d_fresh, const uint32_t* d_packed,
+                              uint32_t total, void* d_out, hipStream_t stream);
+// d_list[j] = (channel, ring slot of the oldest of its q rows) -> d_out[j][q][32 bytes] (16-byte aligned); n_list * q <= 2^31
+hipError_t launch_bank_window(const BankDev& b, const uint2* d_list, uint64_t n_list, uint32_t q, void* d_out, hipStream_t stream);
+
 // measurement: ticks of the shader clock and of the constant 100 MHz clock over ~usec microseconds (2 words)
 hipError_t launch_clock_probe(uint32_t usec, unsigned long long* d_out, hipStream_t stream);
 // synthetic data

@@ -435,6 +435,75 @@ OSStatus LBAudioDetectiveDebugStreamBankPlan(UInt32 inWindowSize, UInt32 inAnaly
                                              UInt32 inNumberOfChannels, const UInt32* inPending, const UInt32* inSampleCounts,
                                              UInt32* outReady, UInt32* outPendingAfter, UInt32* outKept);
 
+/* Resampler bank: the sample-rate converter of the file front end in streaming form, for MANY live channels at once, on the
+ * device -- what stands between live feeds (44.1 or 48 kHz, often int16) and a stream bank at the processing rate.  A bank owns,
+ * in device memory, each channel's filter history and a copy of the rate pair's phase table.  One push takes a ragged block of new
+ * samples and emits every output sample that became final -- all channels in one launch chain -- in the layout
+ * LBAudioDetectiveStreamBankPushDevice reads: a resampler push followed by a stream-bank push of (outSamples, outNewCounts) on the
+ * same stream is the whole path, with nothing read back.
+ *
+ * The arithmetic is the rational position of LBAudioDetectiveReadAudioURLWithResampler.  With inInputSampleRate /
+ * inOutputSampleRate = p / q in lowest terms, output n of a channel sits at ip = (n p) div q with phase (n p) mod q and sums its
+ * phase's taps x[ip + m]; m_lo / m_hi are the smallest first / largest last tap over the phases (-192 / 193 for 44100 -> 5512 Hz,
+ * mode 0).  An output is final once its last possible tap has arrived: after a channel has received L samples since it started,
+ * in any chunking, it has emitted emitted(L) = 0 for L <= m_hi, else ceil((L - m_hi) q / p) samples, and they are the first
+ * emitted(L) samples the whole-signal converter gives for x[0, L') for every L' >= L long enough to have them, bit for bit.
+ * Finishing a channel at L emits the outputs [emitted(L), n_out(L)), n_out(L) = (UInt64)(L / (rate_in / rate_out)), with taps at
+ * or beyond L contributing nothing: the channel's whole output is then the whole-signal conversion of x[0, L) exactly, and the
+ * channel starts again.
+ *
+ * New returns NULL for equal rates (push those samples straight into the stream bank), for a pair the rational position does not
+ * cover (rates that are not whole numbers of Hz, q > 16384, p > 2^24, a ratio outside [1/4096, 4096]), for a mode other than 0
+ * (long Kaiser sinc) or 1 (short sinc), for a pair whose tap span m_hi - m_lo + 1 exceeds LBAD_RESAMPLER_BANK_MAX_TAP_SPAN input
+ * samples -- what a workgroup can stage; mode 0: a ratio above about 53, mode 1: above about 319 --, for zero or more than 2^24
+ * channels, without a device or without memory.  Per channel the bank holds 2 x tap span samples.  It depends on no detective.
+ *
+ * The sample counts are HOST memory, and the bank mirrors on the host each channel's input total, output total and carried-buffer
+ * side: no call reads anything back, PushDevice and FinishChannels are asynchronous on inStream.  A mutex guards the host side; a
+ * call on another stream than the call before it first waits ON THE DEVICE for that call's last launch.  Argument checks that need
+ * no handle come first (NULL handles and required pointers, inSampleFormat above 1, inSamples off 4 bytes (float32) / 2 bytes
+ * (int16), outSamples off 4 bytes), then kLBAudioDetectiveDeviceUnavailable without a device, then the rest -- a channel index out
+ * of range or listed twice, new samples without inSamples, outputs without outSamples, inCapacity below the call's total, more
+ * than 2^31 - 1 outputs in one call, a channel whose n p would leave 63 bits -- each kLBAudioDetectiveArgumentInvalid; a refused
+ * call changes neither the mirror nor device memory.  A HIP failure behind a call's first launch leaves the device state unknown:
+ * every later call returns kLBAudioDetectiveDeviceError; only Dispose remains. */
+#define LBAD_RESAMPLER_BANK_MAX_TAP_SPAN 2560
+typedef struct LBAudioDetectiveResamplerBank* LBAudioDetectiveResamplerBankRef;
+LBAudioDetectiveResamplerBankRef LBAudioDetectiveResamplerBankNew(Float64 inInputSampleRate, Float64 inOutputSampleRate,
+                                                                  UInt32 inResamplerMode, UInt32 inNumberOfChannels);
+void LBAudioDetectiveResamplerBankDispose(LBAudioDetectiveResamplerBankRef inBank);   /* waits for the bank's launches */
+/* inSamples: DEVICE, the channels' new samples one after the other in channel order, exactly as StreamBankPushDevice takes them;
+ * inSampleFormat 0: float32, 1: int16, read as (float)s * (1.0f / 32768.0f); a channel's run may start at any sample; they are
+ * read until the call's launches have run.  inSampleCounts: HOST, one count per channel, 0 = nothing for this channel.
+ * outNewCounts (HOST, may be NULL): one entry per channel of the bank, zeros included: the samples each channel emitted in this
+ * call -- known when the call returns.  outSamples (DEVICE float32, 4-byte aligned): those samples in channel order, then in time
+ * order, written asynchronously on inStream; inCapacity: its room in samples; outNewTotal (may be NULL): their number. */
+OSStatus LBAudioDetectiveResamplerBankPushDevice(LBAudioDetectiveResamplerBankRef inBank, const void* inSamples, UInt32 inSampleFormat,
+                                                 const UInt32* inSampleCounts, UInt32* outNewCounts, Float32* outSamples,
+                                                 UInt64 inCapacity, UInt64* outNewTotal, void* inStream);
+/* the same with HOST samples; returns once inSamples may be reused; the outputs as above */
+OSStatus LBAudioDetectiveResamplerBankPush(LBAudioDetectiveResamplerBankRef inBank, const void* inSamples, UInt32 inSampleFormat,
+                                           const UInt32* inSampleCounts, UInt32* outNewCounts, Float32* outSamples,
+                                           UInt64 inCapacity, UInt64* outNewTotal, void* inStream);
+/* the listed channels (HOST, each at most once) end their signals where they are: the outputs the whole-signal converter still
+ * has for them, laid out and reported as a push's (channel order, whatever the list's), and the channels start again */
+OSStatus LBAudioDetectiveResamplerBankFinishChannels(LBAudioDetectiveResamplerBankRef inBank, const UInt32* inChannels, UInt32 inNumberOfChannels,
+                                                     UInt32* outNewCounts, Float32* outSamples, UInt64 inCapacity, UInt64* outNewTotal, void* inStream);
+/* host mirror, no device work: per channel the samples received and emitted since it (re)started (either pointer may be NULL,
+ * not both) */
+OSStatus LBAudioDetectiveResamplerBankGetCounts(LBAudioDetectiveResamplerBankRef inBank, UInt64* outInputTotals, UInt64* outOutputTotals);
+/* the listed channels start again without emitting anything: totals 0, nothing carried (the mirror alone changes) */
+OSStatus LBAudioDetectiveResamplerBankResetChannels(LBAudioDetectiveResamplerBankRef inBank, const UInt32* inChannels, UInt32 inNumberOfChannels);
+/* Debug / tests: the host plan of one call, needs no device.  Per channel, from inInputTotals samples received, inOutputTotals =
+ * emitted(inInputTotals) samples emitted and inSampleCounts new ones: outNew = the samples the call emits -- emitted(total) -
+ * emitted, or with inFinish != 0 n_out(total) - emitted --, outCarried = the samples the channel carries afterwards (0 with
+ * inFinish); *outTapLow / *outTapHigh (may be NULL) = m_lo / m_hi.  ArgumentInvalid for a pair New refuses and for an output total
+ * that is not the input total's. */
+OSStatus LBAudioDetectiveDebugResamplerBankPlan(Float64 inInputSampleRate, Float64 inOutputSampleRate, UInt32 inResamplerMode,
+                                                UInt32 inNumberOfChannels, const UInt64* inInputTotals, const UInt64* inOutputTotals,
+                                                const UInt32* inSampleCounts, UInt32 inFinish, UInt32* outNew, UInt32* outCarried,
+                                                SInt32* outTapLow, SInt32* outTapHigh);
+
 /* Stage 2 alone: inFrames = device pointer to inNumberOfFrames x 128 x bands float32 frame rows (what
  * LBAudioDetectiveFrameSetRow collects upstream) -> packed sub-fingerprints; outFramesHaar (optional)
  * receives the decomposed frames.  Replaces LBAudioDetectiveSynthesizeFingerprint

@@ -134,6 +134,18 @@ _SIGNATURES = {
     "LBAudioDetectiveStreamBankResetChannels": (OSStatus, [Ref, _P(UInt32), UInt32]),
     "LBAudioDetectiveDebugStreamBankPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, _P(UInt32), _P(UInt32), _P(UInt32), _P(UInt32),
                                                        _P(UInt32)]),
+    "LBAudioDetectiveResamplerBankNew": (Ref, [Float64, Float64, UInt32, UInt32]),
+    "LBAudioDetectiveResamplerBankDispose": (None, [Ref]),
+    "LBAudioDetectiveResamplerBankPushDevice": (OSStatus, [Ref, C.c_void_p, UInt32, _P(UInt32), _P(UInt32), C.c_void_p, UInt64, _P(UInt64),
+                                                           C.c_void_p]),
+    "LBAudioDetectiveResamplerBankPush": (OSStatus, [Ref, C.c_void_p, UInt32, _P(UInt32), _P(UInt32), C.c_void_p, UInt64, _P(UInt64),
+                                                     C.c_void_p]),
+    "LBAudioDetectiveResamplerBankFinishChannels": (OSStatus, [Ref, _P(UInt32), UInt32, _P(UInt32), C.c_void_p, UInt64, _P(UInt64),
+                                                               C.c_void_p]),
+    "LBAudioDetectiveResamplerBankGetCounts": (OSStatus, [Ref, _P(UInt64), _P(UInt64)]),
+    "LBAudioDetectiveResamplerBankResetChannels": (OSStatus, [Ref, _P(UInt32), UInt32]),
+    "LBAudioDetectiveDebugResamplerBankPlan": (OSStatus, [Float64, Float64, UInt32, UInt32, _P(UInt64), _P(UInt64), _P(UInt32), UInt32,
+                                                          _P(UInt32), _P(UInt32), _P(SInt32), _P(SInt32)]),
     "LBAudioDetectiveFingerprintClips": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p]),
     "LBAudioDetectiveFingerprintClipsFormat": (OSStatus, [Ref, C.c_void_p, UInt32, UInt64, UInt64, C.c_void_p]),
     "LBAudioDetectiveSetKernelVariant": (OSStatus, [Ref, UInt32]),

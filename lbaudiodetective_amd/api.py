@@ -659,6 +659,141 @@ class StreamBank:
         return corpus.query_packed_topk_keys_device(packed, packed.shape[0], n, k, aligned=aligned, range_=range_, stream=stream)
 
 
+def debug_resampler_bank_plan(rate_in: float, rate_out: float, mode: int, input_totals, output_totals, counts, finish: bool = False):
+    """LBAudioDetectiveDebugResamplerBankPlan (tests): the host plan of one resampler-bank call -> (new, carried, m_lo, m_hi): the
+    samples every channel emits and carries afterwards (uint32 arrays, one value per channel) and the rate pair's tap range.
+    Needs no GPU."""
+    li = np.ascontiguousarray(np.asarray(input_totals).reshape(-1), dtype=np.uint64)
+    lo = np.ascontiguousarray(np.asarray(output_totals).reshape(-1), dtype=np.uint64)
+    n, npt = _u32_list(counts)
+    if not li.size == lo.size == n.size:
+        raise ValueError("input totals, output totals and counts must have one value per channel")
+    out = [np.zeros(max(1, n.size), np.uint32) for _ in range(2)]
+    taps = [N.SInt32(0), N.SInt32(0)]
+    u64p = C.POINTER(N.UInt64)
+    _check(N.lib().LBAudioDetectiveDebugResamplerBankPlan(rate_in, rate_out, mode, n.size, li.ctypes.data_as(u64p) if li.size else None,
+                                                          lo.ctypes.data_as(u64p) if lo.size else None, npt, 1 if finish else 0,
+                                                          *[o.ctypes.data_as(C.POINTER(N.UInt32)) for o in out],
+                                                          *[C.byref(t) for t in taps]), "DebugResamplerBankPlan")
+    return out[0][:n.size], out[1][:n.size], int(taps[0].value), int(taps[1].value)
+
+
+class ResamplerBank:
+    """LBAudioDetectiveResamplerBankRef: `channels` live channels converted from `rate_in` to `rate_out` on the device, their filter
+    history kept there between pushes.  A push takes new samples (float32 or int16) of any of the channels and emits every output
+    sample that became final, laid out as StreamBank.push_device takes them; `feed` runs both pushes on one stream.  After L samples
+    in any chunking a channel has emitted a prefix of what the whole-signal converter gives, bit for bit; `finish` emits the rest."""
+
+    def __init__(self, rate_in: float, rate_out: float, channels: int, mode: int = 0):
+        self._L = N.lib()
+        self.rate_in, self.rate_out, self.n_channels, self.mode = float(rate_in), float(rate_out), int(channels), int(mode)
+        self._ref = self._L.LBAudioDetectiveResamplerBankNew(self.rate_in, self.rate_out, self.mode, self.n_channels)
+        if not self._ref:
+            raise LBAudioDetectiveError(1, "ResamplerBankNew (equal or unsupported rates, mode above 1, zero channels or no HIP device)")
+
+    def dispose(self):
+        if self._ref:
+            self._L.LBAudioDetectiveResamplerBankDispose(self._ref)
+            self._ref = None
+
+    def __del__(self):
+        try:
+            self.dispose()
+        except Exception:
+            pass
+
+    def _plan_total(self, counts, finish=False) -> int:
+        li, lo = self.totals()
+        return int(debug_resampler_bank_plan(self.rate_in, self.rate_out, self.mode, li, lo, counts, finish)[0].sum(dtype=np.uint64))
+
+    def _out(self, out, total, stream):
+        import torch
+        if out is None:                      # sized from the plan, which the host can make alone
+            with torch.cuda.stream(stream):  # (the block belongs to the stream that fills it)
+                out = torch.empty(total, dtype=torch.float32, device="cuda")
+        if not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float32:
+            raise ValueError("out must be a contiguous float32 device tensor")
+        return out
+
+    def _emit(self, call, what, out, stream):
+        new_counts = np.zeros(self.n_channels, np.uint32)
+        total = N.UInt64(0)
+        _check(call(new_counts.ctypes.data_as(C.POINTER(N.UInt32)), _dev_ptr(out) if out.numel() else None, out.numel(), C.byref(total),
+                    _stream_ptr(stream)), what)
+        return new_counts, out.reshape(-1)[:total.value]
+
+    def _push(self, fn, what, samples_ptr, fmt, counts, out, stream):
+        n, npt = _u32_list(counts)
+        if n.size != self.n_channels:
+            raise ValueError("counts must have one value per channel")
+        out = self._out(out, self._plan_total(n) if out is None else 0, stream)
+        return self._emit(lambda *rest: fn(self._ref, samples_ptr, fmt, npt, *rest), what, out, stream)
+
+    def push_device(self, samples, counts, out=None, stream=None):
+        """LBAudioDetectiveResamplerBankPushDevice: `samples`, a float32 or int16 device tensor holding the channels' new samples one
+        after the other in channel order; `counts`, one host integer per channel.  out: None (a tensor of exactly the emitted
+        samples is made) or a contiguous float32 device tensor with room for them -> (new_counts uint32 [channels] on the host,
+        the emitted samples float32 [total] on the device in channel order then time order).  Asynchronous on `stream`; `samples`
+        must stay untouched until the stream has run the call."""
+        import torch
+        if not samples.is_cuda or not samples.is_contiguous() or samples.dtype not in (torch.float32, torch.int16):
+            raise ValueError("samples must be a contiguous float32 or int16 device tensor")
+        if samples.numel() < int(np.asarray(counts, dtype=np.uint64).sum()):
+            raise ValueError("samples holds fewer values than the counts add up to")
+        return self._push(self._L.LBAudioDetectiveResamplerBankPushDevice, "ResamplerBankPushDevice",
+                          C.c_void_p(samples.data_ptr()) if samples.numel() else None, 1 if samples.dtype == torch.int16 else 0, counts, out,
+                          stream)
+
+    def push(self, chunks, out=None, stream=None):
+        """LBAudioDetectiveResamplerBankPush: `chunks`, one numpy array of new samples per channel (None or empty: nothing for that
+        channel), from host memory -- int16 when every array given is int16, float32 when none is, ValueError for a mixture;
+        returns as push_device once the samples have been taken."""
+        if len(chunks) != self.n_channels:
+            raise ValueError("chunks must have one entry per channel")
+        given = [np.asarray(c) for c in chunks if c is not None and np.asarray(c).size]
+        as_int = [g.dtype == np.int16 for g in given]
+        if any(as_int) and not all(as_int):      # (an int16 sample is s / 32768, not s: one push has one format)
+            raise ValueError("chunks mix int16 arrays with others: one push has one sample format")
+        dtype = np.int16 if given and all(as_int) else np.float32
+        parts = [np.ascontiguousarray(c, dtype=dtype).reshape(-1) if c is not None else np.zeros(0, dtype) for c in chunks]
+        x = np.concatenate(parts) if parts else np.zeros(0, dtype)
+        return self._push(self._L.LBAudioDetectiveResamplerBankPush, "ResamplerBankPush", C.c_void_p(x.ctypes.data) if x.size else None,
+                          1 if dtype == np.int16 else 0, [p.size for p in parts], out, stream)
+
+    def finish(self, channels, out=None, stream=None):
+        """LBAudioDetectiveResamplerBankFinishChannels: the listed channels end their signals where they are -> (new_counts, the
+        samples the whole-signal converter still has for them, in channel order), and start again."""
+        ch, cp = _u32_list(channels)
+        if out is None:
+            listed = np.zeros(self.n_channels, bool)
+            listed[ch[ch < self.n_channels]] = True
+            li, lo = self.totals()
+            new = debug_resampler_bank_plan(self.rate_in, self.rate_out, self.mode, li, lo, np.zeros(self.n_channels, np.uint32), True)[0]
+            out = self._out(None, int(new[listed].sum(dtype=np.uint64)), stream)
+        else:
+            out = self._out(out, 0, stream)
+        return self._emit(lambda *rest: self._L.LBAudioDetectiveResamplerBankFinishChannels(self._ref, cp, ch.size, *rest),
+                          "ResamplerBankFinishChannels", out, stream)
+
+    def totals(self):
+        """(samples received, samples emitted) of every channel since it (re)started (uint64 arrays, the host mirror)"""
+        out = [np.zeros(self.n_channels, np.uint64) for _ in range(2)]
+        _check(self._L.LBAudioDetectiveResamplerBankGetCounts(self._ref, *[o.ctypes.data_as(C.POINTER(N.UInt64)) for o in out]),
+               "ResamplerBankGetCounts")
+        return out[0], out[1]
+
+    def reset(self, channels):
+        """LBAudioDetectiveResamplerBankResetChannels: the listed channels start again, emitting nothing."""
+        ch, cp = _u32_list(channels)
+        _check(self._L.LBAudioDetectiveResamplerBankResetChannels(self._ref, cp, ch.size), "ResamplerBankResetChannels")
+
+    def feed(self, stream_bank: "StreamBank", samples, counts, new_out=None, stream=None):
+        """The live path: push_device, then stream_bank.push_device on what it emitted, on ONE stream with nothing read back.
+        Returns what StreamBank.push_device returns."""
+        new_counts, converted = self.push_device(samples, counts, stream=stream)
+        return stream_bank.push_device(converted, new_counts, new_out=new_out, stream=stream)
+
+
 class Corpus:
     """LBAudioDetectiveCorpusRef: device-resident reference fingerprints with a top-1 query."""
 

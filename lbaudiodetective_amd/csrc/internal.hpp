@@ -769,6 +769,55 @@ hipError_t launch_bank_commit(const BankDev& b, const BankRow* d_rows, uint32_t 
 // d_list[j] = (channel, ring slot of the oldest of its q rows) -> d_out[j][q][32 bytes] (16-byte aligned); n_list * q <= 2^31
 hipError_t launch_bank_window(const BankDev& b, const uint2* d_list, uint64_t n_list, uint32_t q, void* d_out, hipStream_t stream);
 
+// resampler bank (k_resample_bank.hip; api_resampler_bank.cpp is its host side).  The bank as its kernels read it:
+constexpr uint32_t kResamplerBankStageMax = 2816;      // samples of a run's staged input range (k_resample.hip's kInMaxR)
+constexpr uint32_t kResamplerBankMaxRun = 256;         // outputs of a run: one per lane
+constexpr uint64_t kResamplerBankNoPeriod = 0x80000000ull;
+constexpr uint32_t kResamplerBankPeriods = 4;          // periods of q outputs a workgroup takes side by side: one weight load for all
+constexpr uint32_t kResamplerBankMaxSpan = LBAD_RESAMPLER_BANK_MAX_TAP_SPAN;
+static_assert(kResamplerBankMaxSpan < kResamplerBankStageMax, "a run of one output can always be staged");
+struct ResamplerBankDev {
+    float* carry = nullptr;             // [2 sides][n_channels][carry_stride] carried samples
+    uint64_t carry_stride = 0;          // floats per channel and side: the tap span rounded up to a multiple of 4
+    uint64_t n_channels = 0;
+    uint64_t p = 0, q = 0;              // the rate pair in lowest terms, and its PhaseTable on the device
+    int32_t m_min = 0;
+    uint32_t m_span = 0;
+    const int32_t* first = nullptr;
+    const uint32_t* count = nullptr;
+    const double* wsum = nullptr;
+    const double* w = nullptr;
+    uint32_t run = 0;                   // outputs per workgroup: the most (<= 256) whose input range fits kResamplerBankStageMax
+    uint64_t period = 0;                // q where a unit takes positions inside the period in several periods (q >= 2 run); else
+                                        // kResamplerBankNoPeriod, above any call's outputs: a unit is a run of consecutive outputs
+};
+// One channel that received samples in a push or is being finished (88 bytes; the host plans the call and uploads these, in
+// channel order).  Signal indices count the channel's samples since it (re)started.
+struct ResamplerRow {
+    uint64_t fresh_at;                  // its first new sample inside the push's sample block
+    uint64_t L, end;                    // samples before the push; the in-signal bound L + n (only a finish has taps beyond it)
+    uint64_t out_first, ip0;            // its first output of the call and that output's (n p) div q
+    uint64_t out_at;                    // where that output goes in the caller's block (channel order, then time)
+    uint64_t c0, c1;                    // signal index of the first sample carried before / after the call
+    uint32_t r0;                        // the first output's phase (n p) mod q
+    uint32_t n, emit;                   // samples new, outputs to emit
+    uint32_t first_unit;                // its first unit (a run inside the period x a group of periods) among the call's
+    uint32_t channel, side;             // side: the carried buffer that holds x[c0, L)
+};
+static_assert(sizeof(ResamplerRow) == 88, "ResamplerRow is uploaded as it is");
+// format: 0 float32, 1 int16 samples at d_fresh.  n_units: the units of all rows (resampler_bank_units); d_out: the caller's block
+// units of a row that emits `emit` outputs: runs inside the period (the row's outputs where they are fewer) x groups of periods;
+// period: ResamplerBankDev::period
+inline uint64_t resampler_bank_units(uint64_t emit, uint64_t period, uint32_t run) {
+    const uint64_t in_period = emit < period ? emit : period, periods = (emit + period - 1) / period;
+    return ((in_period + run - 1) / run) * ((periods + kResamplerBankPeriods - 1) / kResamplerBankPeriods);
+}
+hipError_t launch_resampler_bank_convert(const ResamplerBankDev& b, const ResamplerRow* d_rows, uint32_t n_rows, const void* d_fresh,
+                                         uint32_t format, uint32_t n_units, float* d_out, hipStream_t stream);
+// behind it: what every row's channel carries on -- into the other side where it emitted an output
+hipError_t launch_resampler_bank_commit(const ResamplerBankDev& b, const ResamplerRow* d_rows, uint32_t n_rows, const void* d_fresh,
+                                        uint32_t format, hipStream_t stream);
+
 // measurement: ticks of the shader clock and of the constant 100 MHz clock over ~usec microseconds (2 words)
 hipError_t launch_clock_probe(uint32_t usec, unsigned long long* d_out, hipStream_t stream);
 // synthetic data

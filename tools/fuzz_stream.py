@@ -3,7 +3,9 @@
 tools/fuzz_stream.py [trials] [seed].  Streaming (random chunkings, empty and tiny chunks included) must equal
 ProcessPCM on the concatenation and the oracle; the host batch call must give the oracle's bits for float32, int16
 and int32 clips; a stream bank fed random chunkings of several channels at once (device or host samples, any history and
-pass size) must hand out, push by push, the oracle's rows of every channel and keep the last of them.
+pass size) must hand out, push by push, the oracle's rows of every channel and keep the last of them; a resampler bank (a random
+rate pair of the tested set, random chunkings, device or host samples, float32 or int16, an occasional finish and reset) must emit,
+push by push, the oracle converter's samples of every channel, bit for bit.
 Round 2: 60 000 trials (seed 3), 0 mismatches, 452 s on one MI355X."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,7 +33,7 @@ for t in range(trials):
                                    subfp_len=cfg.subfp_len)
     total = int(rng.integers(0, cfg.window + cfg.stride * 128 * 3 + 1000))
     pcm = O.synth_clip(int(rng.integers(0, 2**31)), 7, 44100, max(total, 1))[:total]
-    leg = rng.integers(0, 3)
+    leg = rng.integers(0, 4)
     if leg == 1:
         # ---- stream bank: several channels, one ragged push after the other ----
         import torch
@@ -64,6 +66,60 @@ for t in range(trials):
         if not ok:
             bad += 1
             print("BANK MISMATCH", t, cfg.sample_rate, cfg.window, cfg.stride, cfg.bands, cfg.subfp_len, n_ch, hist, total, flush=True)
+        continue
+    if leg == 3:
+        # ---- resampler bank: several channels, ragged pushes, finishes and resets ----
+        import torch
+        from math import gcd
+        rate_in, rate_out, mode = [(44100, 5512, 0), (48000, 5512, 0), (8000, 44100, 0), (44100, 48000, 0), (44100, 5512, 1), (48000, 8000, 1)][int(rng.integers(0, 6))]
+        p, q = rate_in // gcd(rate_in, rate_out), rate_out // gcd(rate_in, rate_out)
+        m_hi = lb.debug_resampler_bank_plan(rate_in, rate_out, mode, [0], [0], [0])[3]
+        n_ch, as_int = int(rng.integers(2, 6)), bool(rng.integers(0, 2))
+        longest = 25000 if p > q else 5000
+        raw = [np.round(O.synth_clip(int(rng.integers(0, 2**31)), c, rate_in, longest)[:int(rng.integers(0, longest + 1))] * 32767).astype(np.int16)
+               for c in range(n_ch)]
+        sigs = [x.astype(np.float32) * np.float32(1.0 / 32768.0) for x in raw]
+        emitted = lambda L: 0 if L <= m_hi else -((L - m_hi) * q // -p)
+        conv = lambda x: O.resample(x, rate_in, rate_out, mode)
+        want = [conv(x) for x in sigs]
+        bank = lb.ResamplerBank(rate_in, rate_out, n_ch, mode)
+        start, at, ok = [0] * n_ch, [0] * n_ch, True
+        while ok and any(a < x.size for a, x in zip(at, sigs)):
+            event = int(rng.integers(0, 12))
+            if event < 2:                                        # finish (0) or reset (1) a random set of channels
+                chosen = [c for c in range(n_ch) if rng.integers(0, 2)]
+                if event == 0:
+                    whole = [conv(sigs[c][start[c]:at[c]]) for c in chosen]
+                    new_counts, new = bank.finish(chosen)
+                    exp = [w[emitted(at[c] - start[c]):] for c, w in zip(chosen, whole)]
+                    ok = [int(new_counts[c]) for c in chosen] == [e.size for e in exp] and int(new_counts.sum()) == sum(e.size for e in exp) and \
+                        np.array_equal(new.cpu().numpy().view(np.uint32), np.concatenate(exp + [np.zeros(0, np.float32)]).view(np.uint32))
+                else:
+                    bank.reset(chosen)
+                for c in chosen:
+                    start[c] = at[c]
+                    want[c] = conv(sigs[c][at[c]:])
+                continue
+            counts = [min(int(rng.choice([0, 1, int(rng.integers(1, 100)), int(rng.integers(100, 3000)), int(rng.integers(3000, 12000))])),
+                          x.size - a) for a, x in zip(at, sigs)]
+            chunks = [(raw if as_int else sigs)[c][a:a + n] for c, (a, n) in enumerate(zip(at, counts))]
+            before = [emitted(a - s) for a, s in zip(at, start)]
+            at = [a + n for a, n in zip(at, counts)]
+            after = [emitted(a - s) for a, s in zip(at, start)]
+            if rng.integers(0, 2) == 0:
+                shift = int(rng.integers(0, 4))
+                flat = torch.from_numpy(np.concatenate([np.zeros(shift, chunks[0].dtype)] + chunks)).cuda()[shift:]
+                new_counts, new = bank.push_device(flat, counts)
+            else:
+                new_counts, new = bank.push([ch.astype(np.int16 if as_int else np.float32) for ch in chunks])
+            exp = np.concatenate([w[b:a] for w, b, a in zip(want, before, after)])
+            totals = bank.totals()
+            ok = new_counts.tolist() == [a - b for a, b in zip(after, before)] and totals[1].tolist() == after and \
+                totals[0].tolist() == [a - s for a, s in zip(at, start)] and np.array_equal(new.cpu().numpy().view(np.uint32), exp.view(np.uint32))
+        bank.dispose()
+        if not ok:
+            bad += 1
+            print("RESAMPLER BANK MISMATCH", t, rate_in, rate_out, mode, n_ch, as_int, [x.size for x in sigs], flush=True)
         continue
     if leg == 0:
         # ---- streaming ----

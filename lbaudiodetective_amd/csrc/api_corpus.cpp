@@ -173,16 +173,6 @@ OSStatus run_ragged(LBAudioDetectiveCorpus* c, const std::vector<uint32_t>& leng
     return noErr;
 }
 
-// n queries of `per` sub-fingerprints whose blocks a builder wrote to d_blocks, key i to keys[i] (d_scores: n == 1)
-OSStatus run_built_ragged(LBAudioDetectiveCorpus* c, const uint32_t* d_blocks, uint32_t n, uint32_t per, uint32_t range,
-                          uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
-    // (one length: the order is the caller's, a launch's blocks lie one after the other)
-    auto built = [&](const uint32_t* idx, uint32_t, uint32_t, const uint32_t*&, const uint32_t*& d) {
-        d = d_blocks + (size_t)idx[0] * sliding_block_words(per);
-    };
-    return run_ragged(c, std::vector<uint32_t>(n, per), false, built, range, index_base, d_scores, keys, stream);
-}
-
 // n queries against the ragged corpus, key i to keys[i]
 OSStatus run_queries_ragged(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
                             uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
@@ -237,14 +227,6 @@ OSStatus run_query_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerp
     LBAD_HIP(launch_compare_planes_generic(c->d_planes, c->capacity, c->count, c->n_sub, c->subfp_len, c->query.dev,
                                            q->count, range, index_base, d_scores, key_dst, stream));
     return c->query_ev[0].record(stream);
-}
-
-// (host allocations -- the packed query, its constant block -- can fail: nothing may unwind through the C boundary)
-OSStatus run_query(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprint* q, uint32_t range, uint64_t index_base,
-                   float* d_scores, unsigned long long* key_dst, hipStream_t stream) {
-    LBAD_GUARD_BEGIN
-    return run_query_impl(c, q, range, index_base, d_scores, key_dst, stream);
-    LBAD_GUARD_END
 }
 
 // LBAudioDetectiveCorpusQuery on the specialised scan: one launch, the result arrives in pinned memory
@@ -306,6 +288,26 @@ OSStatus query_fast(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprint
 }
 
 }  // namespace
+
+// ---- the scans the top-K, threshold and packed queries run (api_select.cpp; internal.hpp declares them) ----
+// n queries of `per` sub-fingerprints whose blocks a builder wrote to d_blocks, key i to keys[i] (d_scores: n == 1)
+OSStatus run_built_ragged(LBAudioDetectiveCorpus* c, const uint32_t* d_blocks, uint32_t n, uint32_t per, uint32_t range,
+                          uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream) {
+    // (one length: the order is the caller's, a launch's blocks lie one after the other)
+    auto built = [&](const uint32_t* idx, uint32_t, uint32_t, const uint32_t*&, const uint32_t*& d) {
+        d = d_blocks + (size_t)idx[0] * sliding_block_words(per);
+    };
+    return run_ragged(c, std::vector<uint32_t>(n, per), false, built, range, index_base, d_scores, keys, stream);
+}
+
+// (host allocations -- the packed query, its constant block -- can fail: nothing may unwind through the C boundary)
+OSStatus run_query(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprint* q, uint32_t range, uint64_t index_base,
+                   float* d_scores, unsigned long long* key_dst, hipStream_t stream) {
+    LBAD_GUARD_BEGIN
+    return run_query_impl(c, q, range, index_base, d_scores, key_dst, stream);
+    LBAD_GUARD_END
+}
+
 }  // namespace lbad
 
 extern "C" {
@@ -575,374 +577,10 @@ OSStatus LBAudioDetectiveCorpusQueryBatch(LBAudioDetectiveCorpusRef c, const LBA
     LBAD_GUARD_END
 }
 
-// ---- top-K queries: exact per-entry scores (the unchanged scans' scores path), then the selection of k_topk.hip ------
-namespace lbad {
-namespace {
-
-// one query's per-entry scores (count floats) to d_scores and the scan's own key word to d_key, on the call's stream
-using ScoreScan = std::function<OSStatus(uint32_t q, float* d_scores, unsigned long long* d_key)>;
-
-// score rows, selection scratch and the scans' key words for a call of n queries (allocated exactly: the score rows are the
-// size of the corpus).  The caller has waited for topk_ev: the previous top-K call's scans and selection may still read /
-// write the scratch, on whatever stream it ran.
-OSStatus reserve_topk(LBAudioDetectiveCorpus* c, uint32_t n) {
-    const uint32_t rows = n < kQueryBatchMax ? n : kQueryBatchMax;
-    OSStatus st = c->d_topk_scores.reserve((size_t)rows * c->count);
-    if (st == noErr) st = c->d_topk_scratch.reserve(topk_scratch_bytes(rows));
-    if (st == noErr) st = c->d_topk_scan_keys.reserve(kQueryBatchMax);
-    return st;
-}
-
-// The score rows of one group of g <= kQueryBatchMax staged queries (q0 the group's first) to d_topk_scores, row i at i * count:
-// d_qblocks given (the batch scan's blocks of ALL the call's queries, on the device): ONE pass of the batch scan; otherwise
-// scan_one per query.
-OSStatus scan_group_scores(LBAudioDetectiveCorpus* c, uint32_t q0, uint32_t g, hipStream_t stream, const uint32_t* d_qblocks,
-                           const ScoreScan& scan_one) {
-    if (d_qblocks) {
-        LBAD_HIP(launch_compare_planes_batch_scores(c->d_planes, c->capacity, c->count, c->n_sub,
-                                                    d_qblocks + (size_t)q0 * plane_query_words(), g, c->d_topk_scores, stream));
-        return noErr;
-    }
-    for (uint32_t i = 0; i < g; ++i) {
-        OSStatus st = scan_one(q0 + i, c->d_topk_scores + (size_t)i * c->count, c->d_topk_scan_keys + i);
-        if (st != noErr) return st;
-    }
-    return noErr;
-}
-
-// The scans and the selection of n staged queries, their keys to keys (device, n x k): groups of up to kQueryBatchMax queries
-// write their score rows (scan_group_scores), then one selection over the group's rows.
-OSStatus topk_scan_select(LBAudioDetectiveCorpus* c, uint32_t n, uint32_t k, uint64_t index_base, unsigned long long* keys,
-                          hipStream_t stream, const uint32_t* d_qblocks, const ScoreScan& scan_one) {
-    for (uint32_t q0 = 0; q0 < n; q0 += kQueryBatchMax) {
-        const uint32_t g = n - q0 < kQueryBatchMax ? n - q0 : kQueryBatchMax;
-        OSStatus st = scan_group_scores(c, q0, g, stream, d_qblocks, scan_one);
-        if (st != noErr) return st;
-        LBAD_HIP(launch_topk_keys(c->d_topk_scores, c->count, g, k, index_base, c->d_topk_scratch, keys + (size_t)q0 * k, stream));
-    }
-    return noErr;
-}
-
-// ... and the same scans with the threshold selection of k_threshold.hip behind them: n x capacity keys and n counts
-OSStatus threshold_scan_select(LBAudioDetectiveCorpus* c, uint32_t n, float threshold, uint64_t capacity, uint64_t index_base,
-                               unsigned long long* keys, unsigned long long* counts, hipStream_t stream, const uint32_t* d_qblocks,
-                               const ScoreScan& scan_one) {
-    for (uint32_t q0 = 0; q0 < n; q0 += kQueryBatchMax) {
-        const uint32_t g = n - q0 < kQueryBatchMax ? n - q0 : kQueryBatchMax;
-        OSStatus st = scan_group_scores(c, q0, g, stream, d_qblocks, scan_one);
-        if (st != noErr) return st;
-        LBAD_HIP(launch_threshold_keys(c->d_topk_scores, c->count, g, threshold, capacity, index_base, c->d_threshold_scratch,
-                                       keys + (size_t)q0 * capacity, counts + q0, stream));
-    }
-    return noErr;
-}
-
-// the batch scan's blocks of n queries (uniform corpus, the specialised shape) through the pinned staging copy to the device,
-// every group's at once: the copy is asynchronous on `stream`
-OSStatus stage_plane_queries(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
-                             hipStream_t stream) {
-    const uint32_t kw = plane_query_words();
-    const size_t bytes = (size_t)n * kw * sizeof(uint32_t);
-    OSStatus st = c->topk_q.reserve((size_t)n * kw);
-    if (st != noErr) return st;
-    std::memset(c->topk_q.host, 0, bytes);
-    std::vector<uint32_t> slots, block;
-    for (uint32_t i = 0; i < n; ++i) {
-        pack_fingerprint(qs[i], slots);
-        build_plane_query(slots.data(), c->n_sub, range, block);
-        std::memcpy(c->topk_q.host + (size_t)i * kw, block.data(), block.size() * sizeof(uint32_t));
-    }
-    LBAD_HIP(hipMemcpyAsync(c->topk_q.dev, c->topk_q.host, bytes, hipMemcpyHostToDevice, stream));
-    return noErr;
-}
-
-// inCount queries, their keys to keys (device, inCount x k): the queries staged from their handles (uniform corpus, the
-// specialised shape: the batch scan's blocks; otherwise each scores scan stages its own), then topk_scan_select
-OSStatus topk_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range, uint32_t k,
-                        uint64_t index_base, unsigned long long* keys, hipStream_t stream) {
-    if (!c || !qs || !keys || n == 0 || k == 0 || k > kTopKMax) return kLBAudioDetectiveArgumentInvalid;
-    if (index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
-    for (uint32_t i = 0; i < n; ++i)
-        if (!qs[i] || qs[i]->length != c->subfp_len || qs[i]->count == 0) return kLBAudioDetectiveArgumentInvalid;
-    if (range == 0) range = c->subfp_len;   // LBAudioDetective.m:443-445
-    bool batch_scan = !c->ragged && c->variant != 1;
-    for (uint32_t i = 0; i < n && batch_scan; ++i) batch_scan = planes_fast_supported(c->subfp_len, c->n_sub, qs[i]->count);
-    OSStatus st = c->topk_ev.wait_or_create();
-    if (st != noErr) return st;
-    if (c->count == 0) {
-        LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * k * sizeof(unsigned long long), stream));
-        return c->topk_ev.record(stream);
-    }
-    st = reserve_topk(c, n);
-    if (st != noErr) return st;
-    if (batch_scan) {
-        st = stage_plane_queries(c, qs, n, range, stream);
-        if (st != noErr) return st;
-    }
-    st = topk_scan_select(c, n, k, index_base, keys, stream, batch_scan ? c->topk_q.dev.get() : nullptr,
-                          [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
-                              return run_query(c, qs[q], range, 0, d_scores, d_key, stream);
-                          });
-    if (st != noErr) return st;
-    return c->topk_ev.record(stream);
-}
-
-// ---- packed queries: the blocks come from the builders of k_query.hip instead of the handles' Booleans ---------------------
-struct BuiltQueries {
-    const uint32_t* scan = nullptr;      // ragged: sliding blocks; uniform: plane blocks (fast) or the rows cleared from the length on
-    bool fast = false;
-    const uint2* desc = nullptr;         // with lags: launch_align_keys' table and words
-    const uint32_t* words = nullptr;
-};
-
-// n queries of `per` packed sub-fingerprints at d_rows (device) -> their blocks in the corpus' scratch, on `stream`.  Waits
-// (on the host, as the top-K scratch does) for the previous packed call's event; the caller records pq_ev behind its last kernel.
-OSStatus build_packed(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t n, uint32_t per, uint32_t range, bool lags,
-                      hipStream_t stream, BuiltQueries& out) {
-    if ((uint64_t)n * per > 0xFFFFFFFFull) return kLBAudioDetectiveArgumentInvalid;      // (the tables count sub-fingerprints in 32 bits)
-    if (lags && (per > 0x7FFFFFFFu || (c->ragged && c->ne_max > 0x7FFFFFFFu))) return kLBAudioDetectiveArgumentInvalid;   // (a lag is a signed 32-bit offset)
-    out.fast = !c->ragged && c->variant != 1 && planes_fast_supported(c->subfp_len, c->n_sub, per);
-    if (!c->ragged) {
-        if (c->variant == 2 && !out.fast) return kLBAudioDetectiveArgumentInvalid;
-        if (!out.fast && (size_t)per * kPackedWords * 4 > 48 * 1024) return kLBAudioDetectiveArgumentInvalid;     // (the generic scan keeps the query in LDS)
-    }
-    const size_t row_words = (size_t)n * per * kPackedWords;
-    const size_t scan_words = c->ragged ? (size_t)n * sliding_block_words(per) : (out.fast ? (size_t)n * plane_query_words() : row_words);
-    const bool rows_serve_both = !c->ragged && !out.fast;         // the generic scan and the uniform alignment read the same words
-    // (every part starts on a 256-byte boundary, as the staging slots of the handle path do)
-    const size_t desc_words = lags ? (((size_t)2 * n + 63) & ~(size_t)63) : 0;
-    const size_t align_words = lags && !rows_serve_both ? ((row_words + 63) & ~(size_t)63) : 0;
-    OSStatus st = c->pq_ev.wait_or_create();
-    if (st == noErr) st = c->d_pq.reserve(desc_words + align_words + scan_words);
-    if (st != noErr) return st;
-    uint2* desc = lags ? reinterpret_cast<uint2*>(c->d_pq.get()) : nullptr;
-    uint32_t* words = c->d_pq + desc_words;
-    uint32_t* scan = words + align_words;
-    if (c->ragged) {
-        LBAD_HIP(launch_build_sliding_queries(d_rows, n, per, c->subfp_len, range, scan, stream));
-        if (lags) LBAD_HIP(launch_build_query_rows(d_rows, n, per, c->subfp_len, true, words, desc, stream));
-    } else if (out.fast) {
-        LBAD_HIP(launch_build_plane_queries(d_rows, n, c->n_sub, range, scan, stream));
-        if (lags) LBAD_HIP(launch_build_query_rows(d_rows, n, per, c->subfp_len, false, words, desc, stream));
-    } else {
-        LBAD_HIP(launch_build_query_rows(d_rows, n, per, c->subfp_len, false, scan, desc, stream));
-        words = scan;
-    }
-    out.scan = scan;
-    out.desc = desc;
-    out.words = lags ? words : nullptr;
-    return noErr;
-}
-
-// one built query's scan with per-entry scores (top-K) or without (d_scores null; uniform generic shapes, top-1)
-OSStatus scan_built_one(LBAudioDetectiveCorpus* c, const BuiltQueries& b, uint32_t q, uint32_t per, uint32_t range, uint64_t index_base,
-                        float* d_scores, unsigned long long* d_key, hipStream_t stream) {
-    if (c->ragged)
-        return run_built_ragged(c, b.scan + (size_t)q * sliding_block_words(per), 1, per, range, index_base, d_scores, d_key, stream);
-    LBAD_HIP(hipMemsetAsync(d_key, 0, sizeof(unsigned long long), stream));
-    LBAD_HIP(launch_compare_planes_generic(c->d_planes, c->capacity, c->count, c->n_sub, c->subfp_len, b.scan + (size_t)q * per * kPackedWords,
-                                           per, range, index_base, d_scores, d_key, stream));
-    return noErr;
-}
-
-OSStatus packed_keys_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t n, uint32_t per, uint32_t range,
-                          uint64_t index_base, unsigned long long* keys, hipStream_t stream) {
-    if (!c || !d_rows || !keys || n == 0 || per == 0) return kLBAudioDetectiveArgumentInvalid;
-    if (index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
-    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    if (range == 0) range = c->subfp_len;   // LBAudioDetective.m:443-445
-    BuiltQueries b;
-    OSStatus st = build_packed(c, d_rows, n, per, range, false, stream, b);
-    if (st != noErr) return st;
-    if (c->ragged) {
-        st = run_built_ragged(c, b.scan, n, per, range, index_base, nullptr, keys, stream);
-    } else if (b.fast) {
-        // the batch scan even for one query: it equals the single-query scan bit for bit
-        st = hip_status(hipMemsetAsync(keys, 0, (size_t)n * sizeof(unsigned long long), stream), "keys", __LINE__);
-        if (st == noErr)
-            st = hip_status(launch_compare_planes_batch(c->d_planes, c->capacity, c->count, c->n_sub, b.scan, n, index_base, keys, stream),
-                            "batch scan", __LINE__);
-    } else {
-        for (uint32_t q = 0; q < n && st == noErr; ++q) st = scan_built_one(c, b, q, per, range, index_base, nullptr, keys + q, stream);
-    }
-    const OSStatus rec = c->pq_ev.record(stream);     // (also behind what a failed call did launch)
-    return st != noErr ? st : rec;
-}
-
-OSStatus packed_topk_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t n, uint32_t per, uint32_t range, uint32_t k,
-                          uint64_t index_base, unsigned long long* keys, int32_t* lags, hipStream_t stream) {
-    if (!c || !d_rows || !keys || n == 0 || per == 0 || k == 0 || k > kTopKMax) return kLBAudioDetectiveArgumentInvalid;
-    if (index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
-    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    if (range == 0) range = c->subfp_len;
-    OSStatus st = c->topk_ev.wait_or_create();
-    if (st != noErr) return st;
-    BuiltQueries b;
-    st = build_packed(c, d_rows, n, per, range, lags != nullptr, stream, b);
-    if (st != noErr) return st;
-    if (c->count == 0) {                                   // nothing to select from: zero keys, zero lags
-        st = hip_status(hipMemsetAsync(keys, 0, (size_t)n * k * sizeof(unsigned long long), stream), "keys", __LINE__);
-        if (st == noErr && lags) st = hip_status(hipMemsetAsync(lags, 0, (size_t)n * k * sizeof(int32_t), stream), "lags", __LINE__);
-    } else {
-        st = reserve_topk(c, n);
-        if (st == noErr)
-            st = topk_scan_select(c, n, k, index_base, keys, stream, b.fast ? b.scan : nullptr,
-                                  [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
-                                      return scan_built_one(c, b, q, per, range, 0, d_scores, d_key, stream);
-                                  });
-    }
-    OSStatus rec = c->topk_ev.record(stream);
-    if (st == noErr && rec == noErr && lags && c->count != 0)
-        st = align_keys_built(c, b.desc, b.words, n, per, range, k, keys, index_base, lags, stream);
-    const OSStatus rec2 = c->pq_ev.record(stream);
-    return st != noErr ? st : (rec != noErr ? rec : rec2);
-}
-
-// host-returning form: keys through the corpus' own buffer on the null stream, then decoded
-OSStatus topk_host_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range, uint32_t k,
-                        SInt64* out_idx, Float32* out_scores, UInt32* out_counts) {
-    if (!c || !qs || n == 0 || k == 0 || k > kTopKMax || !out_idx || !out_scores || !out_counts) return kLBAudioDetectiveArgumentInvalid;
-    OSStatus st = c->topk_ev.wait();    // (the key buffer is the previous call's until then)
-    const size_t words = (size_t)n * k;
-    if (st == noErr) st = c->d_topk_keys.reserve(words);
-    if (st == noErr) st = topk_keys_impl(c, qs, n, range, k, 0, c->d_topk_keys, nullptr);
-    if (st != noErr) return st;
-    std::vector<unsigned long long> keys(words);
-    LBAD_HIP(hipMemcpy(keys.data(), c->d_topk_keys, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    for (uint32_t q = 0; q < n; ++q) {
-        UInt32 got = 0;
-        for (uint32_t i = 0; i < k; ++i) {
-            LBAudioDetectiveCorpusDecodeKey(keys[(size_t)q * k + i], out_idx + (size_t)q * k + i, out_scores + (size_t)q * k + i);
-            if (out_idx[(size_t)q * k + i] >= 0) ++got;
-        }
-        out_counts[q] = got;
-    }
-    return noErr;
-}
-
-// ---- threshold queries: the same scores scans, then every entry at or above the threshold (k_threshold.hip) ------------------
-// what needs neither corpus nor device: a finite threshold above 0, at least one slot per row, n x capacity <= 2^31 slots
-bool threshold_args_ok(uint32_t n, float threshold, uint64_t capacity) {
-    return n != 0 && std::isfinite(threshold) && threshold > 0.0f && capacity != 0 && capacity <= 0x80000000ull &&
-           (uint64_t)n * capacity <= 0x80000000ull;
-}
-
-// score rows, the scans' key words and the selection's tile words for a call of n queries; the caller has waited for topk_ev
-OSStatus reserve_threshold(LBAudioDetectiveCorpus* c, uint32_t n) {
-    const uint32_t rows = n < kQueryBatchMax ? n : kQueryBatchMax;
-    OSStatus st = c->d_topk_scores.reserve((size_t)rows * c->count);
-    if (st == noErr) st = c->d_threshold_scratch.reserve(threshold_scratch_bytes(c->count, rows));
-    if (st == noErr) st = c->d_topk_scan_keys.reserve(kQueryBatchMax);
-    return st;
-}
-
-// zero keys (and lags) and zero counts: the answer of an empty corpus
-OSStatus threshold_nothing(uint32_t n, uint64_t capacity, unsigned long long* keys, unsigned long long* counts, int32_t* lags,
-                           hipStream_t stream) {
-    LBAD_HIP(hipMemsetAsync(keys, 0, (size_t)n * capacity * sizeof(unsigned long long), stream));
-    LBAD_HIP(hipMemsetAsync(counts, 0, (size_t)n * sizeof(unsigned long long), stream));
-    if (lags) LBAD_HIP(hipMemsetAsync(lags, 0, (size_t)n * capacity * sizeof(int32_t), stream));
-    return noErr;
-}
-
-// n queries staged from their handles as topk_keys_impl stages them, their n x capacity keys and n counts to the device
-OSStatus threshold_keys_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
-                             float threshold, uint64_t capacity, uint64_t index_base, unsigned long long* keys,
-                             unsigned long long* counts, hipStream_t stream) {
-    if (!qs || !keys || !counts || !threshold_args_ok(n, threshold, capacity)) return kLBAudioDetectiveArgumentInvalid;
-    for (uint32_t i = 0; i < n; ++i)
-        if (!qs[i] || qs[i]->count == 0) return kLBAudioDetectiveArgumentInvalid;
-    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    if (!c || index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
-    for (uint32_t i = 0; i < n; ++i)
-        if (qs[i]->length != c->subfp_len) return kLBAudioDetectiveArgumentInvalid;
-    if (range == 0) range = c->subfp_len;   // LBAudioDetective.m:443-445
-    bool batch_scan = !c->ragged && c->variant != 1;
-    for (uint32_t i = 0; i < n && batch_scan; ++i) batch_scan = planes_fast_supported(c->subfp_len, c->n_sub, qs[i]->count);
-    OSStatus st = c->topk_ev.wait_or_create();
-    if (st != noErr) return st;
-    if (c->count == 0) {
-        st = threshold_nothing(n, capacity, keys, counts, nullptr, stream);
-        return st != noErr ? st : c->topk_ev.record(stream);
-    }
-    st = reserve_threshold(c, n);
-    if (st == noErr && batch_scan) st = stage_plane_queries(c, qs, n, range, stream);
-    if (st != noErr) return st;
-    st = threshold_scan_select(c, n, threshold, capacity, index_base, keys, counts, stream, batch_scan ? c->topk_q.dev.get() : nullptr,
-                               [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
-                                   return run_query(c, qs[q], range, 0, d_scores, d_key, stream);
-                               });
-    if (st != noErr) return st;
-    return c->topk_ev.record(stream);
-}
-
-// the packed form: the builders' blocks (build_packed), the same scans and selection, and the lags of the compacted keys
-OSStatus packed_threshold_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t n, uint32_t per, uint32_t range,
-                               float threshold, uint64_t capacity, uint64_t index_base, unsigned long long* keys,
-                               unsigned long long* counts, int32_t* lags, hipStream_t stream) {
-    if (!d_rows || !keys || !counts || per == 0 || !threshold_args_ok(n, threshold, capacity)) return kLBAudioDetectiveArgumentInvalid;
-    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    if (!c || index_base + c->count > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
-    if (range == 0) range = c->subfp_len;
-    OSStatus st = c->topk_ev.wait_or_create();
-    if (st != noErr) return st;
-    BuiltQueries b;
-    st = build_packed(c, d_rows, n, per, range, lags != nullptr, stream, b);
-    if (st != noErr) return st;
-    if (c->count == 0) {
-        st = threshold_nothing(n, capacity, keys, counts, lags, stream);
-    } else {
-        st = reserve_threshold(c, n);
-        if (st == noErr)
-            st = threshold_scan_select(c, n, threshold, capacity, index_base, keys, counts, stream, b.fast ? b.scan : nullptr,
-                                       [&](uint32_t q, float* d_scores, unsigned long long* d_key) {
-                                           return scan_built_one(c, b, q, per, range, 0, d_scores, d_key, stream);
-                                       });
-    }
-    OSStatus rec = c->topk_ev.record(stream);
-    if (st == noErr && rec == noErr && lags && c->count != 0)       // (capacity <= 2^31 slots: it fits the alignment's 32-bit k)
-        st = align_keys_built(c, b.desc, b.words, n, per, range, (uint32_t)capacity, keys, index_base, lags, stream);
-    const OSStatus rec2 = c->pq_ev.record(stream);
-    return st != noErr ? st : (rec != noErr ? rec : rec2);
-}
-
-// host-returning forms: keys, counts and (out_lags given) lags in ONE block of the corpus' own key buffer on the null stream,
-// one read-back, then decoded.  A list that was cut (count > capacity) is no error.
-OSStatus threshold_host_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
-                             float threshold, uint64_t capacity, SInt64* out_idx, Float32* out_scores, SInt32* out_lags, bool want_lags,
-                             UInt64* out_counts) {
-    if (!qs || !out_idx || !out_scores || !out_counts || (want_lags && !out_lags) || !threshold_args_ok(n, threshold, capacity))
-        return kLBAudioDetectiveArgumentInvalid;
-    for (uint32_t i = 0; i < n; ++i)
-        if (!qs[i] || qs[i]->count == 0 || (want_lags && qs[i]->count > 0x7FFFFFFFu)) return kLBAudioDetectiveArgumentInvalid;
-    if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    if (!c) return kLBAudioDetectiveArgumentInvalid;
-    OSStatus st = c->topk_ev.wait();    // (the key buffer is the previous call's until then)
-    const size_t slots = (size_t)n * capacity;
-    const size_t words = slots + n + (want_lags ? (slots + 1) / 2 : 0);
-    if (st == noErr) st = c->d_topk_keys.reserve(words);
-    if (st != noErr) return st;
-    unsigned long long* d_keys = c->d_topk_keys;
-    unsigned long long* d_counts = d_keys + slots;
-    int32_t* d_lags = reinterpret_cast<int32_t*>(d_counts + n);
-    st = threshold_keys_impl(c, qs, n, range, threshold, capacity, 0, d_keys, d_counts, nullptr);
-    if (st == noErr && want_lags && c->count != 0)
-        st = align_keys_handles(c, qs, n, range, (uint32_t)capacity, d_keys, 0, d_lags, nullptr);
-    if (st != noErr) return st;
-    std::vector<unsigned long long> host(words);
-    LBAD_HIP(hipMemcpy(host.data(), d_keys, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    const int32_t* lags = reinterpret_cast<const int32_t*>(host.data() + slots + n);
-    for (size_t at = 0; at < slots; ++at) {
-        LBAudioDetectiveCorpusDecodeKey(host[at], out_idx + at, out_scores + at);
-        if (want_lags) out_lags[at] = out_idx[at] >= 0 && c->count != 0 ? lags[at] : 0;
-    }
-    for (uint32_t q = 0; q < n; ++q) out_counts[q] = host[slots + q];
-    return noErr;
-}
-
-
 // ---- corpus join: the entries of `q` as queries against `c`, every pair at or above the threshold as CSR (k_join.hip) --------
 // (kJoinScratchDefault: internal.hpp, shared with api_occurrences.cpp)
+namespace lbad {
+namespace {
 
 // what needs neither handle nor device
 bool join_args_ok(uint64_t first, uint64_t count, float threshold, uint64_t capacity, uint64_t index_base) {
@@ -1029,8 +667,9 @@ OSStatus join_keys_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, ui
     return st != noErr ? st : (rec != noErr ? rec : rec2);
 }
 
-// host-returning form: keys and offsets (and the ragged join's lags behind them, where they are wanted) in ONE block of the
-// corpus' key buffer on the null stream, one read-back, then decoded
+// host-returning form: keys and offsets -- the count + 1 offsets ride as keys behind the capacity slots -- and the ragged join's
+// lags, where they are wanted, as the 32-bit values in ONE block of the corpus' key buffer on the null stream (key_block_*), one
+// read-back, then decoded
 OSStatus join_host_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, uint64_t first, uint64_t count, uint32_t range,
                         float threshold, uint32_t skip, uint64_t capacity, bool ragged, SInt64* out_rows, SInt64* out_idx,
                         Float32* out_scores, SInt32* out_lags, UInt64* out_total) {
@@ -1040,19 +679,15 @@ OSStatus join_host_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, ui
     uint64_t chunk = 0;
     OSStatus st = join_plan(c, q, first, count, 0, ragged, &chunk);   // (a refused call reserves nothing)
     if (st != noErr) return st;
-    st = c->topk_ev.wait();             // (the key buffer is the previous top-K or threshold call's until then)
-    const size_t words = (size_t)capacity + count + 1 + (out_lags ? (capacity + 1) / 2 : 0);
-    if (st == noErr) st = c->d_topk_keys.reserve(words);
+    KeyBlock b;
+    st = key_block_reserve(c, (size_t)capacity + count + 1, out_lags ? (size_t)capacity : 0, &b);
     if (st != noErr) return st;
-    unsigned long long* d_keys = c->d_topk_keys;
-    int32_t* d_lags = out_lags ? reinterpret_cast<int32_t*>(d_keys + capacity + count + 1) : nullptr;
-    st = join_keys_impl(c, q, first, count, range, threshold, skip, capacity, 0, ragged, d_keys, d_lags, d_keys + capacity, nullptr);
-    if (st != noErr) {
-        (void)hipStreamSynchronize(nullptr);       // whatever was launched has left the key buffer before its next user
-        return st;
-    }
-    std::vector<unsigned long long> host(words);
-    LBAD_HIP(hipMemcpy(host.data(), d_keys, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    st = join_keys_impl(c, q, first, count, range, threshold, skip, capacity, 0, ragged, b.d_keys, reinterpret_cast<int32_t*>(b.d_words),
+                        b.d_keys + capacity, nullptr);
+    if (st != noErr) return key_block_failed(st);
+    std::vector<unsigned long long> host;
+    st = key_block_read(b, b.n_keys, &host);
+    if (st != noErr) return st;
     const unsigned long long* off = host.data() + capacity;
     const int32_t* lags = reinterpret_cast<const int32_t*>(off + count + 1);
     uint64_t row = 0;
@@ -1073,55 +708,6 @@ OSStatus join_host_impl(LBAudioDetectiveCorpus* c, LBAudioDetectiveCorpus* q, ui
 }  // namespace lbad
 
 extern "C" {
-
-OSStatus LBAudioDetectiveCorpusQueryBatchThresholdKeysDevice(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
-                                                             UInt32 inCount, UInt32 inRange, Float32 inThreshold, UInt64 inCapacity,
-                                                             UInt64 inIndexBase, void* outKeys, void* outCounts, void* inStream) {
-    LBAD_GUARD_BEGIN
-    return lbad::threshold_keys_impl(c, inQueries, inCount, inRange, inThreshold, inCapacity, inIndexBase,
-                                     static_cast<unsigned long long*>(outKeys), static_cast<unsigned long long*>(outCounts),
-                                     static_cast<hipStream_t>(inStream));
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveCorpusQueryBatchThreshold(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
-                                                   UInt32 inCount, UInt32 inRange, Float32 inThreshold, UInt64 inCapacity,
-                                                   SInt64* outIndices, Float32* outScores, UInt64* outCounts) {
-    LBAD_GUARD_BEGIN
-    return lbad::threshold_host_impl(c, inQueries, inCount, inRange, inThreshold, inCapacity, outIndices, outScores, nullptr, false,
-                                     outCounts);
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveCorpusQueryBatchThresholdAligned(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
-                                                          UInt32 inCount, UInt32 inRange, Float32 inThreshold, UInt64 inCapacity,
-                                                          SInt64* outIndices, Float32* outScores, SInt32* outLags, UInt64* outCounts) {
-    LBAD_GUARD_BEGIN
-    return lbad::threshold_host_impl(c, inQueries, inCount, inRange, inThreshold, inCapacity, outIndices, outScores, outLags, true,
-                                     outCounts);
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveCorpusQueryThreshold(LBAudioDetectiveCorpusRef c, LBAudioDetectiveFingerprintRef inQuery, UInt32 inRange,
-                                              Float32 inThreshold, UInt64 inCapacity, SInt64* outIndices, Float32* outScores,
-                                              UInt64* outCount) {
-    LBAD_GUARD_BEGIN
-    if (!inQuery) return kLBAudioDetectiveArgumentInvalid;
-    return lbad::threshold_host_impl(c, &inQuery, 1, inRange, inThreshold, inCapacity, outIndices, outScores, nullptr, false, outCount);
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice(LBAudioDetectiveCorpusRef c, const void* inPackedQueries, UInt32 inCount,
-                                                              UInt32 inSubfingerprintsPerQuery, UInt32 inRange, Float32 inThreshold,
-                                                              UInt64 inCapacity, UInt64 inIndexBase, void* outKeys, void* outCounts,
-                                                              void* outLags, void* inStream) {
-    LBAD_GUARD_BEGIN
-    return lbad::packed_threshold_impl(c, static_cast<const uint32_t*>(inPackedQueries), inCount, inSubfingerprintsPerQuery, inRange,
-                                       inThreshold, inCapacity, inIndexBase, static_cast<unsigned long long*>(outKeys),
-                                       static_cast<unsigned long long*>(outCounts), static_cast<int32_t*>(outLags),
-                                       static_cast<hipStream_t>(inStream));
-    LBAD_GUARD_END
-}
 
 OSStatus LBAudioDetectiveCorpusJoinThresholdKeysDevice(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveCorpusRef inQueries,
                                                        UInt64 inFirstQuery, UInt64 inQueryCount, UInt32 inRange, Float32 inThreshold,
@@ -1177,76 +763,6 @@ OSStatus LBAudioDetectiveCorpusSetJoinScratchLimit(LBAudioDetectiveCorpusRef inC
         inCorpus->d_join_scratch.reset();
     }
     return noErr;
-}
-
-OSStatus LBAudioDetectiveThresholdKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, Float32 inThreshold,
-                                                       UInt64 inCapacity, UInt64 inIndexBase, void* outKeys, void* outCounts,
-                                                       void* inStream) {
-    LBAD_GUARD_BEGIN
-    if (!inScores || !outKeys || !outCounts || !lbad::threshold_args_ok(inRows, inThreshold, inCapacity))
-        return kLBAudioDetectiveArgumentInvalid;
-    if (inCount > 0x100000000ull || inIndexBase + inCount > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
-    if (!lbad::device_ready()) return kLBAudioDetectiveDeviceUnavailable;
-    hipStream_t stream = static_cast<hipStream_t>(inStream);
-    unsigned long long* keys = static_cast<unsigned long long*>(outKeys);
-    unsigned long long* counts = static_cast<unsigned long long*>(outCounts);
-    const uint32_t rows = inRows < lbad::kThresholdRowsMax ? inRows : lbad::kThresholdRowsMax;
-    lbad::DeviceBuffer<void> scratch;                      // (its own, not counted among a corpus' bytes for long: freed on return)
-    OSStatus st = scratch.reserve(lbad::threshold_scratch_bytes(inCount, rows));
-    if (st != noErr) return st;
-    for (uint32_t r0 = 0; r0 < inRows && st == noErr; r0 += rows) {
-        const uint32_t g = inRows - r0 < rows ? inRows - r0 : rows;
-        st = lbad::hip_status(lbad::launch_threshold_keys(inScores + (size_t)r0 * inCount, inCount, g, inThreshold, inCapacity, inIndexBase,
-                                                          scratch, keys + (size_t)r0 * inCapacity, counts + r0, stream),
-                              "threshold selection", __LINE__);
-    }
-    const OSStatus done = lbad::hip_status(hipStreamSynchronize(stream), "threshold selection", __LINE__);
-    return st != noErr ? st : done;
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveCorpusQueryBatchTopKKeysDevice(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
-                                                        UInt32 inCount, UInt32 inRange, UInt32 inK, UInt64 inIndexBase,
-                                                        void* outKeys, void* inStream) {
-    LBAD_GUARD_BEGIN
-    return lbad::topk_keys_impl(c, inQueries, inCount, inRange, inK, inIndexBase, static_cast<unsigned long long*>(outKeys),
-                                static_cast<hipStream_t>(inStream));
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveCorpusQueryBatchTopK(LBAudioDetectiveCorpusRef c, const LBAudioDetectiveFingerprintRef* inQueries,
-                                              UInt32 inCount, UInt32 inRange, UInt32 inK, SInt64* outIndices, Float32* outScores,
-                                              UInt32* outCounts) {
-    LBAD_GUARD_BEGIN
-    return lbad::topk_host_impl(c, inQueries, inCount, inRange, inK, outIndices, outScores, outCounts);
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveCorpusQueryTopK(LBAudioDetectiveCorpusRef c, LBAudioDetectiveFingerprintRef inQuery, UInt32 inRange,
-                                         UInt32 inK, SInt64* outIndices, Float32* outScores, UInt32* outCount) {
-    LBAD_GUARD_BEGIN
-    if (!inQuery) return kLBAudioDetectiveArgumentInvalid;
-    return lbad::topk_host_impl(c, &inQuery, 1, inRange, inK, outIndices, outScores, outCount);
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveCorpusQueryPackedKeysDevice(LBAudioDetectiveCorpusRef c, const void* inPackedQueries, UInt32 inCount,
-                                                     UInt32 inSubfingerprintsPerQuery, UInt32 inRange, UInt64 inIndexBase, void* outKeys,
-                                                     void* inStream) {
-    LBAD_GUARD_BEGIN
-    return lbad::packed_keys_impl(c, static_cast<const uint32_t*>(inPackedQueries), inCount, inSubfingerprintsPerQuery, inRange,
-                                  inIndexBase, static_cast<unsigned long long*>(outKeys), static_cast<hipStream_t>(inStream));
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveCorpusQueryPackedTopKKeysDevice(LBAudioDetectiveCorpusRef c, const void* inPackedQueries, UInt32 inCount,
-                                                         UInt32 inSubfingerprintsPerQuery, UInt32 inRange, UInt32 inK,
-                                                         UInt64 inIndexBase, void* outKeys, void* outLags, void* inStream) {
-    LBAD_GUARD_BEGIN
-    return lbad::packed_topk_impl(c, static_cast<const uint32_t*>(inPackedQueries), inCount, inSubfingerprintsPerQuery, inRange, inK,
-                                  inIndexBase, static_cast<unsigned long long*>(outKeys), static_cast<int32_t*>(outLags),
-                                  static_cast<hipStream_t>(inStream));
-    LBAD_GUARD_END
 }
 
 // Debug / tests: the blocks a builder makes of inCount x inPer sub-fingerprints -- from packed rows on the device (the kernels
@@ -1325,28 +841,6 @@ OSStatus LBAudioDetectiveDebugSlidingChoice(const UInt32* inEntryLengths, const 
     group.scores = inScores != 0; group.host_blocks = inHostBlocks != 0;
     lbad::sliding_choice_words(lbad::sliding_choose(stats, group, inComputeUnits), inQueryLength, outWords);
     return noErr;
-    LBAD_GUARD_END
-}
-
-OSStatus LBAudioDetectiveTopKKeysFromScoresDevice(const Float32* inScores, UInt64 inCount, UInt32 inRows, UInt32 inK,
-                                                  UInt64 inIndexBase, void* outKeys, void* inStream) {
-    LBAD_GUARD_BEGIN
-    if (!inScores || !outKeys || inRows == 0 || inK == 0 || inK > lbad::kTopKMax) return kLBAudioDetectiveArgumentInvalid;
-    if (inCount > 0x100000000ull || inIndexBase + inCount > 0x100000000ull) return kLBAudioDetectiveArgumentInvalid;
-    hipStream_t stream = static_cast<hipStream_t>(inStream);
-    unsigned long long* keys = static_cast<unsigned long long*>(outKeys);
-    constexpr uint32_t kRowsPerLaunch = 64;                // bounds the scratch (about 11 MiB)
-    const uint32_t rows = inRows < kRowsPerLaunch ? inRows : kRowsPerLaunch;
-    lbad::DeviceBuffer<void> scratch;
-    OSStatus st = scratch.reserve(lbad::topk_scratch_bytes(rows));
-    if (st != noErr) return st;
-    for (uint32_t r0 = 0; r0 < inRows && st == noErr; r0 += rows) {
-        const uint32_t g = inRows - r0 < rows ? inRows - r0 : rows;
-        st = lbad::hip_status(lbad::launch_topk_keys(inScores + (size_t)r0 * inCount, inCount, g, inK, inIndexBase, scratch,
-                                                     keys + (size_t)r0 * inK, stream), "top-K selection", __LINE__);
-    }
-    const OSStatus done = lbad::hip_status(hipStreamSynchronize(stream), "top-K selection", __LINE__);
-    return st != noErr ? st : done;
     LBAD_GUARD_END
 }
 

@@ -503,10 +503,12 @@ OSStatus pass_plan(const struct ::LBAudioDetectiveCorpus* c, const PassQuery& q,
 // The events a call takes: join_ev (the partials), the query's (align_ev or pq_ev: the staged words) and, with `topk`, topk_ev
 // (the score row and the selection's words).  wait() before the scratch is touched; then every way out goes through finish(),
 // which records them all on the stream behind whatever was launched, also after a failure -- the scratch and the staged words
-// are in use until then -- and gives the call's status, else the first record's that failed.
+// are in use until then -- and gives the call's status, else the first record's that failed.  The top-K and threshold queries
+// (api_select.cpp) name their events themselves: one guard per point of the stream at which an event is due.
 struct PassGuard {
     Event* ev[3] = {nullptr, nullptr, nullptr};
     PassGuard(struct ::LBAudioDetectiveCorpus* c, const PassQuery& q, bool topk);
+    explicit PassGuard(Event* e0, Event* e1 = nullptr, Event* e2 = nullptr) : ev{e0, e1, e2} {}
     OSStatus wait();
     OSStatus finish(hipStream_t stream, OSStatus st);
 };
@@ -525,10 +527,11 @@ hipError_t pass_chunks(uint64_t count, uint64_t chunk, Launch launch) {
 struct KeyBlock {
     unsigned long long* d_keys = nullptr;
     uint32_t* d_words = nullptr;         // nullptr: n_words == 0
-    size_t n_keys = 0;
+    size_t n_keys = 0, n_words = 0;
 };
 OSStatus key_block_reserve(struct ::LBAudioDetectiveCorpus* c, size_t n_keys, size_t n_words, KeyBlock* b);
-// the first m keys and, where there are any, m values behind them (host[m] onwards) read back; the whole block is one copy
+// the first m keys and, where there are any, m values behind them (host[m] onwards) read back; m == n_keys: the whole block,
+// every value of it, in one copy
 OSStatus key_block_read(const KeyBlock& b, size_t m, std::vector<unsigned long long>* host);
 // after a failure behind the reservation: whatever was launched has left the key buffer before its next user
 OSStatus key_block_failed(OSStatus st);
@@ -841,6 +844,14 @@ OSStatus align_keys_built(struct ::LBAudioDetectiveCorpus* c, const uint2* d_des
 // ... and for n queries given as handles, staged by the alignment itself
 OSStatus align_keys_handles(struct ::LBAudioDetectiveCorpus* c, const ::LBAudioDetectiveFingerprintRef* qs, uint32_t n, uint32_t range,
                             uint32_t k, const unsigned long long* keys, uint64_t index_base, int32_t* lags, hipStream_t stream);
+// api_corpus.cpp, the top-1 scans as the top-K and threshold queries (api_select.cpp) run them: one query given as a handle,
+// staged and scanned on `stream`, its key to key_dst (device) and, d_scores given, its per-entry scores (count floats) ...
+OSStatus run_query(struct ::LBAudioDetectiveCorpus* c, const struct ::LBAudioDetectiveFingerprint* q, uint32_t range, uint64_t index_base,
+                   float* d_scores, unsigned long long* key_dst, hipStream_t stream);
+// ... and n queries of `per` sub-fingerprints against a ragged corpus whose sliding blocks a builder wrote to d_blocks, key i to
+// keys[i] (d_scores: n == 1)
+OSStatus run_built_ragged(struct ::LBAudioDetectiveCorpus* c, const uint32_t* d_blocks, uint32_t n, uint32_t per, uint32_t range,
+                          uint64_t index_base, float* d_scores, unsigned long long* keys, hipStream_t stream);
 ::LBAudioDetectiveFingerprintRef fingerprint_from_bools(const struct ::LBAudioDetective* d, const Boolean* bools, uint64_t per);
 // the file entry points (api_files.cpp): decode, conversion and the window loop of n files in one launch chain per
 // hop value; statuses (optional) receives every file's status
@@ -974,17 +985,21 @@ struct LBAudioDetectiveCorpus {
     bool shard_stale = false;                    // a sharded query timed out: work may still be queued behind the key block
     lbad::Event shard_stale_event;               // ... recorded behind that work when the call gave up (the stream may be gone by the next call)
     uint64_t query_seq = 0;
-    // top-K queries (api_corpus.cpp): score rows (up to kQueryBatchMax x count floats), the selection's scratch, the staged
+    // top-K queries (api_select.cpp): score rows (up to kQueryBatchMax x count floats), the selection's scratch, the staged
     // query blocks of the batch scan, the scans' own key words (the top-1 state -- d_key, the polled slots -- stays
-    // untouched) and the keys of the host-returning forms.  Grown on demand; a call reuses them only after topk_ev, recorded
-    // behind the previous call's last kernel.
+    // untouched) and the keys of the host-returning forms.  Grown on demand.  topk_ev covers d_topk_scores, d_topk_scratch,
+    // d_threshold_scratch, topk_q, d_topk_scan_keys and d_topk_keys: a call touches them only after it, and records it behind
+    // its selection -- the last kernel that reads or writes any of them -- also after a failure, behind whatever was launched.
+    // The alignment that a packed call runs behind its selection is NOT under it (align_ev and pq_ev cover what it reads): the
+    // next call on another stream waits for the selection, not for the lags.  The recording passes that select (api_recording.cpp)
+    // keep their score row and selection words under it too.
     lbad::DeviceBuffer<float> d_topk_scores;
     lbad::DeviceBuffer<void> d_topk_scratch;
     lbad::StagingPair<uint32_t> topk_q;
     lbad::DeviceBuffer<unsigned long long> d_topk_scan_keys;   // kQueryBatchMax words
     lbad::DeviceBuffer<unsigned long long> d_topk_keys;
     lbad::Event topk_ev;
-    // threshold queries (api_corpus.cpp): the tile counts and offsets of the selection of k_threshold.hip.  The score rows, the
+    // threshold queries (api_select.cpp): the tile counts and offsets of the selection of k_threshold.hip.  The score rows, the
     // scans' key words, the staged query blocks, the host forms' key buffer and the event are the top-K calls': one convention
     // for one scratch.
     lbad::DeviceBuffer<void> d_threshold_scratch;
@@ -996,7 +1011,8 @@ struct LBAudioDetectiveCorpus {
     lbad::DeviceBuffer<void> d_align_out;
     lbad::Event align_ev;
     // packed queries (the ...QueryPacked...Device calls): what the builders of k_query.hip write -- the scan's blocks, then the
-    // alignment's table and words.  Grown on demand; a call reuses it only after pq_ev, recorded behind its last kernel.
+    // alignment's table and words.  Grown on demand.  pq_ev covers d_pq alone: a call touches it only after it, and records it
+    // behind the last kernel that reads d_pq (the last scan, or the alignment when lags are wanted), also after a failure.
     lbad::DeviceBuffer<uint32_t> d_pq;
     lbad::Event pq_ev;
     // corpus join (LBAudioDetectiveCorpusJoinThreshold..., k_join.hip), held by the corpus that is scanned: the chunk's row

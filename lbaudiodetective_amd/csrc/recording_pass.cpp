@@ -77,11 +77,13 @@ OSStatus key_block_reserve(LBAudioDetectiveCorpus* c, size_t n_keys, size_t n_wo
     b->d_keys = c->d_topk_keys;
     b->d_words = n_words ? reinterpret_cast<uint32_t*>(b->d_keys + n_keys) : nullptr;
     b->n_keys = n_keys;
+    b->n_words = n_words;
     return noErr;
 }
 
 OSStatus key_block_read(const KeyBlock& b, size_t m, std::vector<unsigned long long>* host) {
-    host->assign(m + (b.d_words ? (m + 1) / 2 : 0), 0ull);
+    // (the whole block holds n_words values, which need not be n_keys: counts or offsets may ride among the keys)
+    host->assign(m + ((m == b.n_keys ? b.n_words : (b.d_words ? m : 0)) + 1) / 2, 0ull);
     if (m == b.n_keys) {
         LBAD_HIP(hipMemcpy(host->data(), b.d_keys, host->size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     } else if (m) {

@@ -414,6 +414,15 @@ def test_identify_clips_end_to_end(lb, gpu, oracle):
 
 
 # ---- 7. ordering ------------------------------------------------------------------------------------------------------------------
+# The threshold of the calls below, fixed against the oracle's scores of these corpora and query sets on the CPU: for any value in
+# 0.64 .. 0.98 every row that is a copy of a corpus entry has 1 .. 8 entries at or above it (its own at 1.0, or just below where a
+# byte was perturbed; a planted duplicate; at most 3 in all), and no row has more than 8.  The largest 9th-best score of any row
+# is 0.6263.  The rows that are no copies -- random rows, the all-zero query, ragged slices across two entries -- find little or
+# nothing (the best score of a random row lies below other rows' 9th-best): no single threshold gives every row of the full
+# sets a match without cutting other rows' lists, so those rows check the empty answer.
+THRESHOLD = 0.66
+
+
 def test_packed_calls_back_to_back_on_two_streams(lb, gpu, oracle, ragged_case):
     rng = np.random.default_rng(9)
     u_corpus, entries, uq = _uniform_case(lb, gpu, rng, 5, 200, N_UNIFORM)
@@ -422,19 +431,31 @@ def test_packed_calls_back_to_back_on_two_streams(lb, gpu, oracle, ragged_case):
     rq_big = _ragged_queries(gpu, rng, packed, counts, 21, 61)
     gpu.cuda.synchronize()
     s1, s2 = gpu.cuda.Stream(), gpu.cuda.Stream()
-    for corpus, small, big, per in ((u_corpus, uq[:3].contiguous(), uq, 5), (r_corpus, rq_small, rq_big, 21)):
+    # which rows of the full sets are copies of corpus entries (perturbed in a byte at most): all of the uniform set but the
+    # all-zero query and the random rows (_uniform_case), and the ragged rows cut from inside one entry (_ragged_queries)
+    u_drawn = np.ones(uq.shape[0], bool)
+    u_drawn[4] = False
+    u_drawn[120:180] = False
+    r_drawn = np.arange(rq_big.shape[0]) % 4 < 2
+    for corpus, small, big, per, drawn in ((u_corpus, uq[:3].contiguous(), uq, 5, u_drawn), (r_corpus, rq_small, rq_big, 21, r_drawn)):
         n_small, n_big = small.shape[0], big.shape[0]
-        # a small call, then a larger one (the scratch grows) on another stream, then a small one again, nothing awaited
+        fps_small = _handles(lb, small.cpu().numpy(), 200)
+        fps_big = _handles(lb, big.cpu().numpy(), 200)
+        # a small call, then a larger one (the scratch grows) on another stream, then a small one again, nothing awaited.  Between
+        # the small and the larger top-K call the threshold calls, which share the score rows, the key words and the events with
+        # them: the handle form on the other stream, then the packed form with lags (and a larger scratch) on the first again
         with gpu.cuda.stream(s1):
             a = corpus.query_packed_topk_keys_device(small, n_small, per, 4, aligned=True, stream=s1)
+        with gpu.cuda.stream(s2):
+            t1 = corpus.query_batch_threshold_keys_device(fps_small, THRESHOLD, 8, stream=s2)
+        with gpu.cuda.stream(s1):
+            t2 = corpus.query_packed_threshold_keys_device(big, n_big, per, THRESHOLD, 8, aligned=True, stream=s1)
         with gpu.cuda.stream(s2):
             b = corpus.query_packed_topk_keys_device(big, n_big, per, 4, aligned=True, stream=s2)
             b1 = corpus.query_packed_keys_device(big, n_big, per, stream=s2)
         with gpu.cuda.stream(s1):
             c = corpus.query_packed_keys_device(small, n_small, per, stream=s1)
         # ... and a handle-taking call behind them
-        fps_small = _handles(lb, small.cpu().numpy(), 200)
-        fps_big = _handles(lb, big.cpu().numpy(), 200)
         want_small = _expect_top1(gpu, corpus, fps_small, 0)
         gpu.cuda.synchronize()
         wk, wl = _expect_topk(gpu, corpus, fps_small, 4, 0)
@@ -443,3 +464,14 @@ def test_packed_calls_back_to_back_on_two_streams(lb, gpu, oracle, ragged_case):
         assert np.array_equal(_u64(b[0]), wk) and np.array_equal(b[1].cpu().numpy(), wl)
         assert np.array_equal(_u64(b1), _expect_top1(gpu, corpus, fps_big, 0))
         assert np.array_equal(_u64(c), want_small)
+        # the threshold calls: the same calls made alone
+        w1 = corpus.query_batch_threshold_keys_device(fps_small, THRESHOLD, 8)
+        gpu.cuda.synchronize()
+        w2 = corpus.query_packed_threshold_keys_device(big, n_big, per, THRESHOLD, 8, aligned=True)
+        gpu.cuda.synchronize()
+        for got, want, rows in ((t1, w1, drawn[:n_small]), (t2, w2, drawn)):
+            counts = _u64(want[1])
+            # every row that was drawn from the corpus finds its own entry, and no list is cut
+            assert counts.shape == rows.shape and (counts[rows] >= 1).all() and (counts <= 8).all(), counts
+            for g, w in zip(got, want):
+                assert g.shape == w.shape and g.dtype == w.dtype and np.array_equal(g.cpu().numpy(), w.cpu().numpy())

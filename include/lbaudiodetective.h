@@ -1161,7 +1161,9 @@ OSStatus LBAudioDetectiveDebugSlidingChoice(const UInt32* inEntryLengths, const 
 OSStatus LBAudioDetectiveDebugLiveBytes(UInt64* outDevice, UInt64* outPinned);
 /* Debug / TESTS ONLY: a process-wide ceiling on the workgroups of every launch whose workgroups walk work items beyond their
  * grid with a stride and carry state in LDS from one item to the next -- the occurrences, recording and timeline passes, both
- * joins and their row scan, the alignment's three launches and the threshold list's count and scatter.  Each of them launches
+ * joins and their row scan, the alignment's three launches and the threshold list's count and scatter -- and of the plain
+ * grid-stride launches of the stream bank, the resampler bank, the duplicate groups (init, hook, flatten), the gather's two
+ * copy launches and the top-K selection's histogram and gather passes (grid.x; the rows stay in grid.y).  Each of them launches
  * min(its work, its built-in ceiling, inWorkgroups) workgroups, never fewer than 1; 0 (the default) restores the built-in
  * ceilings alone.  Results NEVER depend on the value: it only decides how many work items one workgroup takes, which is how a
  * test of seconds reaches the trips that otherwise need a corpus of a million entries.  The second call reports the ceiling

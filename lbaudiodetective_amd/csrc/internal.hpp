@@ -53,6 +53,10 @@ struct PerDevice {
 // The grid of a launch whose workgroups carry state in LDS from one work item to the next (w += gridDim.x): the work, at most
 // the launcher's own ceiling, at most the tests' ceiling where one is set (LBAudioDetectiveDebugSetGridCeiling; 0: none) --
 // never 0 for work > 0.  Results do not depend on the grid; a launch that really strides (a grid below its work) is counted.
+// The plain grid-stride launches (x += gridDim.x * threads, nothing carried) take their grids from here as well, so that the
+// tests' ceiling reaches their second trips: the stream and resampler banks, the duplicate groups' init, hook and flatten
+// (k_groups.hip), the gather's copy launches (k_gather.hip) and the top-K selection's histogram and gather passes (k_topk.hip,
+// grid.x only).  The corpus scans of k_compare.hip keep their own caps: the 10 M-entry tests cross them by shape.
 inline std::atomic<uint32_t> g_grid_ceiling{0};
 inline std::atomic<uint64_t> g_strided_launches{0};
 inline uint32_t strided_grid(uint64_t work, uint32_t built_in_ceiling) {

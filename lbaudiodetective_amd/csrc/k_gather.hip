@@ -222,10 +222,7 @@ __global__ __launch_bounds__(kGaThreads) void gather_copy_records_kernel(const u
     }
 }
 
-uint32_t ga_copy_grid(uint64_t items) {
-    const uint64_t blocks = (items + kGaThreads - 1) / kGaThreads;
-    return (uint32_t)(blocks < kGaCopyGridMax ? blocks : kGaCopyGridMax);
-}
+uint32_t ga_copy_grid(uint64_t items) { return strided_grid((items + kGaThreads - 1) / kGaThreads, kGaCopyGridMax); }
 
 }  // namespace
 

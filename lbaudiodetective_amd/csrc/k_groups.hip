@@ -223,10 +223,7 @@ __global__ __launch_bounds__(kGrThreads) void groups_extra_scatter_kernel(const 
     }
 }
 
-uint32_t gr_grid(uint64_t items) {
-    const uint64_t blocks = (items + kGrThreads - 1) / kGrThreads;
-    return (uint32_t)(blocks < kGrGridMax ? blocks : kGrGridMax);
-}
+uint32_t gr_grid(uint64_t items) { return strided_grid((items + kGrThreads - 1) / kGrThreads, kGrGridMax); }
 
 }  // namespace
 

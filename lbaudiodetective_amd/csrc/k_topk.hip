@@ -216,8 +216,7 @@ hipError_t launch_topk_keys(const float* d_scores, uint64_t n, uint32_t rows, ui
     uint32_t* hist = static_cast<uint32_t*>(d_scratch);
     RowState* st = reinterpret_cast<RowState*>(hist + (size_t)rows * kPasses * kBins);
     unsigned long long* cand = reinterpret_cast<unsigned long long*>(st + rows);
-    const uint64_t blocks = (n + kHistThreads - 1) / kHistThreads;
-    const dim3 grid((uint32_t)(blocks < 256 ? blocks : 256), rows);
+    const dim3 grid(strided_grid((n + kHistThreads - 1) / kHistThreads, 256), rows);   // (one count of a strided launch per call)
     hipLaunchKernelGGL(topk_init_kernel, dim3(rows), dim3(kScanThreads), 0, stream, hist, st, k);
 #define LBAD_TOPK_PASS(D)                                                                                                    \
     hipLaunchKernelGGL(topk_hist_kernel<D>, grid, dim3(kHistThreads), 0, stream, d_scores, n, index_base, hist, st);        \

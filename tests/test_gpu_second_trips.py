@@ -15,8 +15,17 @@ Every comparison is exact -- keys as 64-bit integers, lags, counts, CSR offsets,
 against the numpy references the families' own tests use (align_ref.profile, timeline_ref, the join files' oracle matrices),
 through those files' corpora, queries, _expected, _check and _run helpers (imported, not copied; their module caches are
 shared).  The thresholds are values of the reference's own cells: nothing needs a tolerance.  The fixture below is the only
-place the ceiling is set, and it puts 0 back on every path."""
+place the ceiling is set, and it puts 0 back on every path.
+
+The plain grid-stride kernels -- nothing carried, x += gridDim.x * threads -- of the duplicate groups (init, hook, flatten), the
+gather's two copy launches and the top-K selection's histogram and gather passes take their grids from the same ceiling and
+run under a. as well: the groups' own test bodies, the gather's _check and the top-K file's numpy sort, under a ceiling.  Their
+single-workgroup scans (groups_extra_tiles_kernel, gather_tiles_kernel, remove_offsets_kernel: 256 tiles per step, a carry from
+step to step) are b.: crossed by 256 * 1024 + 1024 + 7 entries, keys or vertices -- 258 tiles, the second step holding two,
+the last one partial."""
 import contextlib
+import os
+import re
 
 import numpy as np
 import pytest
@@ -24,11 +33,15 @@ import pytest
 import align_ref
 import timeline_ref
 import test_gpu_align as AL
+import test_gpu_gather as GA
+import test_gpu_groups as GR
 import test_gpu_join as JN
 import test_gpu_join_ragged as JR
 import test_gpu_occurrences as OC
 import test_gpu_recording as RC
+import test_gpu_remove as RM
 import test_gpu_timeline as TL
+import test_gpu_topk as TK
 
 pytestmark = pytest.mark.gpu
 
@@ -338,8 +351,168 @@ def test_match_profile_under_a_ceiling(lb, gpu, oracle, ceiling):
             assert first == 0 and np.array_equal(AL._bits(got), AL._bits(want)), (nq, e)
 
 
+# ---- a. duplicate groups: init, hook and flatten stride by 256 vertices or key slots per workgroup -------------------------------
+# The bodies are test_gpu_groups.py's own: every graph in them has more than 4 x 256 vertices, so init and flatten stride under
+# both ceilings (4 097 vertices under ceiling 1: 17 trips, the last with one live lane -- flatten's ballot needs every lane of a
+# wave to make all of them), and every list of edges has more slots than that where the hook pass is the point: the chain's
+# 2 999, the path's 4 096, K(3, 2000)'s 12 000 in both directions, the random graph's 2 000 and more.
+_GROUP_BODIES = {
+    "chain of 3000": lambda lb, gpu: GR.test_chain(lb, gpu),
+    "path over a permutation of 4097": lambda lb, gpu: GR.test_path_over_a_permutation(lb, gpu),
+    "stars and K(3, 2000)": lambda lb, gpu: GR.test_stars(lb, gpu),
+    "random graph at base 5000": lambda lb, gpu: GR.test_random_graph(lb, gpu),
+    "pitched rows and row keys": lambda lb, gpu: GR.test_pitched_rows_and_row_keys(lb, gpu),
+    "incremental, rows ascending": lambda lb, gpu: GR.test_incremental_calls_equal_one_call(lb, gpu, "rows ascending"),
+    "incremental, rows descending": lambda lb, gpu: GR.test_incremental_calls_equal_one_call(lb, gpu, "rows descending"),
+    "list cut by n_slots": lambda lb, gpu: GR.test_cut_list_is_used_as_far_as_it_goes(lb, gpu),
+}
+
+
+@pytest.mark.parametrize("body", list(_GROUP_BODIES))
+def test_groups_under_a_ceiling(lb, gpu, ceiling, body):
+    """labels against _union_find, the group count against the number of roots, both poison-filled: see the bodies"""
+    with _strides(lb):
+        _GROUP_BODIES[body](lb, gpu)
+
+
+def test_groups_second_trip_with_one_live_lane(lb, gpu, ceiling1):
+    """257 vertices under ceiling 1: two trips, the second with one live lane in wave 0 and none in the other three"""
+    n = 257
+    with _strides(lb):
+        want = GR._check(lb, gpu, GR.Rows(n, [[] for _ in range(n)]), "257, no edges")
+    assert np.array_equal(want, np.arange(n))
+    with _strides(lb):
+        want = GR._check(lb, gpu, GR.Rows(n, GR._rows_of(n, [(256, 0), (255, 256)])), "257, the last vertex hooked")
+    assert want[256] == 0 and want[255] == 0 and (want == np.arange(n)).sum() == n - 2
+
+
+# ---- a. gather: the two copy launches stride by 256 output sub-fingerprints per workgroup ------------------------------------------
+def _gather_lists(n, rng):
+    """name -> GLOBAL indices at base 0 (-1: a zero key; n and above: a key of another index range); 900 keys each"""
+    mixed = rng.integers(0, n, 900)
+    mixed[::7] = mixed[3]                                         # duplicates (copies of one entry all through the list)
+    mixed[5::11] = -1
+    mixed[2::13] = n + np.arange(len(mixed[2::13])) % 2
+    mixed[[100, 600]] = 0xFFFFFFFF                                # (a zero low word under a score word)
+    return {"900 of a shuffle": rng.permutation(n)[:900].astype(np.int64), "duplicates, zero and foreign keys": mixed.astype(np.int64)}
+
+
+def _gather_cases(lb, gpu, c, rows, what, seed, min_len):
+    rng = np.random.default_rng(seed)
+    n = len(rows)
+    for base in (0, GA.BASE):
+        for name, rel in _gather_lists(n, rng).items():
+            g = np.where(rel >= 0, np.minimum(rel + base, 0xFFFFFFFF), -1)
+            exp_off, _ = GA._expected(rows, g, base)
+            assert int(exp_off[-1]) > 4 * 256                     # more output than one trip of four workgroups
+            with _strides(lb):
+                GA._check(gpu, c, rows, g, base, rng, (what, base, name))
+            # a capacity that cuts the output inside a row, behind the first trip of every workgroup
+            k = next(i for i in range(2 * len(g) // 3, len(g)) if exp_off[i + 1] - exp_off[i] >= min_len)
+            cap = int(exp_off[k]) + 1
+            assert cap > 4 * 256 and exp_off[k] < cap < exp_off[k + 1]
+            with _strides(lb):
+                GA._check(gpu, c, rows, g, base, rng, (what, base, name, "cut inside row", k), capacity=cap)
+
+
+@pytest.mark.parametrize("shape", [(200, 5), (33, 3)])
+def test_gather_uniform_under_a_ceiling(lb, gpu, oracle, ceiling, shape):
+    """gather_copy_planes_kernel: offsets, bytes and the poison behind min(total, capacity) against the rows appended"""
+    length, n_sub = shape
+    n = 2 * GA.T + 3
+    bools = GA._uniform_bools(length, n_sub, n)
+    c = GA._uniform(lb, gpu, oracle, bools, n + 5)
+    try:
+        _gather_cases(lb, gpu, c, list(GA._packed(oracle, bools)), shape, length + n_sub, n_sub)
+    finally:
+        c.dispose()
+
+
+@pytest.mark.parametrize("length", [200, 199])
+def test_gather_ragged_under_a_ceiling(lb, gpu, oracle, ceiling, length):
+    """gather_copy_records_kernel: the binary search of every trip's position in the offsets"""
+    flat, counts = GA._ragged_made(length)
+    c = GA._ragged(lb, gpu, oracle, flat, counts, len(counts) + 3, int(counts.sum()) + 11)
+    try:
+        _gather_cases(lb, gpu, c, GA._ragged_rows(oracle, flat, counts), ("ragged", length), length, 3)
+    finally:
+        c.dispose()
+
+
+# ---- a. top-K selection: the histogram and gather passes stride by 1024 scores per workgroup ---------------------------------------
+N_SCORES = 5000                                               # 5 trips of 1024 under ceiling 1, the last one partial
+TOPK_POISON = -0x0123456789ABCDEF
+
+
+def _select_poisoned(lb, gpu, scores, k, index_base=0):
+    """test_gpu_topk.py's _select with the key block (and three words behind it) poison-filled before the call"""
+    s = gpu.from_numpy(np.ascontiguousarray(scores, np.float32)).cuda()
+    rows, n = (1, s.numel()) if s.dim() == 1 else (s.shape[0], s.shape[1])
+    out = gpu.full((rows * k + 3,), TOPK_POISON, dtype=gpu.int64, device="cuda")
+    st = lb.lib().LBAudioDetectiveTopKKeysFromScoresDevice(s.data_ptr(), n, rows, k, index_base, out.data_ptr(),
+                                                           gpu.cuda.current_stream().cuda_stream)
+    assert st == 0, st
+    gpu.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert (got[rows * k:] == TOPK_POISON).all(), "words behind the keys were written"
+    return got[:rows * k].reshape(rows, k)
+
+
+def _score_patterns():
+    """name -> a row of N_SCORES scores; the patterns of test_selection_on_crafted_score_arrays, what decides them placed at
+    indices of the later trips"""
+    rng = np.random.default_rng(99)
+    n = N_SCORES
+    cases = {"all equal": np.full(n, 0.5, np.float32)}
+    one = np.full(n, 0.5, np.float32)
+    one[4321] = 0.5000001
+    cases["all equal but one"] = one
+    tie = (0.45 + 0.01 * rng.random(n)).astype(np.float32)
+    at = rng.permutation(n)
+    tie[at[:1100]] = np.float32(0.7)                              # the 1024th lies among 1100 equal scores
+    tie[at[1100:1111]] = np.float32(0.9)                          # the 10th among 11
+    tie[at[1111:1114]] = np.float32(0.95)                         # the 1st among 3
+    cases["ties at the k-th score"] = tie
+    ulp = np.full(n, 0.5, np.float32)
+    some = rng.choice(n, 1500, replace=False)
+    ulp[some] = np.nextafter(np.float32(0.5), np.float32(1), dtype=np.float32) + np.arange(1500) % 7 * np.float32(2 ** -24)
+    cases["one ulp apart"] = ulp
+    odd = np.zeros(n, np.float32)
+    odd[::3] = np.float32(1e-42)                                  # denormals
+    odd[1::7] = np.nan
+    odd[2::11] = -0.5
+    odd[1025] = -0.0
+    odd[2050] = np.float32(1.4e-45)
+    odd[4999] = np.inf
+    odd[3100] = 3.0
+    odd[4100] = -np.inf
+    cases["NaN, inf, -0.0, denormals"] = odd
+    cases["normal"] = np.clip(rng.normal(0.5, 0.03, n), 0, 1).astype(np.float32)
+    return cases
+
+
+def test_topk_selection_under_a_ceiling(lb, gpu, ceiling):
+    """rows of 5000 scores against the numpy sort by (score descending, index ascending) of test_gpu_topk.py, keys compared as
+    64-bit integers: every pattern alone, then two rows in one call (grid.y) with an index base"""
+    cases = _score_patterns()
+    assert -(-N_SCORES // 1024) > 4
+    for name, s in cases.items():
+        for k in (1, 10, 1024):
+            with _strides(lb):
+                got = _select_poisoned(lb, gpu, s, k)
+            assert np.array_equal(got[0], TK._host_keys(s, k)), (name, k)
+    names = list(cases)
+    for a, b in zip(names, names[1:] + names[:1]):
+        rows = np.stack([cases[a], cases[b]])
+        for k in (1, 10, 1024):
+            with _strides(lb):
+                got = _select_poisoned(lb, gpu, rows, k, index_base=1000)
+            for r in range(2):
+                assert np.array_equal(got[r], TK._host_keys(rows[r], k, 1000)), (a, b, r, k)
+
+
 # ---- b. step loops, the ceiling as it comes ---------------------------------------------------------------------------------------
-N_REC = 129_700                                               # ceil(129 700 / 126) = 1030 tiles
+N_REC = 129_700                                              # ceil(129 700 / 126) = 1030 tiles
 EARLY, LATE = 500, 1026 * 126 + 3                             # below and above offset 1024 x 126
 
 
@@ -418,6 +591,205 @@ def test_many_short_entries_cross_the_row_grid_and_the_offsets_steps(lb, gpu, or
             with _strides(lb):
                 got = OC._run(gpu, corpus, fp, t, peaks, capacity)
             OC._check(got, want_keys, want_lags, capacity)
+
+
+# ---- b. the single-workgroup scans of remove, gather and the groups' extra keys: 256 tiles per step -----------------------------
+def _constant(file, name):
+    src = open(os.path.join(RM.ROOT, "lbaudiodetective_amd", "csrc", file)).read()
+    return int(re.search(r"constexpr\s+uint32_t\s+%s\s*=\s*(\d+)\s*;" % name, src).group(1))
+
+
+T = RM.T
+STEP = _constant("k_remove.hip", "kRmThreads")                # tiles per step of each of the three scans
+N_BIG = STEP * T + T + 7                                      # 258 tiles: step 2 holds two, the last one partial
+SEED_BIG = 0x32545250
+_BIG = {}
+
+
+def test_the_three_scans_share_their_tile_and_step():
+    assert T == GA.T == _constant("k_groups.hip", "kGrTile") == 1024
+    assert STEP == _constant("k_gather.hip", "kGaThreads") == _constant("k_groups.hip", "kGrThreads") == 256
+    assert N_BIG == 263_175 and -(-N_BIG // T) == STEP + 2 and N_BIG % T == 7
+
+
+def _big(oracle):
+    """N_BIG + 15 entries of one sub-fingerprint of 200 Booleans and their packed bytes, made once and read-only: the uniform
+    corpus is the first N_BIG of them, the ragged ones cut their records out of the same rows"""
+    if not _BIG:
+        bools = oracle.synth_corpus(SEED_BIG, 0, N_BIG + 15, 1, 200)
+        packed = RM._packed(oracle, bools)
+        for a in (bools, packed):
+            a.setflags(write=False)
+        _BIG.update(bools=bools, packed=packed)
+    return _BIG
+
+
+def _big_uniform(lb, gpu, oracle):
+    c = lb.Corpus(200, 1, N_BIG)
+    c.append_packed_device(gpu.from_numpy(_big(oracle)["packed"][:N_BIG].copy()).cuda())
+    return c
+
+
+def _in_order_keys(n):
+    return np.uint64(0xFFFFFFFF) - np.arange(n, dtype=np.uint64)
+
+
+def _contents(gpu, c, want_bytes, want_counts, what):
+    """every entry of c, gathered in order into poisoned buffers, against the expected bytes [records, 32] and entry lengths"""
+    records = len(want_bytes)
+    off, packed = GA._gather_dev(gpu, c, _in_order_keys(len(c)), 0, records)
+    want_off = np.concatenate([np.zeros(1, np.uint64), np.cumsum(want_counts, dtype=np.uint64)])
+    assert np.array_equal(off, want_off), (what, "entry offsets", np.flatnonzero(off != want_off)[:4])
+    bad = np.flatnonzero((packed[:records] != want_bytes).any(axis=1))
+    assert len(bad) == 0, (what, "bytes of records", len(bad), bad[:4])
+    assert (packed[records:] == GA.POISON8).all(), what
+
+
+def _big_removal_sets(n):
+    """name -> sorted indices out of n entries (n in tile 257)"""
+    rng = np.random.default_rng(77)
+    late = np.arange(STEP * T, n)
+    return {"i": np.sort(rng.choice(late, len(late) // 2, replace=False)),                  # only in tiles >= 256
+            "ii": np.union1d([3 * T + 17], rng.choice(n, n // 100, replace=False)),          # one in tile 3 and a random 1 %
+            "iii": np.arange(0, n, 2)}                                                       # every other
+
+
+@pytest.mark.parametrize("which", ["i", "ii", "iii"])
+def test_uniform_removal_crosses_the_offsets_step(lb, gpu, oracle, which):
+    """remove_offsets_kernel's second step over 258 tiles: the kept count carried into tiles 256 and 257, and the lowest removed
+    index -- (i) found only by step 2 while step 1 carries "none", (ii) found by step 1 and not to be overwritten, (iii) the
+    largest carry.  The count, the whole old -> new map (poison-filled), every byte of the corpus afterwards (a gather of all
+    kept entries: more than 256 tiles of keys in (i) and (ii), so gather_tiles_kernel's second step as well), and two queries
+    against oracle.corpus_best on the kept Booleans."""
+    assert lb.debug_grid_ceiling()[0] == 0
+    big = _big(oracle)
+    bools, packed = big["bools"][:N_BIG], big["packed"][:N_BIG]
+    indices = _big_removal_sets(N_BIG)[which]
+    keep, new, removed = RM._expected(N_BIG, indices)
+    assert removed == len(indices) and 3 * T + 17 in _big_removal_sets(N_BIG)["ii"]
+    assert (indices.min() >= STEP * T) == (which == "i") and indices.max() >= STEP * T
+    c = _big_uniform(lb, gpu, oracle)
+    try:
+        st, got_removed, got_map = RM._remove_host(lb, c, indices)
+        assert st == 0
+        assert got_removed == removed and len(c) == N_BIG - removed, (got_removed, removed, len(c))
+        assert np.array_equal(got_map, new), np.flatnonzero(got_map != new)[:8]
+        _contents(gpu, c, packed[keep].reshape(-1, 32), np.ones(N_BIG - removed, np.uint64), which)
+        kept = np.ascontiguousarray(bools[keep])
+        last_tile = np.arange((STEP + 1) * T, N_BIG)
+        for name, e in (("kept, last tile", last_tile[keep[last_tile]][-1]), ("removed", indices[-1])):
+            want = oracle.corpus_best(bools[e], kept, 200, nthreads=16)
+            got = c.query(lb.Fingerprint.from_bools(bools[e]))
+            assert got[0] == want[0] and RM._bits(got[1]) == RM._bits(want[1]), (which, name, got, want)
+            assert (name == "removed") or (want == (int(new[e]), 1.0))
+    finally:
+        c.dispose()
+
+
+def test_ragged_removal_crosses_the_offsets_step(lb, gpu, oracle):
+    """N_BIG + 3 entries of one record each but three of five, in tiles 0, 255 and 257; every other entry from tile 256 on goes,
+    the long one of tile 257 stays: its records' new place is the sum of step 1's carry, what tile 256 keeps and what goes in
+    front of it inside its own tile"""
+    assert lb.debug_grid_ceiling()[0] == 0
+    n = N_BIG + 3
+    long_ones = [5, (STEP - 1) * T + 9, (STEP + 1) * T + 3]
+    counts = np.ones(n, np.uint32)
+    counts[long_ones] = 5
+    total = int(counts.sum())
+    assert total == n + 12
+    big = _big(oracle)
+    flat, packed = big["bools"][:total, 0, :], big["packed"][:total, 0, :]
+    indices = np.arange(STEP * T, n, 2)
+    assert long_ones[2] not in indices and -(-n // T) == STEP + 2 and indices[-1] > long_ones[2]
+    keep, new, removed = RM._expected(n, indices)
+    c = RM._ragged(lb, gpu, oracle, flat, counts, n, total)
+    try:
+        st, got_removed, got_map = RM._remove_host(lb, c, indices)
+        assert st == 0
+        assert got_removed == removed and len(c) == n - removed, (got_removed, removed, len(c))
+        assert c.subfingerprint_total == int(counts[keep].sum())
+        assert np.array_equal(got_map, new), np.flatnonzero(got_map != new)[:8]
+        _contents(gpu, c, packed[np.repeat(keep, counts)], counts[keep], "ragged")
+    finally:
+        c.dispose()
+
+
+def test_gather_of_more_keys_than_one_step_of_tiles(lb, gpu, oracle):
+    """gather_tiles_kernel's second step.  N_BIG keys of the uniform corpus of N_BIG entries -- a permutation, every 50th key zero,
+    every 97th of another index range: the offsets are sums of 0 or 1; then N_BIG keys drawn with repetition from a ragged corpus
+    of 3000 entries of 1 .. 40 records: the carry out of step 1 is a sum of real lengths.  Offsets (N_BIG + 1 words), total and
+    every gathered byte against numpy."""
+    assert lb.debug_grid_ceiling()[0] == 0
+    big = _big(oracle)
+    rng = np.random.default_rng(31)
+    # uniform
+    g = rng.permutation(N_BIG).astype(np.int64)
+    g[::50] = -1
+    g[::97] = N_BIG + np.arange(len(g[::97]))
+    valid = (g >= 0) & (g < N_BIG)
+    assert valid[STEP * T:].any() and not valid[STEP * T:].all()
+    want_off = np.concatenate([[0], np.cumsum(valid)]).astype(np.uint64)
+    want = big["packed"][:N_BIG, 0, :][g[valid]]
+    c = _big_uniform(lb, gpu, oracle)
+    try:
+        off, packed = GA._gather_dev(gpu, c, GA._keys(g, rng), 0, len(want))
+        assert np.array_equal(off, want_off), ("uniform", np.flatnonzero(off != want_off)[:4], off[-1], len(want))
+        assert np.array_equal(packed[:len(want)], want) and (packed[len(want):] == GA.POISON8).all()
+    finally:
+        c.dispose()
+    # ragged: most entries of 1 .. 3 records, every 20th of 1 .. 40
+    n_e = 3000
+    counts = rng.integers(1, 4, n_e).astype(np.uint32)
+    counts[::20] = rng.integers(1, 41, len(counts[::20]))
+    counts[7], counts[8] = 40, 1
+    first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    flat, rows = big["bools"][:first[-1], 0, :], big["packed"][:first[-1], 0, :]
+    g = rng.integers(0, n_e, N_BIG).astype(np.int64)
+    g[3::50] = -1
+    g[5::97] = n_e + 4
+    valid = (g >= 0) & (g < n_e)
+    lens = np.where(valid, counts[np.where(valid, g, 0)], 0).astype(np.int64)
+    want_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    total = int(want_off[-1])
+    assert lens[STEP * T:].sum() > T and total < 1_500_000        # (at most 48 MB of output)
+    record = np.repeat(first[np.where(valid, g, 0)], lens) + (np.arange(total) - np.repeat(want_off[:-1], lens))
+    c = GA._ragged(lb, gpu, oracle, flat, counts, n_e, int(first[-1]))
+    try:
+        off, packed = GA._gather_dev(gpu, c, GA._keys(g, rng), 0, total)
+        assert np.array_equal(off.astype(np.int64), want_off), ("ragged", np.flatnonzero(off.astype(np.int64) != want_off)[:4], off[-1], total)
+        bad = np.flatnonzero((packed[:total] != rows[record]).any(axis=1))
+        assert len(bad) == 0, ("ragged, bytes of records", len(bad), bad[:4])
+        assert (packed[total:] == GA.POISON8).all()
+    finally:
+        c.dispose()
+
+
+def test_extra_keys_of_more_tiles_than_one_step(lb, gpu):
+    """groups_extra_tiles_kernel's second step, and the largest shape of init, hook and flatten.  About 4 000 edges over N_BIG
+    vertices, every one inside tile 0, tile 255, tile 256 or the partial tile 257, or between two of them: the extra vertices lie
+    there and nowhere in tiles 1 .. 254.  Labels against _union_find, then the extra keys of the DEVICE's labels against numpy
+    -- every i with labels[i] != i, ascending, and the count -- with room for all of them and with a capacity that ends inside
+    tile 256."""
+    assert lb.debug_grid_ceiling()[0] == 0
+    rng = np.random.default_rng(53)
+    n = N_BIG
+    spans = [(0, T), ((STEP - 1) * T, STEP * T), (STEP * T, (STEP + 1) * T), ((STEP + 1) * T, n)]
+    edges = []
+    for lo, hi in spans:
+        edges += [(int(a), int(b)) for a, b in rng.integers(lo, hi, (1200 if hi - lo == T else 6, 2))]
+    for (lo_a, hi_a), (lo_b, hi_b) in ((spans[0], spans[3]), (spans[1], spans[2]), (spans[3], spans[1])):
+        edges += [(int(rng.integers(lo_a, hi_a)), int(rng.integers(lo_b, hi_b))) for _ in range(100)]
+    g = GR.Rows(n, GR._rows_of(n, edges))
+    want = GR._union_find(n, g.edges())
+    labels, count = GR._labels_call(lb, gpu, g)
+    got = labels.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    assert np.array_equal(got, want), (np.flatnonzero(got != want)[:8], got[got != want][:8], want[got != want][:8])
+    assert count == int((want == np.arange(n)).sum())
+    extra = np.flatnonzero(got != np.arange(n))
+    per_span = [int(((extra >= lo) & (extra < hi)).sum()) for lo, hi in spans]
+    assert min(per_span) >= 3 and sum(per_span) == len(extra) and per_span[2] >= 10, per_span
+    assert GR._check_extra(lb, gpu, got, len(extra) + 9) == len(extra)
+    assert GR._check_extra(lb, gpu, got, per_span[0] + per_span[1] + per_span[2] // 2) == len(extra)
 
 
 # ---- the ceiling is left at 0 ------------------------------------------------------------------------------------------------------

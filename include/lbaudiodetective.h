@@ -944,7 +944,7 @@ OSStatus LBAudioDetectiveCorpusQueryRecordingTimeline(LBAudioDetectiveCorpusRef 
  * offsets and length histogram) are up to date; everything issued later finds the new corpus.  One read-back per call: the
  * tile offsets, and the index map when the host form returns it or the corpus is ragged.  Like appends, a removal must not run
  * concurrently with any other call on the same corpus.  The sharded key block is left alone; a sharded corpus has no removal
- * (the index bases of all later shards would shift).
+ * by index (the index bases of all later shards would shift) -- with entry ids each rank takes down by id on its own (below).
  * inCount == 0, or a list that names nothing valid: noErr, 0 removed, the identity map, nothing is moved.  Removing every entry
  * leaves a working empty corpus; removing only the last entries moves nothing (entries below the lowest removed index are
  * neither read nor written).  A NULL handle, a NULL outRemoved, a NULL list with inCount != 0 and inIndexBase > 2^32 are
@@ -1008,6 +1008,61 @@ OSStatus LBAudioDetectiveCorpusGatherKeysDevice(LBAudioDetectiveCorpusRef inCorp
 OSStatus LBAudioDetectiveCorpusGatherIndices(LBAudioDetectiveCorpusRef inCorpus, const UInt64* inIndices, UInt64 inCount,
                                              void* outPacked /* host */, UInt64 inCapacity, UInt64* outOffsets /* host */);
 LBAudioDetectiveFingerprintRef LBAudioDetectiveCorpusCopyFingerprint(LBAudioDetectiveCorpusRef inCorpus, UInt64 inIndex);
+/* Entry ids: the caller's own 64-bit id of every entry, kept on the device with the entry.  Every result names an entry by its
+ * index, and a removal gives every later entry a new index; an id stays with its entry through removals, is stored by
+ * LBAudioDetectiveCorpusSave, comes back for any match (IdsFromKeys) and names the entries of a take-down or a hand-back
+ * (KeysFromIds, whose output RemoveKeysDevice, GatherKeysDevice and AlignKeysDevice take as it is).  Both kinds of corpus.
+ * Model.  A corpus either has ids or it has none; it starts without.  The first successful SetEntryIds... call with a
+ * non-empty range turns ids on: `capacity` UInt64 on the device, all zero, a block that never moves.  Id 0 means "no id".  The
+ * words at and above the count are always zero, so appended entries have id 0 until the caller sets them, and no append knows of
+ * ids.  Duplicate ids are legal; wherever an id has to name ONE entry, the LOWEST index wins.  Ids are global by nature:
+ * inIndexBase applies to keys only.  A corpus that never sets an id gets no new memory, launches nothing new and writes the same
+ * file bytes as before.
+ * SetEntryIdsDevice / SetEntryIds: entries [inFirst, inFirst + inCount) get the inCount ids at inIds (device, 8-byte aligned / host).
+ * inFirst + inCount > count is kLBAudioDetectiveArgumentInvalid and nothing changes; inCount == 0 is noErr and does NOT turn ids
+ * on.  The device form is asynchronous on inStream.  The host form copies the ids into pinned staging of the corpus (8 x inCount
+ * bytes, grown on demand) and returns when the copy from there is enqueued on the null stream: inIds may be reused at once.
+ * GetEntryIds: a synchronous read-back of the words [inFirst, inFirst + inCount) to host memory; the range may reach up to the
+ * CAPACITY (the words from the count on read as zero, which is the invariant above), beyond it kLBAudioDetectiveArgumentInvalid.
+ * A corpus without ids gives zeros.  HasEntryIds: 1 for a corpus with ids, else 0 (also for NULL); needs no device.
+ * IdsFromKeysDevice: inCount 64-bit keys on the device, read exactly as RemoveKeysDevice and GatherKeysDevice read them (the low
+ * word is 0xFFFFFFFF - (inIndexBase + index), the score word is ignored) -> outIds[i], the id of the entry key i names; 0 for a
+ * zero key, for an index outside [inIndexBase, inIndexBase + count), or for a corpus without ids.  All inCount words are
+ * written, nothing behind them.  It serves the key block of every call that writes this key format: top-K, threshold, the packed
+ * forms, both joins, occurrences, the recording forms, the timeline, the groups' extra keys.  One launch (a corpus without ids:
+ * one memset and no allocation).
+ * KeysFromIdsDevice: inCount ids on the device -> outKeys[i] = bits(1.0f) << 32 | 0xFFFFFFFF - (inIndexBase + index) for the
+ * LOWEST index whose id equals inIds[i] -- LBAudioDetectiveGroupExtraKeysFromLabelsDevice's convention, a key is never zero by
+ * accident -- and the zero key for id 0, an id no entry has, or a corpus without ids.  List order, duplicates allowed.  The
+ * lookup goes through an index on the device: an open-addressing table of slots = the power of two >= 2 x count (at least 1024),
+ * 12 bytes a slot, built whole (two launches) on the call's stream by the first KeysFromIds after anything made it stale -- ids
+ * set, a removal, a load; an append alone does not -- and kept until it is stale again or the corpus is disposed.
+ * Removal.  Both removal calls move the ids of a corpus that has them with the SAME device map as the entries, through a block
+ * of its own of 8 x (count - lowest removed index) bytes (two launches; the result never depends on
+ * LBAudioDetectiveCorpusSetRemoveScratchLimit), zero the words from the new count to the old one, and make the index stale.
+ * Save / Load.  A corpus with ids writes a trailer behind the payload of either file kind: "LBADIDS1", UInt64 count, count x
+ * UInt64.  Load of such a file turns ids on; the trailer is untrusted: a count other than the payload's, or fewer bytes than
+ * announced, make Load return NULL.  Bytes behind a payload that do not start with the magic are ignored, as before.
+ * Refusals, in this order.  Decided before a handle is read, each kLBAudioDetectiveArgumentInvalid: a NULL corpus; a NULL pointer
+ * with inCount != 0; a device pointer not aligned to 8 bytes; inIndexBase > 2^32; inCount > 2^31 (the list calls) or inFirst or
+ * inCount > 2^32 (the range calls).  Then a missing device is kLBAudioDetectiveDeviceUnavailable.  Then what needs the corpus,
+ * kLBAudioDetectiveArgumentInvalid: inIndexBase + count > 2^32, the range rules of Set and Get.  Then inCount == 0 is noErr.  A
+ * refused call reserves nothing, launches nothing and touches no event.
+ * Asynchrony.  One event of the corpus covers the id block, the index, the removal's block and the staging: every id call waits
+ * for the previous id call's device work before it touches any of them and records the event behind its last launch, also
+ * after a failure.  IdsFromKeysDevice and KeysFromIdsDevice never await inStream and read nothing back; they wait ON THE DEVICE
+ * for the latest append, as the gather does.  A removal and LBAudioDetectiveCorpusDispose await the event.  Like every other
+ * call, none of these may run concurrently with a removal of the same corpus.  LBAudioDetectiveCorpusGather...'s packed output
+ * carries no ids: IdsFromKeysDevice with the same key list gives them. */
+OSStatus LBAudioDetectiveCorpusSetEntryIdsDevice(LBAudioDetectiveCorpusRef inCorpus, UInt64 inFirst, UInt64 inCount,
+                                                 const void* inIds /* device, 8-byte aligned */, void* inStream);
+OSStatus LBAudioDetectiveCorpusSetEntryIds(LBAudioDetectiveCorpusRef inCorpus, UInt64 inFirst, UInt64 inCount, const UInt64* inIds /* host */);
+OSStatus LBAudioDetectiveCorpusGetEntryIds(LBAudioDetectiveCorpusRef inCorpus, UInt64 inFirst, UInt64 inCount, UInt64* outIds /* host */);
+UInt32 LBAudioDetectiveCorpusHasEntryIds(LBAudioDetectiveCorpusRef inCorpus);
+OSStatus LBAudioDetectiveCorpusIdsFromKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inKeys /* device */, UInt64 inCount,
+                                                 UInt64 inIndexBase, void* outIds /* device */, void* inStream);
+OSStatus LBAudioDetectiveCorpusKeysFromIdsDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inIds /* device */, UInt64 inCount,
+                                                 UInt64 inIndexBase, void* outKeys /* device */, void* inStream);
 /* Groups: the step between a join's duplicate pairs and the removal -- the connected components of the match graph, computed on
  * the device where the keys lie, and the key list "every entry except the first of its group", which
  * LBAudioDetectiveCorpusRemoveKeysDevice and LBAudioDetectiveCorpusGatherKeysDevice take as it is.  (The join reports ORDERED
@@ -1163,7 +1218,8 @@ OSStatus LBAudioDetectiveDebugLiveBytes(UInt64* outDevice, UInt64* outPinned);
  * grid with a stride and carry state in LDS from one item to the next -- the occurrences, recording and timeline passes, both
  * joins and their row scan, the alignment's three launches and the threshold list's count and scatter -- and of the plain
  * grid-stride launches of the stream bank, the resampler bank, the duplicate groups (init, hook, flatten), the gather's two
- * copy launches and the top-K selection's histogram and gather passes (grid.x; the rows stay in grid.y).  Each of them launches
+ * copy launches, the top-K selection's histogram and gather passes (grid.x; the rows stay in grid.y) and all six launches of the
+ * entry ids (ids from keys, the index's init and insert, keys from ids, the removal's id gather and scatter).  Each of them launches
  * min(its work, its built-in ceiling, inWorkgroups) workgroups, never fewer than 1; 0 (the default) restores the built-in
  * ceilings alone.  Results NEVER depend on the value: it only decides how many work items one workgroup takes, which is how a
  * test of seconds reaches the trips that otherwise need a corpus of a million entries.  The second call reports the ceiling
@@ -1173,7 +1229,8 @@ OSStatus LBAudioDetectiveDebugSetGridCeiling(UInt32 inWorkgroups);
 OSStatus LBAudioDetectiveDebugGridCeiling(UInt32* outWorkgroups, UInt64* outStridedLaunches);
 /* Binary corpus file ("LBADCRP1" header + the stored entries' planes; a ragged corpus: "LBADCRP2" header + the
  * entries' sub-fingerprint counts + the records); Load recognises both, reserves max(inCapacity, stored count)
- * entries and, for a ragged corpus, records in proportion. */
+ * entries and, for a ragged corpus, records in proportion.  A corpus with entry ids writes the "LBADIDS1" trailer behind either
+ * payload (see Entry ids); one without writes exactly the bytes above. */
 OSStatus LBAudioDetectiveCorpusSave(LBAudioDetectiveCorpusRef inCorpus, const char* inPath);
 LBAudioDetectiveCorpusRef LBAudioDetectiveCorpusLoad(const char* inPath, UInt64 inCapacity);
 /* Kernel selection: 0 = automatic, 1 = generic kernel, 2 = specialised plane kernel.  Ragged corpora only: 3 = always hand

@@ -242,6 +242,12 @@ _SIGNATURES = {
     "LBAudioDetectiveCorpusGatherKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, UInt64, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusGatherIndices": (OSStatus, [Ref, _P(UInt64), UInt64, C.c_void_p, UInt64, _P(UInt64)]),
     "LBAudioDetectiveCorpusCopyFingerprint": (Ref, [Ref, UInt64]),
+    "LBAudioDetectiveCorpusSetEntryIdsDevice": (OSStatus, [Ref, UInt64, UInt64, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusSetEntryIds": (OSStatus, [Ref, UInt64, UInt64, _P(UInt64)]),
+    "LBAudioDetectiveCorpusGetEntryIds": (OSStatus, [Ref, UInt64, UInt64, _P(UInt64)]),
+    "LBAudioDetectiveCorpusHasEntryIds": (UInt32, [Ref]),
+    "LBAudioDetectiveCorpusIdsFromKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveCorpusKeysFromIdsDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveGroupLabelsFromKeysDevice": (OSStatus, [C.c_void_p, UInt64, C.c_void_p, UInt64, UInt64, UInt64, C.c_void_p, UInt64, UInt64,
                                                              UInt32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveGroupExtraKeysFromLabelsDevice": (OSStatus, [C.c_void_p, UInt64, UInt64, UInt64, C.c_void_p, _P(UInt64), C.c_void_p]),

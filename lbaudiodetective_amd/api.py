@@ -1457,6 +1457,86 @@ class Corpus:
             _check(self._L.LBAudioDetectiveCorpusGatherIndices(self._ref, ip, n, packed.ctypes.data, total, op), "CorpusGatherIndices")
         return packed, offsets
 
+    # ---- entry ids: the caller's own 64-bit id of every entry (0: none), on the device with the entry: it moves with it through
+    # removals, is saved with it, comes back for any key list and names entries in the key format the taking calls read.
+    @property
+    def has_entry_ids(self) -> bool:
+        """LBAudioDetectiveCorpusHasEntryIds: ids were set (or loaded) at some time; a corpus starts without."""
+        return bool(self._L.LBAudioDetectiveCorpusHasEntryIds(self._ref))
+
+    def set_entry_ids(self, ids, first: int = 0, stream=None):
+        """LBAudioDetectiveCorpusSetEntryIdsDevice / ...SetEntryIds: entries [first, first + len(ids)) get these ids.  ids: a
+        contiguous device tensor of 8-byte elements (asynchronous on `stream`) or host integers (copied before the call returns;
+        `stream` is ignored).  A range beyond len(self) is refused and nothing changes; an empty list does not turn ids on."""
+        if hasattr(ids, "is_cuda") and ids.is_cuda:
+            assert ids.is_contiguous() and ids.element_size() == 8
+            n = ids.numel()
+            _check(self._L.LBAudioDetectiveCorpusSetEntryIdsDevice(self._ref, first, n, _dev_ptr(ids) if n else None, _stream_ptr(stream)),
+                   "CorpusSetEntryIdsDevice")
+        else:
+            host = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.uint64)
+            _check(self._L.LBAudioDetectiveCorpusSetEntryIds(self._ref, first, host.size,
+                                                            host.ctypes.data_as(C.POINTER(N.UInt64)) if host.size else None),
+                   "CorpusSetEntryIds")
+        return self
+
+    def entry_ids(self, first: int = 0, n=None) -> np.ndarray:
+        """LBAudioDetectiveCorpusGetEntryIds: the ids of entries [first, first + n) as numpy uint64 (n None: up to len(self));
+        zeros for a corpus without ids.  The range may reach up to the capacity: the words from len(self) on are zero."""
+        if n is None:
+            n = max(0, len(self) - first)
+        out = np.zeros(n, dtype=np.uint64)
+        _check(self._L.LBAudioDetectiveCorpusGetEntryIds(self._ref, first, n, out.ctypes.data_as(C.POINTER(N.UInt64)) if n else None),
+               "CorpusGetEntryIds")
+        return out
+
+    def ids_from_keys_device(self, keys, index_base: int = 0, out=None, stream=None):
+        """LBAudioDetectiveCorpusIdsFromKeysDevice: 64-bit keys on the device, exactly as the top-K, threshold, join, occurrences,
+        recording, timeline and group calls write them -> an int64 device tensor of keys.numel() ids (the id's 64 bits): 0 for
+        a zero key, a key of another entry, or a corpus without ids.  Asynchronous on `stream`."""
+        import torch
+        assert keys.is_cuda and keys.is_contiguous() and keys.element_size() == 8
+        n = keys.numel()
+        if out is None:
+            out = torch.empty(n, dtype=torch.int64, device=keys.device)
+        assert out.element_size() == 8
+        _out_ok(out, n, "out")
+        _check(self._L.LBAudioDetectiveCorpusIdsFromKeysDevice(self._ref, _dev_ptr(keys) if n else None, n, index_base,
+                                                              _dev_ptr(out) if n else None, _stream_ptr(stream)), "CorpusIdsFromKeysDevice")
+        return out
+
+    def keys_from_ids_device(self, ids, index_base: int = 0, out=None, stream=None):
+        """LBAudioDetectiveCorpusKeysFromIdsDevice: 64-bit ids on the device -> an int64 device tensor of ids.numel() keys in list
+        order: score word 1.0f, low word 0xFFFFFFFF - (index_base + index) of the LOWEST index with that id; the zero key for
+        id 0, an id no entry has, or a corpus without ids.  remove_keys_device, gather_keys_device and align_keys_device take
+        the result as it is.  Asynchronous on `stream`; the first call after ids were set, a removal or a load builds the index."""
+        import torch
+        assert ids.is_cuda and ids.is_contiguous() and ids.element_size() == 8
+        n = ids.numel()
+        if out is None:
+            out = torch.empty(n, dtype=torch.int64, device=ids.device)
+        assert out.element_size() == 8
+        _out_ok(out, n, "out")
+        _check(self._L.LBAudioDetectiveCorpusKeysFromIdsDevice(self._ref, _dev_ptr(ids) if n else None, n, index_base,
+                                                              _dev_ptr(out) if n else None, _stream_ptr(stream)), "CorpusKeysFromIdsDevice")
+        return out
+
+    def _ids_tensor(self, ids):
+        import torch
+        if hasattr(ids, "is_cuda") and ids.is_cuda:
+            return ids
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.uint64).view(np.int64)).cuda()
+
+    def remove_ids(self, ids, stream=None) -> int:
+        """take-down by id: keys_from_ids_device, then remove_keys_device.  Of entries that share an id the one at the lowest
+        index goes; ids no entry has are skipped.  Returns the number of entries removed."""
+        return self.remove_keys_device(self.keys_from_ids_device(self._ids_tensor(ids), stream=stream), stream=stream)
+
+    def gather_ids(self, ids, stream=None):
+        """hand-back by id: keys_from_ids_device, then gather_keys_device -> (packed, offsets) on the device, row i = ids[i] (an
+        empty row for an id no entry has)."""
+        return self.gather_keys_device(self.keys_from_ids_device(self._ids_tensor(ids), stream=stream), stream=stream)
+
     def fingerprint(self, index: int) -> Fingerprint:
         """LBAudioDetectiveCorpusCopyFingerprint: entry `index` as a new host Fingerprint (IndexError for index >= len(self))."""
         if not 0 <= index < len(self):

@@ -423,7 +423,7 @@ OSStatus LBAudioDetectiveCorpusAppendRaggedPackedDevice(LBAudioDetectiveCorpusRe
 
 // Everything that may still touch the corpus' memory is awaited first -- the plan, the scans, the top-K, alignment and packed
 // scratch, the joins that scanned it or took their rows from it (join_ev, with the join scratch), the gathers (gather_ev), the
-// polled query's stream --
+// id calls (ids_ev), the polled query's stream --
 // and nothing else: NOT append_event or shard_stale_event (the latter may sit behind a collective that never ends).  The
 // members then release what they own.
 void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
@@ -435,6 +435,7 @@ void LBAudioDetectiveCorpusDispose(LBAudioDetectiveCorpusRef c) {
     (void)c->pq_ev.wait();
     (void)c->join_ev.wait();
     (void)c->gather_ev.wait();
+    (void)c->ids_ev.wait();
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     delete c;
 }
@@ -880,7 +881,7 @@ OSStatus save_ragged(LBAudioDetectiveCorpus* c, FILE* f) {
         if (st != noErr) return st;
         if (std::fwrite(host.data(), 32, n, f) != n) return kLBAudioDetectiveDeviceError;
     }
-    return noErr;
+    return lbad::ids_save_trailer(c, f);                  // (a corpus without ids: nothing)
 }
 
 LBAudioDetectiveCorpusRef load_ragged(FILE* f, long file_size, uint64_t capacity) {
@@ -945,6 +946,7 @@ LBAudioDetectiveCorpusRef load_ragged(FILE* f, long file_size, uint64_t capacity
         ok = lbad::hip_status(lbad::launch_restamp_records(c->d_recs, c->d_off, h.count, h.n_pos, h.subfp_len, old_layout, nullptr),
                               "restamp records", __LINE__) == noErr &&
              lbad::hip_status(hipStreamSynchronize(nullptr), "restamp records", __LINE__) == noErr;
+    if (ok) ok = lbad::ids_load_trailer(c, f, h.count);      // (f stands behind the records)
     if (!ok) {
         LBAudioDetectiveCorpusDispose(c);
         return NULL;
@@ -980,6 +982,10 @@ OSStatus LBAudioDetectiveCorpusSave(LBAudioDetectiveCorpusRef c, const char* inP
         st = lbad::hip_status(hipMemcpy(host.data(), c->d_planes + (size_t)p * c->capacity, c->count * sizeof(uint4),
                                         hipMemcpyDeviceToHost), "corpus plane D2H", __LINE__);
         if (st == noErr && std::fwrite(host.data(), sizeof(uint4), c->count, f) != c->count) st = kLBAudioDetectiveDeviceError;
+    }
+    if (st == noErr) {
+        st = kLBAudioDetectiveMemFull;
+        try { st = lbad::ids_save_trailer(c, f); } catch (const std::bad_alloc&) {}      // (a corpus without ids: nothing)
     }
     std::fclose(f);
     return st;
@@ -1033,6 +1039,11 @@ LBAudioDetectiveCorpusRef LBAudioDetectiveCorpusLoad(const char* inPath, UInt64 
             LBAudioDetectiveCorpusDispose(c);
             c = NULL;
         }
+    }
+    // f stands behind the planes (an empty corpus: behind the header)
+    if (c && !lbad::ids_load_trailer(c, f, h.count)) {
+        LBAudioDetectiveCorpusDispose(c);
+        c = NULL;
     }
     if (c) c->count = h.count;
     std::fclose(f);

@@ -33,6 +33,7 @@ OSStatus await_in_flight(LBAudioDetectiveCorpus* c, hipStream_t stream) {
     if (st == noErr) st = c->pq_ev.wait();
     if (st == noErr) st = c->join_ev.wait();
     if (st == noErr) st = c->gather_ev.wait();
+    if (st == noErr) st = c->ids_ev.wait();
     if (st != noErr) return st;
     if (c->stream) LBAD_HIP(hipStreamSynchronize(c->stream));        // the polled top-1 query's own stream
     if (c->append_event.ev) LBAD_HIP(hipStreamWaitEvent(stream, c->append_event, 0));
@@ -145,6 +146,10 @@ OSStatus remove_impl(LBAudioDetectiveCorpus* c, const unsigned long long* d_list
         LBAD_HIP(hipStreamSynchronize(stream));
         return noErr;
     }
+    if (c->d_ids) {                                                   // the ids' scratch, before anything moves
+        st = c->d_ids_scratch.reserve((size_t)(count - first));
+        if (st != noErr) return st;
+    }
     if (c->ragged) {
         std::vector<uint32_t> new_off((size_t)kept + 1);
         std::map<uint32_t, uint64_t> hist;
@@ -173,6 +178,12 @@ OSStatus remove_impl(LBAudioDetectiveCorpus* c, const unsigned long long* d_list
             (void)hipStreamSynchronize(stream);
             return st;
         }
+    }
+    // the ids of a corpus that has them go with their entries, by the same device map (a corpus without ids: nothing happens)
+    st = ids_compact(c, ix.map, first, kept, stream);
+    if (st != noErr) {
+        (void)hipStreamSynchronize(stream);
+        return st;
     }
     c->count = kept;
     *out_removed = count - kept;

@@ -55,8 +55,8 @@ struct PerDevice {
 // never 0 for work > 0.  Results do not depend on the grid; a launch that really strides (a grid below its work) is counted.
 // The plain grid-stride launches (x += gridDim.x * threads, nothing carried) take their grids from here as well, so that the
 // tests' ceiling reaches their second trips: the stream and resampler banks, the duplicate groups' init, hook and flatten
-// (k_groups.hip), the gather's copy launches (k_gather.hip) and the top-K selection's histogram and gather passes (k_topk.hip,
-// grid.x only).  The corpus scans of k_compare.hip keep their own caps: the 10 M-entry tests cross them by shape.
+// (k_groups.hip), the gather's copy launches (k_gather.hip), the top-K selection's histogram and gather passes (k_topk.hip,
+// grid.x only) and every launch of the entry ids (k_ids.hip).  The corpus scans of k_compare.hip keep their own caps: the 10 M-entry tests cross them by shape.
 inline std::atomic<uint32_t> g_grid_ceiling{0};
 inline std::atomic<uint64_t> g_strided_launches{0};
 inline uint32_t strided_grid(uint64_t work, uint32_t built_in_ceiling) {
@@ -589,6 +589,28 @@ size_t gather_scratch_bytes(uint64_t n_keys);    // one 64-bit sum per tile
 hipError_t launch_gather(const GatherSource& src, const unsigned long long* d_keys, uint64_t n_keys, uint64_t index_base, void* d_scratch,
                          void* d_packed, uint64_t capacity, unsigned long long* d_offsets, hipStream_t stream);
 
+// entry ids (k_ids.hip): the caller's 64-bit ids of the entries, one word per entry (0: no id).
+// d_out[i] = the id of the entry key i names, 0 for a zero key or an index outside [index_base, index_base + count); d_ids null (a
+// corpus without ids): all zeros.  n <= 2^31 keys, index_base + count <= 2^32.  One launch.
+hipError_t launch_ids_from_keys(const unsigned long long* d_keys, uint64_t n, uint64_t index_base, uint64_t count,
+                                const unsigned long long* d_ids, unsigned long long* d_out, hipStream_t stream);
+// the id index: an open-addressing table of `slots` id words (0: empty) and `slots` index words, slots = ids_index_slots(count) -- a
+// power of two >= 2 x count, at least 1024.  The build is an init and an insert launch; afterwards the id of every entry with a
+// non-zero id owns one slot whose index word is the LOWEST index with that id.
+uint64_t ids_index_slots(uint64_t count);
+hipError_t launch_ids_index_build(const unsigned long long* d_ids, uint64_t count, unsigned long long* d_slot_ids,
+                                  uint32_t* d_slot_index, uint64_t slots, hipStream_t stream);
+// d_out[i] = bits(1.0f) << 32 | 0xFFFFFFFF - (index_base + index) for the lowest index whose id is d_list[i]; a zero key for id 0,
+// an id no entry has, or a null table (a corpus without ids).  n <= 2^31.  One launch, the table is only read.
+hipError_t launch_keys_from_ids(const unsigned long long* d_list, uint64_t n, uint64_t index_base, uint64_t count,
+                                const unsigned long long* d_slot_ids, const uint32_t* d_slot_index, uint64_t slots,
+                                unsigned long long* d_out, hipStream_t stream);
+// behind a removal's moves: d_map (RemoveIndex::map) takes the ids of the kept entries from `first` (the lowest removed index) on
+// to their new indices through d_scratch (count - first words), and the words from `kept` to the old `count` become zero.
+// first <= kept < count.  Two launches (one where kept == first).
+hipError_t launch_ids_compact(unsigned long long* d_ids, const uint32_t* d_map, uint64_t first, uint64_t kept, uint64_t count,
+                              unsigned long long* d_scratch, hipStream_t stream);
+
 // groups (k_groups.hip): the connected components of the graph whose edges are match keys, and the keys of every entry that is
 // not its group's first.  1 <= n <= 2^32 vertices, labels as a forest whose parents lie below their vertices (any content is
 // legal input without a reset).  Slots: n_slots <= 2^31 keys; their rows by d_offsets (n_rows + 1 words, CSR) or, when it is
@@ -1039,4 +1061,27 @@ struct LBAudioDetectiveCorpus {
     // a call reuses it only after gather_ev, recorded behind its last kernel.
     lbad::DeviceBuffer<void> d_gather_scratch;
     lbad::Event gather_ev;
+    // entry ids (LBAudioDetectiveCorpusSetEntryIds..., api_ids.cpp, k_ids.hip): empty until the first ids are set, then `capacity`
+    // words for the corpus' lifetime (0: no id; the words at and above the count are zero).  The id index (slot ids and slot
+    // indices, ids_slots of each in use) is built by the first KeysFromIds after anything made it stale and kept until then;
+    // d_ids_scratch is the removal's compaction block, h_ids_stage the host form's pinned staging.  ids_ev covers them all: an
+    // id call touches them only after it, and records it behind its last launch, also after a failure.
+    lbad::DeviceBuffer<unsigned long long> d_ids;
+    lbad::DeviceBuffer<unsigned long long> d_ids_slot_ids;
+    lbad::DeviceBuffer<uint32_t> d_ids_slot_index;
+    uint64_t ids_slots = 0;
+    bool ids_index_valid = false;
+    lbad::DeviceBuffer<unsigned long long> d_ids_scratch;
+    lbad::PinnedBuffer<unsigned long long> h_ids_stage;
+    lbad::Event ids_ev;
 };
+
+namespace lbad {
+// api_ids.cpp, for the corpus file (api_corpus.cpp): the trailer of a corpus with ids behind the payload (nothing for one
+// without), and the trailer of a file read back -- false: a trailer that lies about itself, the load fails
+OSStatus ids_save_trailer(struct ::LBAudioDetectiveCorpus* c, FILE* f);
+bool ids_load_trailer(struct ::LBAudioDetectiveCorpus* c, FILE* f, uint64_t count);
+// api_ids.cpp, for the removal (api_remove.cpp): the ids of a corpus that has them move with the entries (map: the call's device
+// map; first: the lowest removed index; kept < count entries stay) on `stream`, and the index is stale
+OSStatus ids_compact(struct ::LBAudioDetectiveCorpus* c, const uint32_t* d_map, uint64_t first, uint64_t kept, hipStream_t stream);
+}  // namespace lbad

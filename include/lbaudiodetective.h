@@ -923,6 +923,42 @@ OSStatus LBAudioDetectiveCorpusRecordingPackedTimelineKeysDevice(LBAudioDetectiv
 OSStatus LBAudioDetectiveCorpusQueryRecordingTimeline(LBAudioDetectiveCorpusRef inCorpus, LBAudioDetectiveFingerprintRef inQuery,
                                                       UInt32 inRange, Float32 inThreshold, SInt64* outIndices, Float32* outScores,
                                                       UInt32* outLengths, UInt64* outCount);
+/* Batch recording timeline: the timeline above for MANY recordings of ONE length in one call -- what plays on every channel of a
+ * broadcast monitor: hundreds to thousands of short windows against a small corpus, where one recording alone leaves the device
+ * idle almost everywhere.  inPackedQueries is on the DEVICE, [inRecordings][inSubfingerprints][LBAD_PACKED_BYTES], 4-byte
+ * aligned: exactly what LBAudioDetectiveStreamBankWindowDevice and LBAudioDetectiveFingerprintClipsDevice write.  outKeys (DEVICE,
+ * [inRecordings][inSubfingerprints] UInt64) and outLengths (DEVICE, the same shape in UInt32, may be NULL; the keys do not depend
+ * on it): row r of both is what LBAudioDetectiveCorpusRecordingPackedTimelineKeysDevice writes for recording r alone with the
+ * same other arguments -- the key format, ties to the lowest entry index, zeros where nothing counts, every word written -- bit
+ * for bit.  No record of recording r + 1 or r - 1 ever enters a cell of recording r.
+ * The restrictions and the order of refusals are the single call's (a ragged corpus, no entry above
+ * LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS, inThreshold finite and > 0, inIndexBase + entries <= 2^32; what needs no handle
+ * first, then kLBAudioDetectiveDeviceUnavailable, then what needs the corpus); in addition inRecordings >= 1 and inRecordings x
+ * inSubfingerprints <= 2^31 - 1.  An empty corpus, or one without a participating entry, is noErr with zero keys and lengths.
+ * Asynchronous on inStream, which it never awaits; it waits ON THE DEVICE for the corpus' latest append; nothing visits the host.
+ * Results do not depend on launch order, grid, chunking, the kernel form or outLengths.
+ * The scratch is the corpus' join scratch under LBAudioDetectiveCorpusSetJoinScratchLimit.  A call runs in PASSES over recordings
+ * and, within a pass, in chunks over entries: where one recording's partials of the whole corpus (the single call's formula) fit
+ * the limit, a pass takes min(inRecordings, limit / that) recordings in one chunk; otherwise one recording per pass, its entries
+ * chunked as the single call chunks them.  A limit below one block of 128 entries for ONE recording is
+ * kLBAudioDetectiveArgumentInvalid at the call.  Two kernel forms, chosen by the plan alone: form S (0), the single call's mapping
+ * with the recording as one more coordinate; form W (1), a window per wave, when a recording has fewer than 4 tiles and four
+ * windows of (126 + 2 + longest entry) records x 36 bytes plus the 20 604-byte table fit 160 KiB - 64 bytes of LDS.
+ * LBAudioDetectiveDebugTimelineBatchPlan is that plan on the host -- the call takes its own from the same function --; it needs
+ * neither device nor handle: from the shape of a call (inShortestEntry <= inLongestEntry <= the cap; inScratchLimit 0: the
+ * default) the form, the tiles per recording, the recordings per pass, the entries per chunk, the scratch of a pass and the LDS
+ * of a workgroup; kLBAudioDetectiveArgumentInvalid for a shape the call refuses, a limit that is too small or a NULL pointer.
+ * LBAudioDetectiveDebugSetTimelineBatchForm (measurements and tests; process-wide, needs no device): non-zero makes every later
+ * plan take form S where form W would be chosen, 0 restores the choice.  Results never depend on it. */
+OSStatus LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                                      UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inRange,
+                                                                      Float32 inThreshold, UInt64 inIndexBase, void* outKeys,
+                                                                      void* outLengths, void* inStream);
+OSStatus LBAudioDetectiveDebugTimelineBatchPlan(UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inShortestEntry,
+                                                UInt32 inLongestEntry, UInt64 inEntries, UInt64 inScratchLimit, UInt32* outForm,
+                                                UInt64* outTiles, UInt32* outRecordingsPerPass, UInt64* outEntriesPerChunk,
+                                                UInt64* outScratchBytes, UInt64* outLdsBytes);
+OSStatus LBAudioDetectiveDebugSetTimelineBatchForm(UInt32 inForceShared);
 /* Removal: entries taken out of a corpus on the device, the other half of the corpus life cycle -- the take-down of one
  * recording, or the action behind a join's duplicate pairs.  Both forms, both kinds of corpus (uniform of any shape, ragged):
  * the named entries go, the others keep their relative order and close up -- the entry at old index i gets the new index

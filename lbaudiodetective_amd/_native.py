@@ -236,7 +236,12 @@ _SIGNATURES = {
                                                                            C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusQueryRecordingTimeline": (OSStatus, [Ref, Ref, UInt32, Float32, _P(SInt64), _P(Float32), _P(UInt32),
                                                                 _P(UInt64)]),
-    "LBAudioDetectiveCorpusRemoveIndices": (OSStatus, [Ref, _P(UInt64), UInt64, _P(UInt32), _P(UInt64)]),
+    "LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, UInt32, Float32, UInt64,
+                                                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveDebugTimelineBatchPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, UInt64, UInt64, _P(UInt32), _P(UInt64), _P(UInt32),
+                                                          _P(UInt64), _P(UInt64), _P(UInt64)]),
+    "LBAudioDetectiveDebugSetTimelineBatchForm": (OSStatus, [UInt32]),
+    "LBAudioDetectiveCorpusRemoveIndices":(OSStatus, [Ref, _P(UInt64), UInt64, _P(UInt32), _P(UInt64)]),
     "LBAudioDetectiveCorpusRemoveKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, _P(UInt64), C.c_void_p]),
     "LBAudioDetectiveCorpusSetRemoveScratchLimit": (OSStatus, [Ref, UInt64]),
     "LBAudioDetectiveCorpusGatherKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, UInt64, C.c_void_p, C.c_void_p]),

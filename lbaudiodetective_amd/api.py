@@ -659,6 +659,16 @@ class StreamBank:
         return corpus.query_packed_topk_keys_device(packed, packed.shape[0], n, k, aligned=aligned, range_=range_, stream=stream)
 
 
+    def timeline(self, corpus: "Corpus", channels, n: int, threshold: float, range_: int = 0, index_base: int = 0,
+                 want_lengths: bool = True, stream=None):
+        """What plays on every listed channel: the n most recent sub-fingerprints of each against the corpus, window_device, then
+        Corpus.recording_timeline_batch_keys_device on its output, on ONE stream with nothing in between.  Returns (keys int64
+        [len(channels), n], lengths int32 of the same shape or None): per channel and offset of its window the best entry at or
+        above `threshold` that starts there and lies inside the window."""
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.recording_timeline_batch_keys_device(packed, packed.shape[0], n, threshold, range_=range_, index_base=index_base,
+                                                           want_lengths=want_lengths, stream=stream)
+
 def debug_resampler_bank_plan(rate_in: float, rate_out: float, mode: int, input_totals, output_totals, counts, finish: bool = False):
     """LBAudioDetectiveDebugResamplerBankPlan (tests): the host plan of one resampler-bank call -> (new, carried, m_lo, m_hi): the
     samples every channel emits and carries afterwards (uint32 arrays, one value per channel) and the rate pair's tap range.
@@ -1345,6 +1355,32 @@ class Corpus:
                    "CorpusRecordingPackedTimelineKeysDevice")
         return keys_out, lengths_out
 
+    def recording_timeline_batch_keys_device(self, packed, n_recordings: int, per_query: int, threshold: float, range_: int = 0,
+                                             index_base: int = 0, keys_out=None, lengths_out=None, want_lengths: bool = True,
+                                             stream=None):
+        """LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice: the timeline of n_recordings recordings of per_query packed
+        sub-fingerprints each, already on the device as [n_recordings, per_query, 32] bytes (StreamBank.window_device's block) ->
+        (keys int64 [n_recordings, per_query], lengths int32 [n_recordings, per_query] or None) on the device, asynchronously on
+        `stream`.  Row r is what recording_timeline_keys_device gives for recording r alone, bit for bit.  want_lengths=False (and
+        no lengths_out) passes NULL: the keys are the same.  Decode with decode_timeline_batch_keys."""
+        R, per = int(n_recordings), int(per_query)
+        _packed_ok(packed, R, per)
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        n = R * per
+        if keys_out is None or (want_lengths and lengths_out is None):
+            import torch
+            if keys_out is None:
+                keys_out = torch.empty(max(1, n), dtype=torch.int64, device=dev)[:n].reshape(R, per)
+            if want_lengths and lengths_out is None:
+                lengths_out = torch.empty(max(1, n), dtype=torch.int32, device=dev)[:n].reshape(R, per)
+        _out_ok(keys_out, n, "keys_out")
+        if lengths_out is not None:
+            _out_ok(lengths_out, n, "lengths_out")
+        _check(self._L.LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice(
+            self._ref, _dev_ptr(packed), R, per, range_, threshold, index_base, _dev_ptr(keys_out),
+            _dev_ptr(lengths_out) if lengths_out is not None else None, _stream_ptr(stream)), "CorpusRecordingPackedTimelineBatchKeysDevice")
+        return keys_out, lengths_out
+
     def recording_timeline(self, fp: Fingerprint, threshold: float, range_: int = 0):
         """LBAudioDetectiveCorpusQueryRecordingTimeline: (indices int64[n_q], scores float32[n_q], lengths uint32[n_q]) per offset
         of the query: the best entry at or above `threshold` that starts there and lies inside the query, its score and its
@@ -1784,6 +1820,26 @@ def debug_grid_ceiling():
     return n.value, strided.value
 
 
+def debug_timeline_batch_plan(n_recordings: int, per_query: int, shortest_entry: int, longest_entry: int, entries: int,
+                              scratch_limit: int = 0) -> dict:
+    """LBAudioDetectiveDebugTimelineBatchPlan: the host plan of one batch timeline call -- the one the call itself takes -- as a
+    dict: form (0: S, the shared window; 1: W, a window per wave), tiles per recording, recordings_per_pass, entries_per_chunk,
+    scratch_bytes of a pass, lds_bytes of a workgroup.  scratch_limit 0: the default.  Raises for a shape or limit the call
+    refuses.  Needs no GPU."""
+    form, rpp = N.UInt32(0), N.UInt32(0)
+    tiles, chunk, scratch, lds = N.UInt64(0), N.UInt64(0), N.UInt64(0), N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveDebugTimelineBatchPlan(int(n_recordings), int(per_query), int(shortest_entry), int(longest_entry),
+                                                          int(entries), int(scratch_limit), C.byref(form), C.byref(tiles), C.byref(rpp),
+                                                          C.byref(chunk), C.byref(scratch), C.byref(lds)), "DebugTimelineBatchPlan")
+    return {"form": form.value, "tiles": tiles.value, "recordings_per_pass": rpp.value, "entries_per_chunk": chunk.value,
+            "scratch_bytes": scratch.value, "lds_bytes": lds.value}
+
+
+def debug_set_timeline_batch_form(force_shared: bool) -> None:
+    """LBAudioDetectiveDebugSetTimelineBatchForm (measurements and tests): True makes every later batch timeline plan take form S
+    where form W would be chosen, False restores the choice.  Results never depend on it."""
+    _check(N.lib().LBAudioDetectiveDebugSetTimelineBatchForm(1 if force_shared else 0), "DebugSetTimelineBatchForm")
+
 class Comm:
     """An RCCL communicator made through the library's helpers (ncclCommInitRank with the current device).
     `unique_id()` on rank 0, the 128 bytes travel to the other ranks by whatever means the host has, then every
@@ -1936,6 +1992,13 @@ def decode_timeline_keys(keys, lengths=None, index_base: int = 0):
         ln = np.asarray(lengths.cpu().numpy() if hasattr(lengths, "cpu") else lengths).reshape(-1).astype(np.int64).astype(np.uint32)
     return idx, sc, ln
 
+
+def decode_timeline_batch_keys(keys, lengths=None, index_base: int = 0):
+    """decode_timeline_keys for a batch call's 2-D keys (and lengths): the same three arrays in the keys' own shape
+    [recordings, offsets], row r what decode_timeline_keys gives for row r."""
+    shape = tuple(keys.shape)
+    idx, sc, ln = decode_timeline_keys(keys, lengths, index_base)
+    return idx.reshape(shape), sc.reshape(shape), (ln.reshape(shape) if ln is not None else None)
 
 def timeline_segments(indices, scores, lengths):
     """Non-overlapping spans from a timeline's per-offset winners (indices -1 where there is none): the winners are visited in

@@ -479,6 +479,30 @@ hipError_t launch_timeline_chunk(const TimelineCall& call, void* d_scratch, uint
 hipError_t launch_timeline_lengths(const unsigned long long* d_keys, uint32_t n, uint64_t index_base, uint64_t count,
                                    const uint32_t* d_off, uint32_t* d_lengths, hipStream_t stream);
 
+// batch recording timeline (k_timeline_batch.hip): the timeline above for `recordings` recordings of n_query sub-fingerprints each,
+// one after the other in d_qwords and in d_keys.  A call runs in passes over recordings and, within a pass, in chunks over entries.
+constexpr uint32_t kTimelineBatchFormShared = 0;   // form S: the single call's mapping, the recording one more coordinate of a unit
+constexpr uint32_t kTimelineBatchFormWave = 1;     // form W: a window per wave, for recordings of fewer than four tiles
+struct TimelineBatchPlan {
+    uint32_t form = kTimelineBatchFormShared;
+    uint64_t tiles = 0;                  // timeline_tiles(n_query, ne_min), per recording
+    uint32_t recordings_per_pass = 0;
+    uint64_t entries_per_chunk = 0;      // a multiple of timeline_block_entries(), or the corpus rounded up to one (0: empty corpus)
+    uint64_t scratch_bytes = 0;          // recordings_per_pass x timeline_scratch_bytes(entries_per_chunk, tiles)
+    uint64_t lds_bytes = 0;              // of a workgroup of the form's maxima kernel
+};
+// THE plan of a call, the debug symbol's and the real call's: several recordings a pass when one recording's whole-corpus partials
+// fit the limit (0: kJoinScratchDefault), else one recording a pass with the single call's entry chunks; recordings x entries x
+// tiles of a pass within the pair loop's 32-bit indices.  Form W exactly when tiles < 4 and four windows of 126 + 2 + ne_max
+// records with the table fit the LDS budget (and the tests do not force form S).  false: the limit holds no block of entries of
+// one recording.  With one recording: the single call's tiles, chunk and scratch.
+bool timeline_batch_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uint32_t ne_max, uint64_t entries, uint64_t limit_bytes,
+                         bool force_shared, TimelineBatchPlan* plan);
+// one chunk of one pass: `recordings` recordings from call.d_qwords / call.d_keys on, `entries` entries from `first_entry`, folded
+// into the keys; d_scratch: plan.scratch_bytes, every word written before it is read.  Two or three launches on the call's stream.
+hipError_t launch_timeline_batch_chunk(const TimelineCall& call, const TimelineBatchPlan& plan, uint32_t recordings, void* d_scratch,
+                                       uint64_t first_entry, uint64_t entries);
+
 // The host side the three families above share (recording_pass.cpp; DESIGN.md 4.4n states the protocol).
 // The query of a call: a handle (staged through the alignment's pair, under its event) or packed sub-fingerprints on the device
 // (through the builder of k_query.hip, under the packed calls' event), and the range it is compared over (0: the whole length)

@@ -959,6 +959,37 @@ OSStatus LBAudioDetectiveDebugTimelineBatchPlan(UInt32 inRecordings, UInt32 inSu
                                                 UInt64* outTiles, UInt32* outRecordingsPerPass, UInt64* outEntriesPerChunk,
                                                 UInt64* outScratchBytes, UInt64* outLdsBytes);
 OSStatus LBAudioDetectiveDebugSetTimelineBatchForm(UInt32 inForceShared);
+/* Recording segments: "what played when" from a timeline's per-offset winners, on the device -- non-overlapping spans per
+ * recording, for one recording (inRecordings == 1) or a batch.  inKeys ([inRecordings][inSubfingerprints] UInt64) and inLengths
+ * (the same shape, UInt32) are what LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice or the single timeline calls
+ * write, or the element-wise maximum of several shards' keys with the winners' lengths.  Independently per recording r: the
+ * candidates are the offsets o with a non-zero key AND a non-zero length; they are visited in descending 64-bit key order (higher
+ * score bits, then lower entry index), equal keys at the lower offset first, and a candidate is accepted when
+ * [o, min(o + length, inSubfingerprints)) meets no span accepted before it -- spans that only touch do not meet, and nothing of
+ * another recording ever blocks an offset.  This is what timeline_segments of the Python interface computes on the host.
+ * Row r of outStarts / outKeys / outLengths ([inRecordings][inCapacity]; outLengths may be NULL and changes nothing else) holds
+ * the accepted spans in ascending start order in slots 0 .. min(count, inCapacity) - 1: the start, the key UNCHANGED -- so
+ * LBAudioDetectiveCorpusIdsFromKeysDevice, ...GatherKeysDevice, ...AlignKeysDevice and ...RemoveKeysDevice read outKeys as it is
+ * -- and the length as inLengths holds it; zeros stand behind them and every word of every row is written.  outCounts[r] is the
+ * TRUE number of spans, never cut; above inCapacity the row holds the first inCapacity spans by start.
+ * The call takes no handle and needs no scratch: one launch (k_segments.hip: a workgroup per recording, its state in
+ * 10 x n2 + 2.25 x inSubfingerprints bytes of LDS and a little, n2 the power of two >= max(inSubfingerprints, 64) -- 100 872
+ * bytes at the cap, which is what LBAD_SEGMENTS_MAX_SUBFINGERPRINTS comes from), asynchronous on
+ * inStream, which it never awaits.  Results do not depend on grid, launch order, stream or outLengths.  The outputs must overlap
+ * no input.
+ * Refusals, each kLBAudioDetectiveArgumentInvalid and decided before anything touches a device: a NULL pointer other than
+ * outLengths; inRecordings, inSubfingerprints or inCapacity 0; inSubfingerprints > LBAD_SEGMENTS_MAX_SUBFINGERPRINTS;
+ * inRecordings x inSubfingerprints or inRecordings x inCapacity above 2^31 - 1; a pointer not aligned to its element (8 bytes for
+ * the key blocks, 4 for the others); outKeys == inKeys or outLengths == inLengths.  Then a missing device is
+ * kLBAudioDetectiveDeviceUnavailable. */
+#define LBAD_SEGMENTS_MAX_SUBFINGERPRINTS 8192
+OSStatus LBAudioDetectiveTimelineSegmentsFromKeysDevice(const void* inKeys /* device, [inRecordings][inSubfingerprints] UInt64 */,
+                                                        const void* inLengths /* device, same shape, UInt32 */,
+                                                        UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inCapacity,
+                                                        void* outStarts /* device, [inRecordings][inCapacity] UInt32 */,
+                                                        void* outKeys /* device, [inRecordings][inCapacity] UInt64 */,
+                                                        void* outLengths /* device, [inRecordings][inCapacity] UInt32, may be NULL */,
+                                                        void* outCounts /* device, [inRecordings] UInt32 */, void* inStream);
 /* Removal: entries taken out of a corpus on the device, the other half of the corpus life cycle -- the take-down of one
  * recording, or the action behind a join's duplicate pairs.  Both forms, both kinds of corpus (uniform of any shape, ragged):
  * the named entries go, the others keep their relative order and close up -- the entry at old index i gets the new index

@@ -25,6 +25,7 @@ PACKED_WORDS = 8
 PACKED_BYTES = 32
 SHARD_KEYS = 4096          # LBAD_SHARD_KEYS: queries per exchange of a sharded query
 ROWS_PER_FRAME = 128
+SEGMENTS_MAX_SUBFINGERPRINTS = 8192   # LBAD_SEGMENTS_MAX_SUBFINGERPRINTS: offsets of one recording of the segments call
 
 
 class AudioStreamBasicDescription(C.Structure):
@@ -241,6 +242,8 @@ _SIGNATURES = {
     "LBAudioDetectiveDebugTimelineBatchPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, UInt64, UInt64, _P(UInt32), _P(UInt64), _P(UInt32),
                                                           _P(UInt64), _P(UInt64), _P(UInt64)]),
     "LBAudioDetectiveDebugSetTimelineBatchForm": (OSStatus, [UInt32]),
+    "LBAudioDetectiveTimelineSegmentsFromKeysDevice": (OSStatus, [C.c_void_p, C.c_void_p, UInt32, UInt32, UInt32, C.c_void_p, C.c_void_p,
+                                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusRemoveIndices":(OSStatus, [Ref, _P(UInt64), UInt64, _P(UInt32), _P(UInt64)]),
     "LBAudioDetectiveCorpusRemoveKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, _P(UInt64), C.c_void_p]),
     "LBAudioDetectiveCorpusSetRemoveScratchLimit": (OSStatus, [Ref, UInt64]),

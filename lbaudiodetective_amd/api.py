@@ -669,6 +669,16 @@ class StreamBank:
         return corpus.recording_timeline_batch_keys_device(packed, packed.shape[0], n, threshold, range_=range_, index_base=index_base,
                                                            want_lengths=want_lengths, stream=stream)
 
+    def segments(self, corpus: "Corpus", channels, n: int, threshold: float, capacity: int, range_: int = 0, index_base: int = 0,
+                 stream=None):
+        """What played when on every listed channel: window_device, then Corpus.recording_segments_batch_keys_device on its
+        output, on ONE stream with nothing in between.  Returns (starts int32, keys int64, lengths int32, all [len(channels),
+        capacity], counts int32 [len(channels)]): per channel the non-overlapping spans of its window of n sub-fingerprints in
+        start order."""
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.recording_segments_batch_keys_device(packed, packed.shape[0], n, threshold, capacity, range_=range_,
+                                                           index_base=index_base, stream=stream)
+
 def debug_resampler_bank_plan(rate_in: float, rate_out: float, mode: int, input_totals, output_totals, counts, finish: bool = False):
     """LBAudioDetectiveDebugResamplerBankPlan (tests): the host plan of one resampler-bank call -> (new, carried, m_lo, m_hi): the
     samples every channel emits and carries afterwards (uint32 arrays, one value per channel) and the rate pair's tap range.
@@ -1381,6 +1391,25 @@ class Corpus:
             _dev_ptr(lengths_out) if lengths_out is not None else None, _stream_ptr(stream)), "CorpusRecordingPackedTimelineBatchKeysDevice")
         return keys_out, lengths_out
 
+    def recording_segments_batch_keys_device(self, packed, n_recordings: int, per_query: int, threshold: float, capacity: int,
+                                             range_: int = 0, index_base: int = 0, stream=None):
+        """What played when in n_recordings recordings at once: recording_timeline_batch_keys_device, then
+        timeline_segments_device on its output, on ONE stream with nothing in between (per_query <= 8192).  Returns (starts int32,
+        keys int64, lengths int32, all [n_recordings, capacity], counts int32 [n_recordings]) on the device: row r holds the
+        non-overlapping spans of recording r in start order, zeros behind them; counts are never cut.  Decode with
+        decode_segments(..., index_base).  The timeline's keys and lengths in between are allocated under `stream`, like the
+        outputs: they are dropped on return while `stream` may still use them, and only a block that belongs to `stream` is
+        handed out again behind that work."""
+        import torch
+        R, per = int(n_recordings), int(per_query)
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        with torch.cuda.stream(stream):                  # (the blocks belong to the stream that fills them)
+            keys = torch.empty(max(1, R * per), dtype=torch.int64, device=dev)[:R * per].reshape(R, per)
+            lengths = torch.empty(max(1, R * per), dtype=torch.int32, device=dev)[:R * per].reshape(R, per)
+        self.recording_timeline_batch_keys_device(packed, R, per, threshold, range_=range_, index_base=index_base, keys_out=keys,
+                                                  lengths_out=lengths, stream=stream)
+        return timeline_segments_device(keys, lengths, capacity, stream=stream)
+
     def recording_timeline(self, fp: Fingerprint, threshold: float, range_: int = 0):
         """LBAudioDetectiveCorpusQueryRecordingTimeline: (indices int64[n_q], scores float32[n_q], lengths uint32[n_q]) per offset
         of the query: the best entry at or above `threshold` that starts there and lies inside the query, its score and its
@@ -2021,6 +2050,75 @@ def timeline_segments(indices, scores, lengths):
         kept.append(int(o))
     kept = np.asarray(sorted(kept), dtype=np.int64)
     return kept, idx[kept], sc[kept], ln[kept]
+
+
+def timeline_segments_device(keys, lengths, capacity: int, starts_out=None, keys_out=None, lengths_out=None, counts_out=None,
+                             want_lengths: bool = True, stream=None):
+    """LBAudioDetectiveTimelineSegmentsFromKeysDevice: timeline_segments on the device, for the keys and lengths of one recording
+    ([n], as recording_timeline_keys_device returns them) or of a batch ([recordings, n], as recording_timeline_batch_keys_device
+    and StreamBank.timeline return them; n <= 8192) -> (starts int32 [recordings, capacity], keys int64 [recordings, capacity],
+    lengths int32 of that shape or None, counts int32 [recordings]) on the device, asynchronously on `stream`; for 1-D input the
+    rows themselves ([capacity], ..., a scalar tensor).  A row holds its recording's non-overlapping spans in start order, the
+    keys unchanged -- ids_from_keys_device, gather_keys_device, align_keys_device, remove_keys_device and decode_threshold_keys
+    read the key block as it is -- zeros behind them; counts are the true numbers of spans, never cut at `capacity`.
+    want_lengths=False (and no lengths_out) passes NULL: the other outputs are the same.  Decode with decode_segments."""
+    if keys.dim() not in (1, 2) or tuple(lengths.shape) != tuple(keys.shape):
+        raise ValueError("keys and lengths must be 1-D or 2-D tensors of one shape")
+    import torch
+    if not (keys.is_cuda and keys.is_contiguous() and lengths.is_cuda and lengths.is_contiguous()
+            and keys.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+            and lengths.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))):
+        raise ValueError("keys (int64 or uint64) and lengths (int32 or uint32) must be contiguous device tensors")
+    R, per = (1, keys.shape[0]) if keys.dim() == 1 else (keys.shape[0], keys.shape[1])
+    cap = int(capacity)
+    if starts_out is None or keys_out is None or counts_out is None or (want_lengths and lengths_out is None):
+        with torch.cuda.stream(stream):                 # (the blocks belong to the stream that fills them)
+            shape = (max(1, R), max(1, cap))
+            if starts_out is None:
+                starts_out = torch.empty(shape, dtype=torch.int32, device=keys.device)
+            if keys_out is None:
+                keys_out = torch.empty(shape, dtype=torch.int64, device=keys.device)
+            if want_lengths and lengths_out is None:
+                lengths_out = torch.empty(shape, dtype=torch.int32, device=keys.device)
+            if counts_out is None:
+                counts_out = torch.empty(max(1, R), dtype=torch.int32, device=keys.device)
+    _out_ok(starts_out, R * cap, "starts_out")
+    _out_ok(keys_out, R * cap, "keys_out")
+    _out_ok(counts_out, R, "counts_out")
+    if lengths_out is not None:
+        _out_ok(lengths_out, R * cap, "lengths_out")
+    _check(N.lib().LBAudioDetectiveTimelineSegmentsFromKeysDevice(
+        _dev_ptr(keys), _dev_ptr(lengths), R, per, cap, _dev_ptr(starts_out), _dev_ptr(keys_out),
+        _dev_ptr(lengths_out) if lengths_out is not None else None, _dev_ptr(counts_out), _stream_ptr(stream)),
+        "TimelineSegmentsFromKeysDevice")
+    if keys.dim() == 1:                                  # (outputs given as [capacity] or [1, capacity]: the row either way)
+        def row(x):
+            return x.reshape(-1)[:cap] if hasattr(x, "reshape") else x
+        return (row(starts_out), row(keys_out), (row(lengths_out) if lengths_out is not None else None),
+                counts_out.reshape(-1)[0] if hasattr(counts_out, "reshape") else counts_out)
+    return starts_out, keys_out, lengths_out, counts_out
+
+
+def decode_segments(starts, keys, lengths, counts, index_base: int = 0):
+    """The rows of timeline_segments_device on the host: per recording the (start int64[m], index int64[m], score float32[m],
+    length uint32[m]) arrays timeline_segments returns, m = min(count, capacity); a list with one tuple per recording, or the one
+    tuple for 1-D rows.  Without lengths the last array is None."""
+    def host(x, dtype):
+        return np.asarray(x.cpu().numpy() if hasattr(x, "cpu") else x).astype(dtype)
+
+    k = host(keys, np.int64).astype(np.uint64)
+    one = k.ndim == 1
+    k = k.reshape(1, -1) if one else k
+    st = host(starts, np.int64).reshape(k.shape)
+    ln = host(lengths, np.int64).astype(np.uint32).reshape(k.shape) if lengths is not None else None
+    cnt = host(counts, np.int64).reshape(-1)
+    out = []
+    for r in range(k.shape[0]):
+        m = min(int(cnt[r]), k.shape[1])
+        idx = (0xFFFFFFFF - (k[r, :m] & np.uint64(0xFFFFFFFF))).astype(np.int64) - int(index_base)
+        sc = (k[r, :m] >> np.uint64(32)).astype(np.uint32).view(np.float32)
+        out.append((st[r, :m].copy(), idx, sc, ln[r, :m].copy() if ln is not None else None))
+    return out[0] if one else out
 
 
 def decode_join_keys(keys, offsets, first: int = 0):

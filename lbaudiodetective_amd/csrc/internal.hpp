@@ -503,6 +503,16 @@ bool timeline_batch_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uin
 hipError_t launch_timeline_batch_chunk(const TimelineCall& call, const TimelineBatchPlan& plan, uint32_t recordings, void* d_scratch,
                                        uint64_t first_entry, uint64_t entries);
 
+// recording segments (k_segments.hip): per recording the non-overlapping spans of a timeline's winners -- d_keys and d_lengths as
+// the timeline calls write them, [recordings][per], per <= LBAD_SEGMENTS_MAX_SUBFINGERPRINTS, both products with `recordings`
+// below 2^31 -- greedy in descending key order (ties to the lower offset), in start order to the rows of `capacity` slots of
+// d_starts / d_out_keys / d_out_lengths (may be null), zeros behind them, the true count to d_counts.  The outputs overlap no
+// input.  One launch, no scratch; segments_lds_bytes: the dynamic LDS of a workgroup (0 for a length outside the cap).
+size_t segments_lds_bytes(uint32_t per);
+hipError_t launch_timeline_segments(const unsigned long long* d_keys, const uint32_t* d_lengths, uint32_t recordings, uint32_t per,
+                                    uint32_t capacity, uint32_t* d_starts, unsigned long long* d_out_keys, uint32_t* d_out_lengths,
+                                    uint32_t* d_counts, hipStream_t stream);
+
 // The host side the three families above share (recording_pass.cpp; DESIGN.md 4.4n states the protocol).
 // The query of a call: a handle (staged through the alignment's pair, under its event) or packed sub-fingerprints on the device
 // (through the builder of k_query.hip, under the packed calls' event), and the range it is compared over (0: the whole length)

@@ -959,6 +959,55 @@ OSStatus LBAudioDetectiveDebugTimelineBatchPlan(UInt32 inRecordings, UInt32 inSu
                                                 UInt64* outTiles, UInt32* outRecordingsPerPass, UInt64* outEntriesPerChunk,
                                                 UInt64* outScratchBytes, UInt64* outLdsBytes);
 OSStatus LBAudioDetectiveDebugSetTimelineBatchForm(UInt32 inForceShared);
+/* Batch recording scores and batch recording top-K: the recording scores and the recording top-K above for MANY recordings of ONE
+ * length in one call -- which entries the window of every channel of a broadcast monitor matches best, and where.
+ * inPackedQueries is on the DEVICE, [inRecordings][inSubfingerprints][LBAD_PACKED_BYTES], 4-byte aligned: exactly what
+ * LBAudioDetectiveStreamBankWindowDevice and LBAudioDetectiveFingerprintClipsDevice write.
+ * LBAudioDetectiveCorpusRecordingPackedScoresBatchDevice: outScores (DEVICE, [inRecordings][entries] Float32) and outLags (DEVICE,
+ * the same shape in SInt32, may be NULL; the scores do not depend on it): row r of both is what
+ * LBAudioDetectiveCorpusRecordingPackedScoresDevice writes for recording r alone, bit for bit; every word is written.
+ * LBAudioDetectiveCorpusQueryPackedRecordingTopKBatchKeysDevice: outKeys (DEVICE, [inRecordings][inK] UInt64) and outLags (DEVICE,
+ * the same shape in SInt32, may be NULL): row r of both is what LBAudioDetectiveCorpusQueryPackedRecordingTopKKeysDevice writes for
+ * recording r alone -- and therefore what LBAudioDetectiveCorpusQueryPackedTopKKeysDevice writes for query r of inRecordings, keys
+ * and lags -- bit for bit: the same selection (score > 0, descending, the lowest index first, zero keys behind), run once per pass
+ * with one row per recording.  Entries longer than the recordings take part, as in the single calls: the recording slides along
+ * them.  No record of recording r + 1 or r - 1 ever enters a cell of recording r.
+ * The restrictions and the order of refusals are the single calls' (a ragged corpus, no entry above
+ * LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS, 1 <= inK <= LBAD_TOPK_MAX, inIndexBase + entries <= 2^32; what needs no handle first,
+ * then kLBAudioDetectiveDeviceUnavailable, then what needs the corpus); in addition inRecordings >= 1, inRecordings x
+ * inSubfingerprints <= 2^31 - 1, inRecordings x inK <= 2^31 and, in the scores form, inRecordings x entries <= 2^31 - 1.  An empty
+ * corpus is noErr: the scores form writes nothing, the key form zero keys and lags.
+ * Asynchronous on inStream, which it never awaits; it waits ON THE DEVICE for the corpus' latest append; nothing visits the host.
+ * Results do not depend on launch order, grid, chunking, the kernel form or outLags.
+ * The scratch is the corpus' join scratch under LBAudioDetectiveCorpusSetJoinScratchLimit.  A call runs in PASSES over recordings
+ * and, within a pass, in chunks over entries: where one recording's partials of the whole corpus (the single call's formula,
+ * entries rounded up to 64 x tiles x 8 bytes, tiles as for the occurrences) fit the limit, a pass takes the smallest of
+ * inRecordings, limit / that, (2^32 - 4097) / (entries x tiles), 65 535 and -- in the key form -- max(1, limit / (entries x 8)), the
+ * rows of scores and lags the selection reads, in one chunk; otherwise one recording per pass, its entries chunked as the single
+ * call chunks them.  A limit below one block of 64 entries for ONE recording is kLBAudioDetectiveArgumentInvalid at the call.  Two
+ * kernel forms, chosen by the plan alone: form S (0), the single call's mapping with the recording as one more coordinate; form W
+ * (1), a window per wave, when a recording has fewer than 4 tiles and four windows of (126 + 2 + longest entry) records x 36 bytes
+ * plus the 20 604-byte table fit 160 KiB - 64 bytes of LDS.
+ * LBAudioDetectiveDebugRecordingBatchPlan is that plan on the host -- the calls take their own from the same function --; it needs
+ * neither device nor handle: from the shape of a call (inShortestEntry <= inLongestEntry <= the cap; inScratchLimit 0: the
+ * default; inKeyForm non-zero: the top-K call's plan) the form, the tiles per recording, the recordings per pass, the entries per
+ * chunk, the scratch of a pass and the LDS of a workgroup; kLBAudioDetectiveArgumentInvalid for a shape the call refuses, a limit
+ * that is too small or a NULL pointer.
+ * LBAudioDetectiveDebugSetRecordingBatchForm (measurements and tests; process-wide, needs no device; independent of the batch
+ * timeline's switch): non-zero makes every later plan take form S where form W would be chosen, 0 restores the choice.  Results
+ * never depend on it. */
+OSStatus LBAudioDetectiveCorpusRecordingPackedScoresBatchDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                                UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inRange,
+                                                                Float32* outScores, SInt32* outLags, void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryPackedRecordingTopKBatchKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                                       UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inRange,
+                                                                       UInt32 inK, UInt64 inIndexBase, void* outKeys, void* outLags,
+                                                                       void* inStream);
+OSStatus LBAudioDetectiveDebugRecordingBatchPlan(UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inShortestEntry,
+                                                 UInt32 inLongestEntry, UInt64 inEntries, UInt64 inScratchLimit, UInt32 inKeyForm,
+                                                 UInt32* outForm, UInt64* outTiles, UInt32* outRecordingsPerPass,
+                                                 UInt64* outEntriesPerChunk, UInt64* outScratchBytes, UInt64* outLdsBytes);
+OSStatus LBAudioDetectiveDebugSetRecordingBatchForm(UInt32 inForceShared);
 /* Recording segments: "what played when" from a timeline's per-offset winners, on the device -- non-overlapping spans per
  * recording, for one recording (inRecordings == 1) or a batch.  inKeys ([inRecordings][inSubfingerprints] UInt64) and inLengths
  * (the same shape, UInt32) are what LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice or the single timeline calls

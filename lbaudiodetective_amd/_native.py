@@ -242,6 +242,13 @@ _SIGNATURES = {
     "LBAudioDetectiveDebugTimelineBatchPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, UInt64, UInt64, _P(UInt32), _P(UInt64), _P(UInt32),
                                                           _P(UInt64), _P(UInt64), _P(UInt64)]),
     "LBAudioDetectiveDebugSetTimelineBatchForm": (OSStatus, [UInt32]),
+    "LBAudioDetectiveCorpusRecordingPackedScoresBatchDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, UInt32, C.c_void_p, C.c_void_p,
+                                                                          C.c_void_p]),
+    "LBAudioDetectiveCorpusQueryPackedRecordingTopKBatchKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, UInt32, UInt32, UInt64,
+                                                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveDebugRecordingBatchPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, UInt64, UInt64, UInt32, _P(UInt32), _P(UInt64),
+                                                           _P(UInt32), _P(UInt64), _P(UInt64), _P(UInt64)]),
+    "LBAudioDetectiveDebugSetRecordingBatchForm": (OSStatus, [UInt32]),
     "LBAudioDetectiveTimelineSegmentsFromKeysDevice": (OSStatus, [C.c_void_p, C.c_void_p, UInt32, UInt32, UInt32, C.c_void_p, C.c_void_p,
                                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusRemoveIndices":(OSStatus, [Ref, _P(UInt64), UInt64, _P(UInt32), _P(UInt64)]),

@@ -658,6 +658,14 @@ class StreamBank:
         packed = self.window_device(channels, n, stream=stream)
         return corpus.query_packed_topk_keys_device(packed, packed.shape[0], n, k, aligned=aligned, range_=range_, stream=stream)
 
+    def identify_recordings(self, corpus: "Corpus", channels, n: int, k: int = 1, aligned: bool = False, range_: int = 0,
+                            index_base: int = 0, stream=None):
+        """identify through the batch recording top-K: window_device, then Corpus.query_packed_recording_topk_batch_keys_device on
+        its output, on ONE stream with nothing in between.  Returns what identify returns, bit for bit (a ragged corpus): the
+        [len(channels), k] int64 key tensor, and with aligned=True (keys, lags int32) -- in entry-length steps per pair."""
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.query_packed_recording_topk_batch_keys_device(packed, packed.shape[0], n, k, range_=range_, index_base=index_base,
+                                                                    aligned=aligned, stream=stream)
 
     def timeline(self, corpus: "Corpus", channels, n: int, threshold: float, range_: int = 0, index_base: int = 0,
                  want_lengths: bool = True, stream=None):
@@ -1311,6 +1319,61 @@ class Corpus:
             _dev_ptr(lags_out) if lags_out is not None else None, _stream_ptr(stream)), "CorpusQueryPackedRecordingTopKKeysDevice")
         return keys_out, lags_out
 
+    def recording_scores_batch_device(self, packed, n_recordings: int, per_query: int, range_: int = 0, scores_out=None, lags_out=None,
+                                      want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusRecordingPackedScoresBatchDevice: recording_scores_device for n_recordings recordings of per_query
+        packed sub-fingerprints each, already on the device as [n_recordings, per_query, 32] bytes (StreamBank.window_device's
+        block) -> (scores float32 [n_recordings, len(self)], lags int32 of the same shape or None) on the device, asynchronously on
+        `stream`.  Row r is what recording_scores_device gives for recording r alone, bit for bit.  want_lags=False (and no
+        lags_out) passes NULL: the scores are the same."""
+        R, per = int(n_recordings), int(per_query)
+        _packed_ok(packed, R, per)
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        count = len(self)
+        n = R * count
+        if scores_out is None or (want_lags and lags_out is None):
+            import torch
+            with torch.cuda.stream(stream):              # (the blocks belong to the stream that fills them)
+                if scores_out is None:
+                    scores_out = torch.empty(max(1, n), dtype=torch.float32, device=dev)[:n].reshape(R, count)
+                if want_lags and lags_out is None:
+                    lags_out = torch.empty(max(1, n), dtype=torch.int32, device=dev)[:n].reshape(R, count)
+        _out_ok(scores_out, n, "scores_out")
+        if lags_out is not None:
+            _out_ok(lags_out, n, "lags_out")
+        _check(self._L.LBAudioDetectiveCorpusRecordingPackedScoresBatchDevice(
+            self._ref, _dev_ptr(packed), R, per, range_, _dev_ptr(scores_out), _dev_ptr(lags_out) if lags_out is not None else None,
+            _stream_ptr(stream)), "CorpusRecordingPackedScoresBatchDevice")
+        return scores_out, lags_out
+
+    def query_packed_recording_topk_batch_keys_device(self, packed, n_recordings: int, per_query: int, k: int, range_: int = 0,
+                                                      index_base: int = 0, keys_out=None, lags_out=None, aligned: bool = False,
+                                                      stream=None):
+        """LBAudioDetectiveCorpusQueryPackedRecordingTopKBatchKeysDevice: the k best entries of n_recordings recordings of per_query
+        packed sub-fingerprints each, already on the device as [n_recordings, per_query, 32] bytes -> the [n_recordings, k] int64
+        key tensor (rows descending, 0-padded), and with aligned=True (or a lags_out) (keys, lags int32 [n_recordings, k]).  Row r
+        is what query_packed_recording_topk_keys_device gives for recording r alone, and what query_packed_topk_keys_device gives
+        for query r of the block, bit for bit -- in entry-length steps per pair, all recordings in one pass.  Asynchronous on
+        `stream`, nothing visits the host."""
+        R, per, k = int(n_recordings), int(per_query), int(k)
+        _packed_ok(packed, R, per)
+        want_lags = aligned or lags_out is not None
+        if keys_out is None or (want_lags and lags_out is None):
+            import torch
+            dev = packed.device if hasattr(packed, "device") else "cuda"
+            with torch.cuda.stream(stream):
+                if keys_out is None:
+                    keys_out = torch.empty((max(1, R), max(1, k)), dtype=torch.int64, device=dev)
+                if want_lags and lags_out is None:
+                    lags_out = torch.empty((max(1, R), max(1, k)), dtype=torch.int32, device=dev)
+        _out_ok(keys_out, R * k, "keys_out")
+        if want_lags:
+            _out_ok(lags_out, R * k, "lags_out")
+        _check(self._L.LBAudioDetectiveCorpusQueryPackedRecordingTopKBatchKeysDevice(
+            self._ref, _dev_ptr(packed), R, per, range_, k, index_base, _dev_ptr(keys_out), _dev_ptr(lags_out) if want_lags else None,
+            _stream_ptr(stream)), "CorpusQueryPackedRecordingTopKBatchKeysDevice")
+        return (keys_out, lags_out) if want_lags else keys_out
+
     def query_packed_recording_threshold_keys_device(self, packed, per_query: int, threshold: float, capacity: int, range_: int = 0,
                                                      index_base: int = 0, keys_out=None, lags_out=None, count_out=None,
                                                      want_lags: bool = True, stream=None):
@@ -1868,6 +1931,28 @@ def debug_set_timeline_batch_form(force_shared: bool) -> None:
     """LBAudioDetectiveDebugSetTimelineBatchForm (measurements and tests): True makes every later batch timeline plan take form S
     where form W would be chosen, False restores the choice.  Results never depend on it."""
     _check(N.lib().LBAudioDetectiveDebugSetTimelineBatchForm(1 if force_shared else 0), "DebugSetTimelineBatchForm")
+
+
+def debug_recording_batch_plan(n_recordings: int, per_query: int, shortest_entry: int, longest_entry: int, entries: int,
+                               scratch_limit: int = 0, key_form: bool = False) -> dict:
+    """LBAudioDetectiveDebugRecordingBatchPlan: the host plan of one batch recording scores call (key_form=True: of one batch
+    recording top-K call) -- the one the call itself takes -- as a dict: form (0: S, the shared window; 1: W, a window per wave),
+    tiles per recording, recordings_per_pass, entries_per_chunk, scratch_bytes of a pass, lds_bytes of a workgroup.
+    scratch_limit 0: the default.  Raises for a shape or limit the call refuses.  Needs no GPU."""
+    form, rpp = N.UInt32(0), N.UInt32(0)
+    tiles, chunk, scratch, lds = N.UInt64(0), N.UInt64(0), N.UInt64(0), N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveDebugRecordingBatchPlan(int(n_recordings), int(per_query), int(shortest_entry), int(longest_entry),
+                                                           int(entries), int(scratch_limit), 1 if key_form else 0, C.byref(form),
+                                                           C.byref(tiles), C.byref(rpp), C.byref(chunk), C.byref(scratch), C.byref(lds)),
+           "DebugRecordingBatchPlan")
+    return {"form": form.value, "tiles": tiles.value, "recordings_per_pass": rpp.value, "entries_per_chunk": chunk.value,
+            "scratch_bytes": scratch.value, "lds_bytes": lds.value}
+
+
+def debug_set_recording_batch_form(force_shared: bool) -> None:
+    """LBAudioDetectiveDebugSetRecordingBatchForm (measurements and tests): True makes every later batch recording plan take form S
+    where form W would be chosen, False restores the choice; the batch timeline's switch is another.  Results never depend on it."""
+    _check(N.lib().LBAudioDetectiveDebugSetRecordingBatchForm(1 if force_shared else 0), "DebugSetRecordingBatchForm")
 
 class Comm:
     """An RCCL communicator made through the library's helpers (ncclCommInitRank with the current device).

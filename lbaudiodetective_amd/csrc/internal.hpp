@@ -503,6 +503,37 @@ bool timeline_batch_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uin
 hipError_t launch_timeline_batch_chunk(const TimelineCall& call, const TimelineBatchPlan& plan, uint32_t recordings, void* d_scratch,
                                        uint64_t first_entry, uint64_t entries);
 
+// batch recording scores (k_recording_batch.hip): the recording scores above for `recordings` recordings of n_query sub-fingerprints
+// each, one after the other in d_qwords; scores and lags as rows of `pitch` words, one per recording.  A call runs in passes over
+// recordings and, within a pass, in chunks over entries.
+constexpr uint32_t kRecordingBatchFormShared = 0;  // form S: the single call's mapping, the recording one more coordinate of a unit
+constexpr uint32_t kRecordingBatchFormWave = 1;    // form W: a window per wave, for recordings of fewer than four tiles
+struct RecordingBatchPlan {
+    uint32_t form = kRecordingBatchFormShared;
+    uint64_t tiles = 0;                  // occurrences_tiles(n_query, ne_min, ne_max), per recording
+    uint32_t recordings_per_pass = 0;
+    uint64_t entries_per_chunk = 0;      // a multiple of occurrences_block_entries(), or the corpus rounded up to one (0: empty corpus)
+    uint64_t scratch_bytes = 0;          // recordings_per_pass x recording_scratch_bytes(entries_per_chunk, tiles)
+    uint64_t lds_bytes = 0;              // of a workgroup of the form's maxima kernel
+};
+// THE plan of a call, the debug symbol's and the real call's: several recordings a pass when one recording's whole-corpus partials
+// fit the limit (0: kJoinScratchDefault) -- the smallest of the recordings, limit / those partials, kOcMaxItems / (entries x
+// tiles), 65 535 and, for the key form, the rows of a score and a lag per entry that fit the same limit (at least one) -- else one
+// recording a pass with the single call's entry chunks.  Form W exactly when tiles < 4 and four windows of 126 + 2 + ne_max records
+// with the table fit the LDS budget (and the tests do not force form S).  false: the limit holds no block of entries of one
+// recording.  With one recording: the single call's tiles, chunk and scratch.
+bool recording_batch_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uint32_t ne_max, uint64_t entries, uint64_t limit_bytes,
+                          bool key_form, bool force_shared, RecordingBatchPlan* plan);
+// one chunk of one pass: `recordings` recordings from call.d_qwords on, `entries` entries from `first_entry`; call.d_scores (and
+// d_lags, optional) are row 0 of the pass, rows `pitch` words apart.  d_scratch: plan.scratch_bytes, every word written before it
+// is read.  Two launches on the call's stream.
+hipError_t launch_recording_batch_chunk(const RecordingCall& call, const RecordingBatchPlan& plan, uint32_t recordings, uint64_t pitch,
+                                        void* d_scratch, uint64_t first_entry, uint64_t entries);
+// d_lags[r][slot] = d_entry_lags[r][entry that d_keys[r][slot] names] over rows x k slots (rows of `count` entry lags), 0 for a zero
+// key; rows x k <= 2^31, index_base + count <= 2^32
+hipError_t launch_recording_batch_lag_gather(const unsigned long long* d_keys, uint32_t rows, uint32_t k, uint64_t index_base, uint64_t count,
+                                             const int32_t* d_entry_lags, int32_t* d_lags, hipStream_t stream);
+
 // recording segments (k_segments.hip): per recording the non-overlapping spans of a timeline's winners -- d_keys and d_lengths as
 // the timeline calls write them, [recordings][per], per <= LBAD_SEGMENTS_MAX_SUBFINGERPRINTS, both products with `recordings`
 // below 2^31 -- greedy in descending key order (ties to the lower offset), in start order to the rows of `capacity` slots of

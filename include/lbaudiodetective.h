@@ -1008,6 +1008,64 @@ OSStatus LBAudioDetectiveDebugRecordingBatchPlan(UInt32 inRecordings, UInt32 inS
                                                  UInt32* outForm, UInt64* outTiles, UInt32* outRecordingsPerPass,
                                                  UInt64* outEntriesPerChunk, UInt64* outScratchBytes, UInt64* outLdsBytes);
 OSStatus LBAudioDetectiveDebugSetRecordingBatchForm(UInt32 inForceShared);
+/* Batch occurrences and batch recording threshold: the occurrences and the recording threshold above for MANY recordings of ONE
+ * length in one call -- every place the window of every channel of a broadcast monitor matches, at or above a score: an event per
+ * (channel, entry, position), or per (channel, entry), with no K to guess.
+ * inPackedQueries is on the DEVICE, [inRecordings][inSubfingerprints][LBAD_PACKED_BYTES], 4-byte aligned: exactly what
+ * LBAudioDetectiveStreamBankWindowDevice and LBAudioDetectiveFingerprintClipsDevice write.  outKeys (DEVICE, [inRecordings]
+ * [inCapacity] UInt64), outLags (DEVICE, the same shape in SInt32, may be NULL; keys and counts do not depend on it) and outCounts
+ * (DEVICE, [inRecordings] UInt64); every word of all three is written.
+ * LBAudioDetectiveCorpusQueryPackedOccurrencesBatchKeysDevice: row r of keys and lags, and outCounts[r], are what
+ * LBAudioDetectiveCorpusQueryPackedOccurrencesKeysDevice writes for recording r alone with the same other arguments, bit for bit:
+ * the key format, the (entry, offset) order, the peak rule with its plateaus (inPeaksOnly), zero keys and lags behind
+ * min(count, inCapacity), the TRUE count never cut.  Entries longer than the recordings take part, as in the single call: the
+ * recording slides along them.  No record of recording r + 1 or r - 1 ever enters a cell of recording r, and a row that overflows
+ * writes nothing into its neighbours' slots.
+ * LBAudioDetectiveCorpusQueryPackedRecordingThresholdBatchKeysDevice: row r is what
+ * LBAudioDetectiveCorpusQueryPackedRecordingThresholdKeysDevice writes for recording r alone -- ascending index, the true count,
+ * the lags aligned with the keys, lag 0 for a zero key -- and therefore what LBAudioDetectiveCorpusQueryPackedThresholdKeysDevice
+ * writes for query r of inRecordings.
+ * The restrictions and the order of refusals are the single calls' (a ragged corpus, no entry above
+ * LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS, inThreshold finite and > 0, 1 <= inCapacity <= 2^31, inIndexBase + entries <= 2^32;
+ * what needs no handle first, then kLBAudioDetectiveDeviceUnavailable, then what needs the corpus); in addition inRecordings >= 1,
+ * inRecordings x inSubfingerprints <= 2^31 - 1 and inRecordings x inCapacity <= 2^31.  An empty corpus is noErr with zero keys,
+ * lags and counts.
+ * Asynchronous on inStream, which they never await; they wait ON THE DEVICE for the corpus' latest append; nothing visits the host.
+ * Results do not depend on launch order, grid, chunking, the kernel form or outLags.  Shards that hold contiguous index ranges
+ * merge per recording: the rows concatenated in rank order, the counts added.
+ * The scratch is the corpus' join scratch under LBAudioDetectiveCorpusSetJoinScratchLimit.  A call runs in PASSES over recordings.
+ * The occurrences: where one recording's scratch for the whole corpus (the single call's formula: 24 + entries rounded up to 64 x
+ * (16 + 8 x tiles) + entry blocks of 64 x groups of 4 tiles x 4 bytes) fits the limit, a pass takes the smallest of inRecordings,
+ * limit / that scratch, (2^32 - 4097) / (entries x tiles) and 65 535 recordings in one chunk, with that scratch per recording;
+ * otherwise one recording per pass, its entries chunked as the single call chunks them, the running total carried from chunk to
+ * chunk.  With one recording the tiles, the chunk and the scratch are the single call's.  A limit below one block of 64 entries
+ * for ONE recording is kLBAudioDetectiveArgumentInvalid at the call.  Two kernel forms, chosen by the plan alone: form S (0), the
+ * single call's unit with the recording as one more coordinate; form W (1), a window per wave, when a recording has fewer than 4
+ * tiles and four windows of (126 + 2 + longest entry) records x 36 bytes plus the 20 604-byte table fit 160 KiB - 64 bytes of LDS.
+ * The recording threshold: the passes, the chunks and the scratch of the batch recording top-K above (its key form), then one
+ * compaction per pass over a row per recording -- the number of launches of a pass does not grow with the recordings.
+ * LBAudioDetectiveDebugOccurrencesBatchPlan is the occurrences' plan on the host -- the call takes its own from the same function
+ * --; it needs neither device nor handle: from the shape of a call (inShortestEntry <= inLongestEntry <= the cap; inScratchLimit
+ * 0: the default) the form, the tiles per recording, the recordings per pass, the entries per chunk, the scratch of a pass and the
+ * LDS of a workgroup; kLBAudioDetectiveArgumentInvalid for a shape the call refuses, a limit that is too small or a NULL pointer.
+ * LBAudioDetectiveDebugSetOccurrencesBatchForm (measurements and tests; process-wide, needs no device; independent of the other
+ * batch calls' switches): non-zero makes every later plan of these two calls take form S where form W would be chosen, 0 restores
+ * the choice.  Results never depend on it. */
+OSStatus LBAudioDetectiveCorpusQueryPackedOccurrencesBatchKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                                     UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inRange,
+                                                                     Float32 inThreshold, UInt32 inPeaksOnly, UInt64 inCapacity,
+                                                                     UInt64 inIndexBase, void* outKeys, void* outLags, void* outCounts,
+                                                                     void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryPackedRecordingThresholdBatchKeysDevice(LBAudioDetectiveCorpusRef inCorpus,
+                                                                            const void* inPackedQueries, UInt32 inRecordings,
+                                                                            UInt32 inSubfingerprints, UInt32 inRange, Float32 inThreshold,
+                                                                            UInt64 inCapacity, UInt64 inIndexBase, void* outKeys,
+                                                                            void* outCounts, void* outLags, void* inStream);
+OSStatus LBAudioDetectiveDebugOccurrencesBatchPlan(UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inShortestEntry,
+                                                   UInt32 inLongestEntry, UInt64 inEntries, UInt64 inScratchLimit, UInt32* outForm,
+                                                   UInt64* outTiles, UInt32* outRecordingsPerPass, UInt64* outEntriesPerChunk,
+                                                   UInt64* outScratchBytes, UInt64* outLdsBytes);
+OSStatus LBAudioDetectiveDebugSetOccurrencesBatchForm(UInt32 inForceShared);
 /* Recording segments: "what played when" from a timeline's per-offset winners, on the device -- non-overlapping spans per
  * recording, for one recording (inRecordings == 1) or a batch.  inKeys ([inRecordings][inSubfingerprints] UInt64) and inLengths
  * (the same shape, UInt32) are what LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice or the single timeline calls

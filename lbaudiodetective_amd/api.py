@@ -687,6 +687,27 @@ class StreamBank:
         return corpus.recording_segments_batch_keys_device(packed, packed.shape[0], n, threshold, capacity, range_=range_,
                                                            index_base=index_base, stream=stream)
 
+    def occurrences(self, corpus: "Corpus", channels, n: int, threshold: float, capacity: int, peaks: bool = True, range_: int = 0,
+                    index_base: int = 0, want_lags: bool = True, stream=None):
+        """Every place the window of every listed channel matches the corpus at or above `threshold`: window_device, then
+        Corpus.query_packed_occurrences_batch_keys_device on its output, on ONE stream with nothing in between.  Returns (keys
+        int64 [len(channels), capacity], lags int32 of the same shape or None, counts int64 [len(channels)]): per channel its
+        matches in (entry, offset) order -- with peaks (the default) the local peaks of every profile only."""
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.query_packed_occurrences_batch_keys_device(packed, packed.shape[0], n, threshold, capacity, peaks=peaks,
+                                                                 range_=range_, index_base=index_base, want_lags=want_lags,
+                                                                 stream=stream)
+
+    def matches_above(self, corpus: "Corpus", channels, n: int, threshold: float, capacity: int, range_: int = 0, index_base: int = 0,
+                      want_lags: bool = True, stream=None):
+        """Every entry the window of every listed channel matches at or above `threshold`: window_device, then
+        Corpus.query_packed_recording_threshold_batch_keys_device on its output, on ONE stream with nothing in between.  Returns
+        (keys int64 [len(channels), capacity], lags int32 of the same shape or None, counts int64 [len(channels)]): per channel
+        the entries in ascending index with the lag of their best cell."""
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.query_packed_recording_threshold_batch_keys_device(packed, packed.shape[0], n, threshold, capacity, range_=range_,
+                                                                         index_base=index_base, want_lags=want_lags, stream=stream)
+
 def debug_resampler_bank_plan(rate_in: float, rate_out: float, mode: int, input_totals, output_totals, counts, finish: bool = False):
     """LBAudioDetectiveDebugResamplerBankPlan (tests): the host plan of one resampler-bank call -> (new, carried, m_lo, m_hi): the
     samples every channel emits and carries afterwards (uint32 arrays, one value per channel) and the rate pair's tap range.
@@ -1389,6 +1410,59 @@ class Corpus:
             _dev_ptr(lags_out) if lags_out is not None else None, _stream_ptr(stream)), "CorpusQueryPackedRecordingThresholdKeysDevice")
         return keys_out, lags_out, count_out
 
+    # ---- batch occurrences and batch recording threshold: every match on every channel at or above a score, in one call
+    def _batch_threshold_call(self, which: str, packed, n_recordings, per_query, capacity, keys_out, lags_out, counts_out, want_lags,
+                              stream, call):
+        R, per, capacity = int(n_recordings), int(per_query), int(capacity)
+        _packed_ok(packed, R, per)
+        want_lags = want_lags or lags_out is not None
+        if keys_out is None or counts_out is None or (want_lags and lags_out is None):
+            import torch
+            dev = packed.device if hasattr(packed, "device") else "cuda"
+            with torch.cuda.stream(stream):              # (the blocks belong to the stream that fills them)
+                if keys_out is None:
+                    keys_out = torch.empty((max(1, R), max(1, capacity)), dtype=torch.int64, device=dev)
+                if want_lags and lags_out is None:
+                    lags_out = torch.empty((max(1, R), max(1, capacity)), dtype=torch.int32, device=dev)
+                if counts_out is None:
+                    counts_out = torch.empty(max(1, R), dtype=torch.int64, device=dev)
+        _out_ok(keys_out, R * capacity, "keys_out")
+        _out_ok(counts_out, R, "counts_out")
+        if want_lags:
+            _out_ok(lags_out, R * capacity, "lags_out")
+        _check(call(R, per, capacity, _dev_ptr(keys_out), _dev_ptr(lags_out) if want_lags else None, _dev_ptr(counts_out),
+                    _stream_ptr(stream)), which)
+        return keys_out, (lags_out if want_lags else None), counts_out
+
+    def query_packed_occurrences_batch_keys_device(self, packed, n_recordings: int, per_query: int, threshold: float, capacity: int,
+                                                   peaks: bool = False, range_: int = 0, index_base: int = 0, keys_out=None,
+                                                   lags_out=None, counts_out=None, want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedOccurrencesBatchKeysDevice: query_packed_occurrences_keys_device for n_recordings
+        recordings of per_query packed sub-fingerprints each, already on the device as [n_recordings, per_query, 32] bytes
+        (StreamBank.window_device's block) -> (keys int64 [n_recordings, capacity], lags int32 of the same shape or None, counts
+        int64 [n_recordings]) on the device, asynchronously on `stream`.  Row r and counts[r] are what the single call gives for
+        recording r alone, bit for bit; a row that overflows touches no other row.  want_lags=False (and no lags_out) passes
+        NULL: keys and counts are the same.  Decode rows with decode_occurrence_keys."""
+        return self._batch_threshold_call(
+            "CorpusQueryPackedOccurrencesBatchKeysDevice", packed, n_recordings, per_query, capacity, keys_out, lags_out, counts_out,
+            want_lags, stream,
+            lambda R, per, cap, kp, lp, cp, sp: self._L.LBAudioDetectiveCorpusQueryPackedOccurrencesBatchKeysDevice(
+                self._ref, _dev_ptr(packed), R, per, range_, threshold, int(bool(peaks)), cap, index_base, kp, lp, cp, sp))
+
+    def query_packed_recording_threshold_batch_keys_device(self, packed, n_recordings: int, per_query: int, threshold: float,
+                                                           capacity: int, range_: int = 0, index_base: int = 0, keys_out=None,
+                                                           lags_out=None, counts_out=None, want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedRecordingThresholdBatchKeysDevice: query_packed_recording_threshold_keys_device for
+        n_recordings recordings of per_query packed sub-fingerprints each -> (keys int64 [n_recordings, capacity], lags int32 of
+        the same shape or None, counts int64 [n_recordings]) on the device, asynchronously on `stream`: per recording every entry
+        whose best cell reaches `threshold`, in ascending index, with the true count and the aligned lags.  Row r is what the
+        single call gives for recording r alone, and what query_packed_threshold_keys_device gives for query r of the block."""
+        return self._batch_threshold_call(
+            "CorpusQueryPackedRecordingThresholdBatchKeysDevice", packed, n_recordings, per_query, capacity, keys_out, lags_out,
+            counts_out, want_lags, stream,
+            lambda R, per, cap, kp, lp, cp, sp: self._L.LBAudioDetectiveCorpusQueryPackedRecordingThresholdBatchKeysDevice(
+                self._ref, _dev_ptr(packed), R, per, range_, threshold, cap, index_base, kp, cp, lp, sp))
+
     # ---- recording timeline: the best entry at every offset of ONE query (a long recording) against a ragged corpus -- the
     # occurrences cells folded per offset over the entries not longer than the query.  One key per sub-fingerprint of the query,
     # whatever the corpus size.  Shards of contiguous index ranges merge by the element-wise maximum of their keys AS UNSIGNED
@@ -1953,6 +2027,29 @@ def debug_set_recording_batch_form(force_shared: bool) -> None:
     """LBAudioDetectiveDebugSetRecordingBatchForm (measurements and tests): True makes every later batch recording plan take form S
     where form W would be chosen, False restores the choice; the batch timeline's switch is another.  Results never depend on it."""
     _check(N.lib().LBAudioDetectiveDebugSetRecordingBatchForm(1 if force_shared else 0), "DebugSetRecordingBatchForm")
+
+
+def debug_occurrences_batch_plan(n_recordings: int, per_query: int, shortest_entry: int, longest_entry: int, entries: int,
+                                 scratch_limit: int = 0) -> dict:
+    """LBAudioDetectiveDebugOccurrencesBatchPlan: the host plan of one batch occurrences call -- the one the call itself takes --
+    as a dict: form (0: S, the shared window; 1: W, a window per wave), tiles per recording, recordings_per_pass,
+    entries_per_chunk, scratch_bytes of a pass, lds_bytes of a workgroup.  scratch_limit 0: the default.  Raises for a shape or
+    limit the call refuses.  Needs no GPU."""
+    form, rpp = N.UInt32(0), N.UInt32(0)
+    tiles, chunk, scratch, lds = N.UInt64(0), N.UInt64(0), N.UInt64(0), N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveDebugOccurrencesBatchPlan(int(n_recordings), int(per_query), int(shortest_entry), int(longest_entry),
+                                                             int(entries), int(scratch_limit), C.byref(form), C.byref(tiles),
+                                                             C.byref(rpp), C.byref(chunk), C.byref(scratch), C.byref(lds)),
+           "DebugOccurrencesBatchPlan")
+    return {"form": form.value, "tiles": tiles.value, "recordings_per_pass": rpp.value, "entries_per_chunk": chunk.value,
+            "scratch_bytes": scratch.value, "lds_bytes": lds.value}
+
+
+def debug_set_occurrences_batch_form(force_shared: bool) -> None:
+    """LBAudioDetectiveDebugSetOccurrencesBatchForm (measurements and tests): True makes every later plan of the batch occurrences
+    and the batch recording threshold take form S where form W would be chosen, False restores the choice; the other batch
+    calls' switches are others.  Results never depend on it."""
+    _check(N.lib().LBAudioDetectiveDebugSetOccurrencesBatchForm(1 if force_shared else 0), "DebugSetOccurrencesBatchForm")
 
 class Comm:
     """An RCCL communicator made through the library's helpers (ncclCommInitRank with the current device).

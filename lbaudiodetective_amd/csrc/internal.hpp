@@ -534,6 +534,45 @@ hipError_t launch_recording_batch_chunk(const RecordingCall& call, const Recordi
 hipError_t launch_recording_batch_lag_gather(const unsigned long long* d_keys, uint32_t rows, uint32_t k, uint64_t index_base, uint64_t count,
                                              const int32_t* d_entry_lags, int32_t* d_lags, hipStream_t stream);
 
+// batch occurrences (k_occurrences_batch.hip): the occurrences above for `recordings` recordings of n_query sub-fingerprints each,
+// one after the other in d_qwords; keys and lags as rows of `capacity` slots, one per recording, and a count per recording.  A call
+// runs in passes over recordings and, within a pass of ONE recording, in chunks over entries.
+constexpr uint32_t kOccurrencesBatchFormShared = 0;    // form S: the single call's unit, the recording one more coordinate
+constexpr uint32_t kOccurrencesBatchFormWave = 1;      // form W: a window per wave, for recordings of fewer than four tiles
+struct OccurrencesBatchPlan {
+    uint32_t form = kOccurrencesBatchFormShared;
+    uint64_t tiles = 0;                  // occurrences_tiles(n_query, ne_min, ne_max), per recording
+    uint32_t recordings_per_pass = 0;
+    uint64_t entries_per_chunk = 0;      // a multiple of occurrences_block_entries(), or the corpus rounded up to one (0: empty corpus)
+    uint64_t scratch_bytes = 0;          // recordings_per_pass x occurrences_scratch_bytes(entries_per_chunk, tiles)
+    uint64_t lds_bytes = 0;              // of a workgroup of the form's count and scatter kernels
+};
+// THE plan of a call, the debug symbol's and the real call's: several recordings a pass when one recording's scratch for the whole
+// corpus fits the limit (0: kJoinScratchDefault) -- the smallest of the recordings, limit / that scratch, kOcMaxItems / (entries x
+// tiles) and 65 535 -- else one recording a pass with the single call's entry chunks and its carried total.  Form W exactly when
+// tiles < 4 and four windows of 126 + 2 + ne_max records with the table fit the LDS budget (and the tests do not force form S).
+// false: the limit holds no block of entries of one recording.  With one recording: the single call's tiles, chunk and scratch.
+bool occurrences_batch_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uint32_t ne_max, uint64_t entries, uint64_t limit_bytes,
+                            bool force_shared, OccurrencesBatchPlan* plan);
+// one chunk of one pass: `recordings` recordings from call.d_qwords on, `entries` entries from `first_entry`; call.d_keys (and
+// d_lags, optional) are row 0 of the pass, rows call.capacity slots apart, zeroed by the caller.  A pass of more than one recording
+// is ONE chunk of the whole corpus (first_chunk 1) and writes its recordings' counts to d_counts; a pass of one recording
+// (plan.recordings_per_pass == 1) carries its total in the first word of d_scratch as launch_occurrences_chunk does, for the
+// caller to copy.  d_scratch: plan.scratch_bytes, the SAME block for every chunk of a pass.  Four or five launches on the call's
+// stream, nothing visits the host.
+hipError_t launch_occurrences_batch_chunk(const OccurrencesCall& call, const OccurrencesBatchPlan& plan, uint32_t recordings,
+                                          void* d_scratch, uint64_t first_entry, uint64_t entries, uint32_t first_chunk,
+                                          unsigned long long* d_counts);
+// threshold selection over ANY number of rows (k_occurrences_batch.hip): launch_threshold_keys' results -- per row of n scores the
+// keys of the entries whose score is >= threshold in ascending entry index, the first min(count, capacity) of them to d_keys + r *
+// capacity, the true count to d_counts[r] -- through the joins' scans with a row per recording.  The caller has zeroed the keys.
+// d_scratch: threshold_batch_scratch_bytes(n, rows) bytes, written before they are read; four launches, whatever the rows.
+// rows <= 65 535, rows x capacity <= 2^31, index_base + n <= 2^32.
+size_t threshold_batch_scratch_bytes(uint64_t entries, uint32_t rows);
+hipError_t launch_threshold_batch_keys(const float* d_scores, uint64_t n, uint32_t rows, float threshold, uint64_t capacity,
+                                       uint64_t index_base, void* d_scratch, unsigned long long* d_keys, unsigned long long* d_counts,
+                                       hipStream_t stream);
+
 // recording segments (k_segments.hip): per recording the non-overlapping spans of a timeline's winners -- d_keys and d_lengths as
 // the timeline calls write them, [recordings][per], per <= LBAD_SEGMENTS_MAX_SUBFINGERPRINTS, both products with `recordings`
 // below 2^31 -- greedy in descending key order (ties to the lower offset), in start order to the rows of `capacity` slots of

@@ -238,7 +238,9 @@ OSStatus query_fast_impl(LBAudioDetectiveCorpus* c, const LBAudioDetectiveFinger
         unsigned long long* h_out_dev = nullptr;
         OSStatus st = c->stream ? noErr : kLBAudioDetectiveDeviceError;     // created with the corpus
         if (st == noErr) st = d_fast.reserve(kScanSlots + 1);
-        if (st == noErr) st = hip_status(hipMemset(d_fast, 0, (kScanSlots + 1) * sizeof(unsigned long long)), "memset", __LINE__);
+        // on the query's own stream: hipMemset returns before the fill is done and the null stream does not order a
+        // non-blocking one, so a fill there could land among the first scan's ticket adds (no last workgroup, no answer)
+        if (st == noErr) st = hip_status(hipMemsetAsync(d_fast, 0, (kScanSlots + 1) * sizeof(unsigned long long), c->stream), "memset", __LINE__);
         if (st == noErr) st = h_out.reserve(2, hipHostMallocMapped | hipHostMallocCoherent);
         if (st == noErr) {
             h_out[0] = h_out[1] = 0;

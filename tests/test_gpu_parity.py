@@ -1234,7 +1234,7 @@ def test_polled_query_sees_appends_from_other_streams(lb, gpu, oracle):
 @pytest.mark.gpu
 @pytest.mark.parametrize("tool,trials", [("fuzz_parity.py", 250), ("fuzz_compare.py", 120), ("fuzz_frame.py", 400),
                                          ("fuzz_stream.py", 120), ("fuzz_files.py", 300), ("fuzz_ragged.py", 400),
-                                         ("fuzz_stage2.py", 600), ("fuzz_recording.py", 200)])
+                                         ("fuzz_stage2.py", 600), ("fuzz_recording.py", 200), ("fuzz_corpus.py", 400)])
 def test_randomized_sweeps(tool, trials):
     """Each sweep compares the device path with the oracle on inputs nobody picked by hand and exits non-zero on the
     first kind of mismatch: fingerprint configurations and shapes (all stage-1 / stage-2 kernels, the file loop), the
@@ -1242,7 +1242,9 @@ def test_randomized_sweeps(tool, trials):
     and converter (against the oracle's own file front end), ragged corpora (every mode of the sliding scan, save / load,
     the sharded entry point), stage 2 alone on frames of extreme magnitudes (the tiers of the division shortcut), the recording
     family (occurrences, recording scores / top-K / threshold, timeline and segments, single and batch, against
-    tests/recording_ref.py with several axes of the plans drawn at once)."""
+    tests/recording_ref.py with several axes of the plans drawn at once), the corpus queries and maintenance (histories of
+    appends, removals, dedup, ids and save / load on one handle, every read after every step against the numpy model corpus of
+    tests/corpus_ref.py)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1066,6 +1066,56 @@ OSStatus LBAudioDetectiveDebugOccurrencesBatchPlan(UInt32 inRecordings, UInt32 i
                                                    UInt64* outTiles, UInt32* outRecordingsPerPass, UInt64* outEntriesPerChunk,
                                                    UInt64* outScratchBytes, UInt64* outLdsBytes);
 OSStatus LBAudioDetectiveDebugSetOccurrencesBatchForm(UInt32 inForceShared);
+/* Live occurrences: of the batch occurrences above only the cells a push has COMPLETED, for a monitor that asks after every push
+ * and wants each match once.  inPackedQueries, outKeys, outLags (may be NULL) and outCounts are exactly
+ * LBAudioDetectiveCorpusQueryPackedOccurrencesBatchKeysDevice's, on the DEVICE: inRecordings recordings of inSubfingerprints packed
+ * sub-fingerprints each, keys and lags [inRecordings][inCapacity], counts UInt64 [inRecordings]; every word is written.
+ * inNewCounts is on the DEVICE too: UInt32 [inRecordings], 4-byte aligned, read on the stream -- how many of recording r's
+ * sub-fingerprints are new since the caller last asked (what a stream bank's push returned).  Recording r uses d_r =
+ * min(inNewCounts[r], inMaxNew, inSubfingerprints).  inMaxNew is the HOST's bound, 1 <= inMaxNew <= LBAD_OCCURRENCES_TAIL_MAX_NEW:
+ * it sizes the launch, and a device value above it counts as inMaxNew -- a caller whose push may complete more keeps the bound
+ * at least that large, or the cells behind the newest inMaxNew are never reported.
+ * Entry j of n_j sub-fingerprints takes part when n_j <= inSubfingerprints (the recording is fingerprint1, equal lengths included:
+ * the timeline's rule); a longer entry has no complete position inside the recording and is skipped.  The cells of (r, j) are the
+ * offsets o with max(0, inSubfingerprints - n_j - d_r + 1) <= o <= inSubfingerprints - n_j: the positions at which the entry ENDS
+ * inside the newest d_r sub-fingerprints; d_r == 0: none.  A cell's value is q_o of LBAudioDetectiveCorpusMatchProfile, bit for
+ * bit; it matches when q_o >= inThreshold as Float32.  There is NO peak rule: a newest cell's right neighbour does not exist yet.
+ * Row r is, bit for bit, row r of the batch occurrences call with inPeaksOnly = 0 and the same other arguments with only those
+ * cells kept: keys q_o bits << 32 | 0xFFFFFFFF - (inIndexBase + j), lags -o, in (entry ascending, offset ascending) order, zero
+ * keys and lags 0 behind min(count, inCapacity); outCounts[r] is the TRUE number of matching cells, never cut; a row that
+ * overflows writes nothing into its neighbours, and no sub-fingerprint of recording r +- 1 enters a cell of r.  Shards merge per
+ * recording by concatenation, as the batch occurrences do.
+ * EXACTLY ONCE: a cell's value depends only on the entry and the n_j sub-fingerprints under it.  So for a channel fed in pushes of
+ * d_1, d_2, ... whose window at call k is at least (longest entry + d_k - 1) long, the cells of all calls moved to absolute
+ * positions (total - inSubfingerprints + o) are the cells of ONE occurrences call (peaks off) over the whole recording, for the
+ * entries not longer than the windows: each appears in exactly one call, with equal key bits.
+ * Refusals in the batch call's order: what needs no handle first (a NULL pointer other than outLags, inNewCounts not 4-byte aligned,
+ * inMaxNew 0 or above the cap, and the batch call's own argument checks), then kLBAudioDetectiveDeviceUnavailable, then what needs
+ * the corpus (ragged, no entry above LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS, the sub-fingerprint length, a scratch limit --
+ * LBAudioDetectiveCorpusSetJoinScratchLimit -- below one block of 64 entries for ONE recording).  An empty corpus, or one with no
+ * entry that takes part, is noErr with zero keys, lags and counts.
+ * Asynchronous on inStream, which it never awaits; it waits ON THE DEVICE for the corpus' latest append; nothing visits the host.
+ * Results do not depend on launch order, grid, chunking, passes or outLags.  The work is proportional to d x the entries' summed
+ * lengths, not to the window.
+ * LBAudioDetectiveDebugOccurrencesTailPlan is the call's plan on the host -- the call takes its own from the same function --; it
+ * needs neither device nor handle: from the shape of a call (inShortestEntry <= inLongestEntry <= the cap; inScratchLimit 0: the
+ * default) the lanes per recording D (the next power of two >= inMaxNew), the recordings per workgroup (256 / D, fewer where that
+ * many windows do not fit the LDS), the records of a recording's LDS window (min(inSubfingerprints, min(longest entry,
+ * inSubfingerprints) + D - 1)), the LDS of a workgroup (recordings x window x 36 bytes + the 20 604-byte table, at most 160 KiB - 64),
+ * the recordings per pass, the entries per chunk and the scratch of a pass (the occurrences' formula with one tile, per recording;
+ * at most 65 535 recordings a pass; one recording per pass in entry chunks when a whole corpus' scratch does not fit);
+ * kLBAudioDetectiveArgumentInvalid for a shape the call refuses, a limit that is too small or a NULL pointer. */
+#define LBAD_OCCURRENCES_TAIL_MAX_NEW 64
+OSStatus LBAudioDetectiveCorpusQueryPackedOccurrencesTailBatchKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                                         UInt32 inRecordings, UInt32 inSubfingerprints,
+                                                                         const void* inNewCounts, UInt32 inMaxNew, UInt32 inRange,
+                                                                         Float32 inThreshold, UInt64 inCapacity, UInt64 inIndexBase,
+                                                                         void* outKeys, void* outLags, void* outCounts, void* inStream);
+OSStatus LBAudioDetectiveDebugOccurrencesTailPlan(UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inShortestEntry,
+                                                  UInt32 inLongestEntry, UInt64 inEntries, UInt32 inMaxNew, UInt64 inScratchLimit,
+                                                  UInt32* outLanes, UInt32* outRecordingsPerWorkgroup, UInt32* outWindowRecords,
+                                                  UInt64* outLdsBytes, UInt32* outRecordingsPerPass, UInt64* outEntriesPerChunk,
+                                                  UInt64* outScratchBytes);
 /* Recording segments: "what played when" from a timeline's per-offset winners, on the device -- non-overlapping spans per
  * recording, for one recording (inRecordings == 1) or a batch.  inKeys ([inRecordings][inSubfingerprints] UInt64) and inLengths
  * (the same shape, UInt32) are what LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice or the single timeline calls

@@ -257,6 +257,11 @@ _SIGNATURES = {
     "LBAudioDetectiveDebugOccurrencesBatchPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, UInt64, UInt64, _P(UInt32), _P(UInt64),
                                                              _P(UInt32), _P(UInt64), _P(UInt64), _P(UInt64)]),
     "LBAudioDetectiveDebugSetOccurrencesBatchForm": (OSStatus, [UInt32]),
+    "LBAudioDetectiveCorpusQueryPackedOccurrencesTailBatchKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, C.c_void_p, UInt32, UInt32,
+                                                                                   Float32, UInt64, UInt64, C.c_void_p, C.c_void_p,
+                                                                                   C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveDebugOccurrencesTailPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, UInt64, UInt32, UInt64, _P(UInt32), _P(UInt32),
+                                                            _P(UInt32), _P(UInt64), _P(UInt32), _P(UInt64), _P(UInt64)]),
     "LBAudioDetectiveTimelineSegmentsFromKeysDevice": (OSStatus, [C.c_void_p, C.c_void_p, UInt32, UInt32, UInt32, C.c_void_p, C.c_void_p,
                                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusRemoveIndices":(OSStatus, [Ref, _P(UInt64), UInt64, _P(UInt32), _P(UInt64)]),

@@ -698,6 +698,23 @@ class StreamBank:
                                                                  range_=range_, index_base=index_base, want_lags=want_lags,
                                                                  stream=stream)
 
+    def new_occurrences(self, corpus: "Corpus", channels, n: int, new_counts, threshold: float, capacity: int, max_new: int = None,
+                        range_: int = 0, index_base: int = 0, want_lags: bool = True, stream=None):
+        """The matches the latest push completed on every listed channel: window_device, then
+        Corpus.query_packed_occurrences_tail_batch_keys_device on its output, on ONE stream with nothing in between.  new_counts:
+        what push / push_device returned (one value per channel of the BANK; the listed channels' are taken), or a device tensor
+        with one value per LISTED channel (max_new required).  Returns (keys int64 [len(channels), capacity], lags int32 of the
+        same shape or None, counts int64 [len(channels)]): per channel the cells at or above `threshold` whose entry ends inside
+        the channel's new sub-fingerprints, in (entry, offset) order -- each match once in a channel's life as long as n >=
+        the longest entry + the push's new sub-fingerprints - 1.  Decode with decode_tail_occurrences and totals()."""
+        if not hasattr(new_counts, "data_ptr"):
+            ch, _ = _u32_list(channels)
+            new_counts = np.asarray(new_counts).reshape(-1)[ch]
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.query_packed_occurrences_tail_batch_keys_device(packed, packed.shape[0], n, new_counts, threshold, capacity,
+                                                                      max_new=max_new, range_=range_, index_base=index_base,
+                                                                      want_lags=want_lags, stream=stream)
+
     def matches_above(self, corpus: "Corpus", channels, n: int, threshold: float, capacity: int, range_: int = 0, index_base: int = 0,
                       want_lags: bool = True, stream=None):
         """Every entry the window of every listed channel matches at or above `threshold`: window_device, then
@@ -1463,6 +1480,44 @@ class Corpus:
             lambda R, per, cap, kp, lp, cp, sp: self._L.LBAudioDetectiveCorpusQueryPackedRecordingThresholdBatchKeysDevice(
                 self._ref, _dev_ptr(packed), R, per, range_, threshold, cap, index_base, kp, cp, lp, sp))
 
+    def query_packed_occurrences_tail_batch_keys_device(self, packed, n_recordings: int, per_query: int, new_counts, threshold: float,
+                                                        capacity: int, max_new: int = None, range_: int = 0, index_base: int = 0,
+                                                        keys_out=None, lags_out=None, counts_out=None, want_lags: bool = True,
+                                                        stream=None):
+        """LBAudioDetectiveCorpusQueryPackedOccurrencesTailBatchKeysDevice: of query_packed_occurrences_batch_keys_device (peaks off)
+        only the cells a push has completed -- per recording r those whose entry ends inside its newest d_r = min(new_counts[r],
+        max_new, per_query) sub-fingerprints, for the entries not longer than per_query -> (keys int64 [n_recordings, capacity],
+        lags int32 of the same shape or None, counts int64 [n_recordings]) on the device, asynchronously on `stream`.  Row r is
+        the batch call's row r with only those cells kept, bit for bit; each match of a channel's life is reported once, by the
+        call behind the push that completes it.  new_counts: a device uint32 / int32 tensor of n_recordings values (max_new is
+        then required: the host's bound, 1 .. 64, which a device value above it is cut to), or a host sequence, uploaded on
+        `stream` (max_new defaults to its maximum, at least 1).  Decode with decode_tail_occurrences."""
+        R = int(n_recordings)
+        if hasattr(new_counts, "data_ptr"):
+            import torch
+            if max_new is None:
+                raise ValueError("max_new is required with new counts on the device")
+            if (not new_counts.is_cuda or not new_counts.is_contiguous() or new_counts.dtype not in (torch.int32, torch.uint32) or
+                    new_counts.numel() < R):
+                raise ValueError("new_counts must be a contiguous device tensor of at least n_recordings uint32 or int32 values")
+            d_new = new_counts
+        else:
+            import torch
+            host = np.ascontiguousarray(np.asarray(new_counts).reshape(-1), dtype=np.int64)
+            if host.size != R or (host.size and (host.min() < 0 or host.max() > 0xFFFFFFFF)):
+                raise ValueError("new_counts must hold one value of 0 .. 2^32 - 1 per recording")
+            if max_new is None:
+                max_new = max(1, int(host.max()) if host.size else 1)
+            dev = packed.device if hasattr(packed, "device") else "cuda"
+            with torch.cuda.stream(stream):              # (uploaded on the stream that reads it)
+                d_new = torch.from_numpy(host.astype(np.uint32).view(np.int32)).to(dev, non_blocking=False)
+        max_new = int(max_new)
+        return self._batch_threshold_call(
+            "CorpusQueryPackedOccurrencesTailBatchKeysDevice", packed, n_recordings, per_query, capacity, keys_out, lags_out, counts_out,
+            want_lags, stream,
+            lambda R, per, cap, kp, lp, cp, sp: self._L.LBAudioDetectiveCorpusQueryPackedOccurrencesTailBatchKeysDevice(
+                self._ref, _dev_ptr(packed), R, per, _dev_ptr(d_new), max_new, range_, threshold, cap, index_base, kp, lp, cp, sp))
+
     # ---- recording timeline: the best entry at every offset of ONE query (a long recording) against a ragged corpus -- the
     # occurrences cells folded per offset over the entries not longer than the query.  One key per sub-fingerprint of the query,
     # whatever the corpus size.  Shards of contiguous index ranges merge by the element-wise maximum of their keys AS UNSIGNED
@@ -2051,6 +2106,22 @@ def debug_set_occurrences_batch_form(force_shared: bool) -> None:
     calls' switches are others.  Results never depend on it."""
     _check(N.lib().LBAudioDetectiveDebugSetOccurrencesBatchForm(1 if force_shared else 0), "DebugSetOccurrencesBatchForm")
 
+
+def debug_occurrences_tail_plan(n_recordings: int, per_query: int, shortest_entry: int, longest_entry: int, entries: int, max_new: int,
+                                scratch_limit: int = 0) -> dict:
+    """LBAudioDetectiveDebugOccurrencesTailPlan: the host plan of one tail occurrences call -- the one the call itself takes -- as
+    a dict: lanes per recording, recordings_per_workgroup, window_records of a recording in LDS, lds_bytes of a workgroup,
+    recordings_per_pass, entries_per_chunk, scratch_bytes of a pass.  scratch_limit 0: the default.  Raises for a shape or limit
+    the call refuses.  Needs no GPU."""
+    lanes, rpw, win, rpp = N.UInt32(0), N.UInt32(0), N.UInt32(0), N.UInt32(0)
+    lds, chunk, scratch = N.UInt64(0), N.UInt64(0), N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveDebugOccurrencesTailPlan(int(n_recordings), int(per_query), int(shortest_entry), int(longest_entry),
+                                                            int(entries), int(max_new), int(scratch_limit), C.byref(lanes), C.byref(rpw),
+                                                            C.byref(win), C.byref(lds), C.byref(rpp), C.byref(chunk), C.byref(scratch)),
+           "DebugOccurrencesTailPlan")
+    return {"lanes": lanes.value, "recordings_per_workgroup": rpw.value, "window_records": win.value, "lds_bytes": lds.value,
+            "recordings_per_pass": rpp.value, "entries_per_chunk": chunk.value, "scratch_bytes": scratch.value}
+
 class Comm:
     """An RCCL communicator made through the library's helpers (ncclCommInitRank with the current device).
     `unique_id()` on rank 0, the 128 bytes travel to the other ranks by whatever means the host has, then every
@@ -2190,6 +2261,27 @@ def decode_occurrence_keys(keys, lags=None, count=None):
     if lags is not None:
         lg = np.asarray(lags.cpu().numpy() if hasattr(lags, "cpu") else lags, dtype=np.int32).reshape(-1)[:m].copy()
     return ((0xFFFFFFFF - (k & np.uint64(0xFFFFFFFF))).astype(np.int64), (k >> np.uint64(32)).astype(np.uint32).view(np.float32), lg)
+
+
+def decode_tail_occurrences(keys, lags, counts, totals, n: int, index_base: int = 0):
+    """The rows of a tail occurrences call (Corpus.query_packed_occurrences_tail_batch_keys_device, StreamBank.new_occurrences) as a
+    list with one (indices int64[m], scores float32[m], starts int64[m]) per recording, m = min(counts[r], capacity): the entry's
+    index (global minus index_base), the cell's score and the ABSOLUTE sub-fingerprint at which the match starts in the
+    recording's life, totals[r] - n - lag, with totals[r] the recording's sub-fingerprints so far (StreamBank.totals() of the
+    listed channels) and n the call's window.  keys / lags: [recordings, capacity], any int sequence or device tensor."""
+    k = np.asarray(keys.cpu().numpy() if hasattr(keys, "cpu") else keys, dtype=np.int64)
+    lg = np.asarray(lags.cpu().numpy() if hasattr(lags, "cpu") else lags, dtype=np.int32)
+    cn = np.asarray(counts.cpu().numpy() if hasattr(counts, "cpu") else counts).reshape(-1).astype(np.int64)
+    tt = np.asarray(totals).reshape(-1).astype(np.int64)
+    k = k.reshape(cn.size, -1)
+    lg = lg.reshape(cn.size, -1)
+    if tt.size != cn.size:
+        raise ValueError("totals must have one value per recording")
+    rows = []
+    for r in range(cn.size):
+        idx, sc, lag = decode_occurrence_keys(k[r], lg[r], cn[r])
+        rows.append((idx - int(index_base), sc, tt[r] - int(n) - lag.astype(np.int64)))
+    return rows
 
 
 def decode_timeline_keys(keys, lengths=None, index_base: int = 0):

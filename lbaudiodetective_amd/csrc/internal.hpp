@@ -563,6 +563,33 @@ bool occurrences_batch_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, 
 hipError_t launch_occurrences_batch_chunk(const OccurrencesCall& call, const OccurrencesBatchPlan& plan, uint32_t recordings,
                                           void* d_scratch, uint64_t first_entry, uint64_t entries, uint32_t first_chunk,
                                           unsigned long long* d_counts);
+// tail occurrences (k_occurrences_tail.hip): the batch occurrences' rows with only the cells whose entry ends inside a recording's
+// newest d_r = min(new count on the device, max_new, n_query) sub-fingerprints, for the entries not longer than the recording; no
+// peak rule.  A call runs in passes over recordings and, within a pass of ONE recording, in chunks over entries.
+struct OccurrencesTailPlan {
+    uint32_t lanes = 0;                  // D: the next power of two >= max_new, the lanes of a recording
+    uint32_t recordings_per_workgroup = 0;   // 256 / D, fewer where that many sub-windows do not fit the LDS (at least 1)
+    uint32_t window_records = 0;         // a recording's sub-window: min(n_query, min(ne_max, n_query) + D - 1)
+    uint64_t lds_bytes = 0;              // recordings_per_workgroup x window_records x 36 + the table
+    uint32_t recordings_per_pass = 0;
+    uint64_t entries_per_chunk = 0;      // a multiple of occurrences_block_entries(), or the corpus rounded up to one (0: empty corpus)
+    uint64_t scratch_bytes = 0;          // recordings_per_pass x occurrences_scratch_bytes(entries_per_chunk, 1)
+};
+// the four fields a workgroup's shape is (plan.cpp): what the launch holds the plan against
+void occurrences_tail_shape(uint32_t per, uint32_t ne_max, uint32_t max_new, OccurrencesTailPlan* plan);
+// THE plan of a call, the debug symbol's and the real call's (plan.cpp): the shape above; several recordings a pass when one
+// recording's scratch for the whole corpus (the occurrences' formula with ONE tile) fits the limit (0: kJoinScratchDefault) -- the
+// smallest of the recordings, limit / that scratch, kOcMaxItems / entries and 65 535 -- else one recording a pass in entry chunks
+// with the carried total.  false: the limit holds no block of entries of one recording.  1 <= max_new <= 64.
+bool occurrences_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uint32_t ne_max, uint64_t entries, uint32_t max_new,
+                           uint64_t limit_bytes, OccurrencesTailPlan* plan);
+// one chunk of one pass: `recordings` recordings from call.d_qwords on with their new counts from d_new_counts on, `entries` entries
+// from `first_entry`; call.tiles == 1, call.peaks unused; keys, lags, counts, scratch and chunks as launch_occurrences_batch_chunk.
+// Four or five launches on the call's stream, nothing visits the host.
+hipError_t launch_occurrences_tail_chunk(const OccurrencesCall& call, const OccurrencesTailPlan& plan, uint32_t recordings,
+                                         const uint32_t* d_new_counts, uint32_t max_new, void* d_scratch, uint64_t first_entry,
+                                         uint64_t entries, uint32_t first_chunk, unsigned long long* d_counts);
+
 // threshold selection over ANY number of rows (k_occurrences_batch.hip): launch_threshold_keys' results -- per row of n scores the
 // keys of the entries whose score is >= threshold in ascending entry index, the first min(count, capacity) of them to d_keys + r *
 // capacity, the true count to d_counts[r] -- through the joins' scans with a row per recording.  The caller has zeroed the keys.

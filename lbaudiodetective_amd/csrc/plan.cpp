@@ -1,5 +1,5 @@
 // plan.cpp -- host-side tables of the fingerprint path (double precision, computed once per
-// configuration instead of once per window as LBAudioDetective.m:361-371 does).
+// configuration instead of once per window as LBAudioDetective.m:361-371 does), and the tail occurrences' plan.
 #include "internal.hpp"
 
 #include <cmath>
@@ -202,6 +202,58 @@ void plan_sparse(Plan& plan) {
     if (sp.n_stored == 0) return;
     sp.ok = true;
     plan.sparse = sp;
+}
+
+// The tail occurrences' plan (k_occurrences_tail.hip; internal.hpp states it): the ONE place that decides the lanes of a recording,
+// the recordings of a workgroup, the sub-window, the LDS, the passes, the chunks and the scratch.
+namespace {
+constexpr uint64_t kTailLdsBudget = 160 * 1024 - 64;       // a CU's LDS less 64 bytes, as the pair loop's windows
+constexpr uint64_t kTailTableBytes = 5151 * 4;             // the table of quotients (sliding_common.hpp: kTriSize floats)
+constexpr uint64_t kTailRecBytes = 36;                     // a prepared record in LDS: P, N, the row
+constexpr uint32_t kTailThreads = 256;
+constexpr uint64_t kTailMaxRecs = 65535;                   // recordings of a pass
+constexpr uint64_t kTailMaxItems = 0xFFFFFFFFull - 4096;   // recordings x entries of a pass: 32-bit indices (kOcMaxItems)
+static_assert((uint64_t)(LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS + LBAD_OCCURRENCES_TAIL_MAX_NEW - 1) * kTailRecBytes + kTailTableBytes <=
+                  kTailLdsBudget,
+              "one recording's longest sub-window and the table fit a CU's LDS");
+}  // namespace
+
+void occurrences_tail_shape(uint32_t per, uint32_t ne_max, uint32_t max_new, OccurrencesTailPlan* plan) {
+    uint32_t lanes = 1;
+    while (lanes < max_new) lanes <<= 1;
+    const uint32_t ne_b = ne_max < per ? ne_max : per;
+    const uint64_t win = (uint64_t)ne_b + lanes - 1 < per ? ne_b + lanes - 1 : per;
+    uint64_t fit = kTailThreads / lanes;
+    if (win != 0 && (kTailLdsBudget - kTailTableBytes) / (win * kTailRecBytes) < fit) fit = (kTailLdsBudget - kTailTableBytes) / (win * kTailRecBytes);
+    plan->lanes = lanes;
+    plan->recordings_per_workgroup = (uint32_t)fit;
+    plan->window_records = (uint32_t)win;
+    plan->lds_bytes = fit * win * kTailRecBytes + kTailTableBytes;
+}
+
+bool occurrences_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uint32_t ne_max, uint64_t entries, uint32_t max_new,
+                           uint64_t limit_bytes, OccurrencesTailPlan* plan) {
+    *plan = OccurrencesTailPlan();
+    occurrences_tail_shape(per, ne_max, max_new, plan);
+    plan->recordings_per_pass = recordings;
+    if (entries == 0) return true;
+    const uint64_t limit = limit_bytes ? limit_bytes : kJoinScratchDefault;
+    const uint64_t fit = occurrences_chunk_entries(1, limit);
+    if (fit == 0) return false;                                // the limit holds no block of entries of ONE recording
+    const uint64_t block = occurrences_block_entries();
+    const uint64_t chunk = fit < entries ? fit : (entries + block - 1) / block * block;
+    const uint64_t one = occurrences_scratch_bytes(chunk, 1);
+    uint64_t recs = 1;
+    if (chunk >= entries) {                                    // one recording's whole-corpus scratch fits: several recordings a pass
+        recs = limit / one;
+        if (recs > kTailMaxItems / entries) recs = kTailMaxItems / entries;    // (>= 1: occurrences_chunk_entries kept the chunk within it)
+        if (recs > kTailMaxRecs) recs = kTailMaxRecs;
+        if (recs > recordings) recs = recordings;
+    }
+    plan->recordings_per_pass = (uint32_t)recs;
+    plan->entries_per_chunk = chunk;
+    plan->scratch_bytes = recs * one;
+    return true;
 }
 
 }  // namespace lbad

@@ -1116,6 +1116,67 @@ OSStatus LBAudioDetectiveDebugOccurrencesTailPlan(UInt32 inRecordings, UInt32 in
                                                   UInt32* outLanes, UInt32* outRecordingsPerWorkgroup, UInt32* outWindowRecords,
                                                   UInt64* outLdsBytes, UInt32* outRecordingsPerPass, UInt64* outEntriesPerChunk,
                                                   UInt64* outScratchBytes);
+/* Live best matches: the cells of the tail occurrences call above folded to ONE value per (recording, entry) -- which entries a
+ * push completed on each channel, as per-entry scores, as the K best, or as all at or above a score -- in a fixed output shape.
+ * Cells, d_r, the entries that take part and a cell's value are EXACTLY those of
+ * LBAudioDetectiveCorpusQueryPackedOccurrencesTailBatchKeysDevice; inPackedQueries, inRecordings, inSubfingerprints, inNewCounts
+ * (DEVICE, UInt32 [inRecordings], 4-byte aligned), inMaxNew (1 .. LBAD_OCCURRENCES_TAIL_MAX_NEW), inRange and inStream are its.  For
+ * recording r and entry j:
+ *   score[r][j] = max(+0, the largest q_o over the tail cells of (r, j)) as Float32; +0 when the pair has no tail cell (d_r == 0,
+ *                 n_j == 0, or n_j > inSubfingerprints);
+ *   lag[r][j]   = -(the LOWEST tail offset whose q_o equals the score); 0 when no tail cell equals it.
+ * ...RecordingPackedScoresTailBatchDevice writes both as [inRecordings][entries] on the device (outLags may be NULL); every word
+ * is written, an empty corpus writes nothing; inRecordings x entries <= 2^31 - 1.
+ * ...QueryPackedRecordingTopKTailBatchKeysDevice: outKeys [inRecordings][inK] UInt64, outLags the same shape SInt32 or NULL.  Row r
+ * is the batch recording top-K's selection over row r of the scores: the entries with score > 0, keys score bits << 32 | 0xFFFFFFFF
+ * - (inIndexBase + j) descending (so the lowest index first among equal scores), zero keys behind them, each key's lag beside
+ * it and lag 0 for a zero key.  1 <= inK <= LBAD_TOPK_MAX, inRecordings x inK <= 2^31.
+ * ...QueryPackedRecordingThresholdTailBatchKeysDevice: outKeys [inRecordings][inCapacity], outCounts UInt64 [inRecordings], outLags
+ * or NULL.  Row r is the batch recording threshold's selection over row r of the scores: the entries with score >= inThreshold
+ * in ascending index, outCounts[r] the TRUE count, zero keys behind min(count, inCapacity), lag 0 for a zero key.  Threshold
+ * (finite, > 0) and capacity (1 .. 2^31, inRecordings x inCapacity <= 2^31) are the batch call's.
+ * What follows from this:
+ * EQUIVALENCE with the tail occurrences call: the threshold call's row r names exactly the DISTINCT entries of row r of the tail
+ * occurrences call at the same threshold (while that row is not cut), each with the key of its largest cell and the lag of the
+ * lowest offset that reaches it.
+ * ONCE PER PUSH: a (channel, entry) pair is reported at most once per push, and only by the push that completes its best new
+ * cell.  Under the tail occurrences' window condition (window >= longest entry + d_k - 1) the union over a channel's pushes of
+ * (entry, absolute start = total - inSubfingerprints - lag) is a subset of the whole recording's occurrences' cells and holds, for
+ * every push and entry, that push's best cell.
+ * INDEPENDENCE: results do not depend on launch order, grid, passes, outLags, or inMaxNew beyond the clamp.
+ * Refusals in the tail occurrences call's order: what needs no handle first (a NULL pointer other than outLags, inNewCounts not
+ * 4-byte aligned, inMaxNew 0 or above the cap, inK, inThreshold, inCapacity, inIndexBase and the products above), then
+ * kLBAudioDetectiveDeviceUnavailable, then what needs the corpus (as the tail occurrences call).  An empty corpus, or one with no
+ * entry that takes part, is noErr with zero keys, lags and counts; the scores form writes +0 scores and 0 lags when entries exist
+ * but none takes part.
+ * Asynchronous on inStream, which they never await; they wait ON THE DEVICE for the corpus' latest append; nothing visits the host.
+ * One compute launch per pass (k_recording_tail.hip: no counts, no scans, no scatter), then the selection.
+ * LBAudioDetectiveDebugRecordingTailPlan is the calls' plan on the host -- they take theirs from the same function --; it needs
+ * neither device nor handle: the lanes per recording, the recordings per workgroup, the records of a recording's LDS window and
+ * the LDS of a workgroup exactly as LBAudioDetectiveDebugOccurrencesTailPlan gives them; the recordings per pass -- all entries
+ * in one launch, at most 65 535 recordings, blocks of 64 entries x recordings within 32 bits, and with inKeyForm != 0 at most
+ * max(1, limit / (entries x 8)), the score and lag rows the selection reads (inScratchLimit 0: the default) --; and the scratch
+ * of a pass (those rows: recordings per pass x entries x 8 bytes; 0 without inKeyForm).  kLBAudioDetectiveArgumentInvalid for a
+ * shape the call refuses or a NULL pointer. */
+OSStatus LBAudioDetectiveCorpusRecordingPackedScoresTailBatchDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                                    UInt32 inRecordings, UInt32 inSubfingerprints, const void* inNewCounts,
+                                                                    UInt32 inMaxNew, UInt32 inRange, Float32* outScores, SInt32* outLags,
+                                                                    void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryPackedRecordingTopKTailBatchKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                                           UInt32 inRecordings, UInt32 inSubfingerprints,
+                                                                           const void* inNewCounts, UInt32 inMaxNew, UInt32 inRange,
+                                                                           UInt32 inK, UInt64 inIndexBase, void* outKeys, void* outLags,
+                                                                           void* inStream);
+OSStatus LBAudioDetectiveCorpusQueryPackedRecordingThresholdTailBatchKeysDevice(LBAudioDetectiveCorpusRef inCorpus,
+                                                                                const void* inPackedQueries, UInt32 inRecordings,
+                                                                                UInt32 inSubfingerprints, const void* inNewCounts,
+                                                                                UInt32 inMaxNew, UInt32 inRange, Float32 inThreshold,
+                                                                                UInt64 inCapacity, UInt64 inIndexBase, void* outKeys,
+                                                                                void* outCounts, void* outLags, void* inStream);
+OSStatus LBAudioDetectiveDebugRecordingTailPlan(UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inLongestEntry, UInt64 inEntries,
+                                                UInt32 inMaxNew, UInt64 inScratchLimit, UInt32 inKeyForm, UInt32* outLanes,
+                                                UInt32* outRecordingsPerWorkgroup, UInt32* outWindowRecords, UInt64* outLdsBytes,
+                                                UInt32* outRecordingsPerPass, UInt64* outScratchBytes);
 /* Recording segments: "what played when" from a timeline's per-offset winners, on the device -- non-overlapping spans per
  * recording, for one recording (inRecordings == 1) or a batch.  inKeys ([inRecordings][inSubfingerprints] UInt64) and inLengths
  * (the same shape, UInt32) are what LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice or the single timeline calls

@@ -13,7 +13,7 @@ from .api import (  # noqa: F401
     group_labels_from_keys_device, group_extra_keys_from_labels_device, decode_timeline_keys, timeline_segments,
     decode_timeline_batch_keys, debug_timeline_batch_plan, debug_set_timeline_batch_form, timeline_segments_device, decode_segments,
     debug_recording_batch_plan, debug_set_recording_batch_form, debug_occurrences_batch_plan, debug_set_occurrences_batch_form,
-    debug_occurrences_tail_plan, decode_tail_occurrences,
+    debug_occurrences_tail_plan, decode_tail_occurrences, debug_recording_tail_plan, decode_tail_matches,
 )
 from .sharded import (  # noqa: F401
     ShardedCorpus, broadcast_fingerprint, gather_packed, gather_topk_aligned, make_comm, merge_topk_aligned, merge_topk_keys, shard_range,
@@ -31,4 +31,5 @@ __all__ = [
     "debug_resampler_bank_plan", "decode_timeline_batch_keys", "debug_timeline_batch_plan", "debug_set_timeline_batch_form",
     "timeline_segments_device", "decode_segments", "debug_recording_batch_plan", "debug_set_recording_batch_form",
     "debug_occurrences_batch_plan", "debug_set_occurrences_batch_form", "debug_occurrences_tail_plan", "decode_tail_occurrences",
+    "debug_recording_tail_plan", "decode_tail_matches",
 ]

@@ -715,6 +715,36 @@ class StreamBank:
                                                                       max_new=max_new, range_=range_, index_base=index_base,
                                                                       want_lags=want_lags, stream=stream)
 
+    def new_best(self, corpus: "Corpus", channels, n: int, new_counts, k: int = 1, max_new: int = None, aligned: bool = True,
+                 range_: int = 0, index_base: int = 0, stream=None):
+        """The k best entries the latest push completed on every listed channel: window_device, then
+        Corpus.query_packed_recording_topk_tail_batch_keys_device on its output, on ONE stream with nothing in between.
+        new_counts as new_occurrences takes them.  Returns (keys int64 [len(channels), k], lags int32 of the same shape) -- the
+        keys alone with aligned=False --: per channel the entries whose best NEW cell scores above 0, best first, zeros behind
+        them; an entry is reported at most once per push.  Decode with decode_tail_matches and totals()."""
+        if not hasattr(new_counts, "data_ptr"):
+            ch, _ = _u32_list(channels)
+            new_counts = np.asarray(new_counts).reshape(-1)[ch]
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.query_packed_recording_topk_tail_batch_keys_device(packed, packed.shape[0], n, new_counts, k, max_new=max_new,
+                                                                         range_=range_, index_base=index_base, aligned=aligned,
+                                                                         stream=stream)
+
+    def new_matches_above(self, corpus: "Corpus", channels, n: int, new_counts, threshold: float, capacity: int, max_new: int = None,
+                          range_: int = 0, index_base: int = 0, want_lags: bool = True, stream=None):
+        """Every entry the latest push completed at or above `threshold` on every listed channel: window_device, then
+        Corpus.query_packed_recording_threshold_tail_batch_keys_device on its output, on ONE stream with nothing in between.
+        new_counts as new_occurrences takes them.  Returns (keys int64 [len(channels), capacity], lags int32 of the same shape or
+        None, counts int64 [len(channels)]): per channel the distinct entries of new_occurrences' row in ascending index, each
+        once with its best new cell.  Decode with decode_tail_matches and totals()."""
+        if not hasattr(new_counts, "data_ptr"):
+            ch, _ = _u32_list(channels)
+            new_counts = np.asarray(new_counts).reshape(-1)[ch]
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.query_packed_recording_threshold_tail_batch_keys_device(packed, packed.shape[0], n, new_counts, threshold, capacity,
+                                                                              max_new=max_new, range_=range_, index_base=index_base,
+                                                                              want_lags=want_lags, stream=stream)
+
     def matches_above(self, corpus: "Corpus", channels, n: int, threshold: float, capacity: int, range_: int = 0, index_base: int = 0,
                       want_lags: bool = True, stream=None):
         """Every entry the window of every listed channel matches at or above `threshold`: window_device, then
@@ -1518,6 +1548,111 @@ class Corpus:
             lambda R, per, cap, kp, lp, cp, sp: self._L.LBAudioDetectiveCorpusQueryPackedOccurrencesTailBatchKeysDevice(
                 self._ref, _dev_ptr(packed), R, per, _dev_ptr(d_new), max_new, range_, threshold, cap, index_base, kp, lp, cp, sp))
 
+    # ---- live best matches: the tail occurrences' cells folded to one value per (recording, entry) -- per-entry scores, the K
+    # best, or all at or above a score, of what a push has completed
+    @staticmethod
+    def _tail_new_counts(packed, n_recordings: int, new_counts, max_new, stream):
+        """(device tensor, max_new) of a tail call's new counts, as query_packed_occurrences_tail_batch_keys_device takes them: a
+        device uint32 / int32 tensor (max_new required) or a host sequence uploaded on `stream` (max_new defaults to its maximum)"""
+        import torch
+        R = int(n_recordings)
+        if hasattr(new_counts, "data_ptr"):
+            if max_new is None:
+                raise ValueError("max_new is required with new counts on the device")
+            if (not new_counts.is_cuda or not new_counts.is_contiguous() or new_counts.dtype not in (torch.int32, torch.uint32) or
+                    new_counts.numel() < R):
+                raise ValueError("new_counts must be a contiguous device tensor of at least n_recordings uint32 or int32 values")
+            return new_counts, int(max_new)
+        host = np.ascontiguousarray(np.asarray(new_counts).reshape(-1), dtype=np.int64)
+        if host.size != R or (host.size and (host.min() < 0 or host.max() > 0xFFFFFFFF)):
+            raise ValueError("new_counts must hold one value of 0 .. 2^32 - 1 per recording")
+        if max_new is None:
+            max_new = max(1, int(host.max()) if host.size else 1)
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        with torch.cuda.stream(stream):                  # (uploaded on the stream that reads it)
+            d_new = torch.from_numpy(host.astype(np.uint32).view(np.int32)).to(dev, non_blocking=False)
+        return d_new, int(max_new)
+
+    def recording_scores_tail_batch_device(self, packed, n_recordings: int, per_query: int, new_counts, max_new: int = None,
+                                           range_: int = 0, scores_out=None, lags_out=None, want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusRecordingPackedScoresTailBatchDevice: the cells of
+        query_packed_occurrences_tail_batch_keys_device -- per recording r those whose entry ends inside its newest d_r =
+        min(new_counts[r], max_new, per_query) sub-fingerprints -- folded per (recording, entry) -> (scores float32 [n_recordings,
+        len(self)], lags int32 of the same shape or None) on the device, asynchronously on `stream`.  scores[r][j] = max(+0, the
+        largest q_o of the pair's tail cells), +0 where the pair has none (d_r == 0, an empty entry, an entry longer than
+        per_query); lags[r][j] = -(the lowest tail offset that reaches the score), 0 where none does.  Every word is written; an
+        empty corpus writes nothing.  new_counts / max_new as the tail occurrences method takes them.  want_lags=False (and no
+        lags_out) passes NULL: the scores are the same."""
+        R, per = int(n_recordings), int(per_query)
+        _packed_ok(packed, R, per)
+        d_new, max_new = self._tail_new_counts(packed, R, new_counts, max_new, stream)
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        count = len(self)
+        n = R * count
+        if scores_out is None or (want_lags and lags_out is None):
+            import torch
+            with torch.cuda.stream(stream):              # (the blocks belong to the stream that fills them)
+                if scores_out is None:
+                    scores_out = torch.empty(max(1, n), dtype=torch.float32, device=dev)[:n].reshape(R, count)
+                if want_lags and lags_out is None:
+                    lags_out = torch.empty(max(1, n), dtype=torch.int32, device=dev)[:n].reshape(R, count)
+        _out_ok(scores_out, n, "scores_out")
+        if lags_out is not None:
+            _out_ok(lags_out, n, "lags_out")
+        _check(self._L.LBAudioDetectiveCorpusRecordingPackedScoresTailBatchDevice(
+            self._ref, _dev_ptr(packed), R, per, _dev_ptr(d_new), max_new, range_, _dev_ptr(scores_out),
+            _dev_ptr(lags_out) if lags_out is not None else None, _stream_ptr(stream)), "CorpusRecordingPackedScoresTailBatchDevice")
+        return scores_out, lags_out
+
+    def query_packed_recording_topk_tail_batch_keys_device(self, packed, n_recordings: int, per_query: int, new_counts, k: int,
+                                                           max_new: int = None, range_: int = 0, index_base: int = 0, keys_out=None,
+                                                           lags_out=None, aligned: bool = False, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedRecordingTopKTailBatchKeysDevice: the k best entries a push has completed on every
+        recording -> the [n_recordings, k] int64 key tensor, and with aligned=True (or a lags_out) (keys, lags int32 [n_recordings,
+        k]).  Row r is query_packed_recording_topk_batch_keys_device's selection over row r of
+        recording_scores_tail_batch_device: the entries scoring above 0, score descending, the lowest index first among equals,
+        zero keys (lag 0) behind them.  A (recording, entry) pair is reported at most once per push, by the push that completes
+        its best new cell.  new_counts / max_new as the tail occurrences method takes them.  Asynchronous on `stream`, nothing
+        visits the host.  Decode with decode_tail_matches and StreamBank.totals()."""
+        R, per, k = int(n_recordings), int(per_query), int(k)
+        _packed_ok(packed, R, per)
+        d_new, max_new = self._tail_new_counts(packed, R, new_counts, max_new, stream)
+        want_lags = aligned or lags_out is not None
+        if keys_out is None or (want_lags and lags_out is None):
+            import torch
+            dev = packed.device if hasattr(packed, "device") else "cuda"
+            with torch.cuda.stream(stream):
+                if keys_out is None:
+                    keys_out = torch.empty((max(1, R), max(1, k)), dtype=torch.int64, device=dev)
+                if want_lags and lags_out is None:
+                    lags_out = torch.empty((max(1, R), max(1, k)), dtype=torch.int32, device=dev)
+        _out_ok(keys_out, R * k, "keys_out")
+        if want_lags:
+            _out_ok(lags_out, R * k, "lags_out")
+        _check(self._L.LBAudioDetectiveCorpusQueryPackedRecordingTopKTailBatchKeysDevice(
+            self._ref, _dev_ptr(packed), R, per, _dev_ptr(d_new), max_new, range_, k, index_base, _dev_ptr(keys_out),
+            _dev_ptr(lags_out) if want_lags else None, _stream_ptr(stream)), "CorpusQueryPackedRecordingTopKTailBatchKeysDevice")
+        return (keys_out, lags_out) if want_lags else keys_out
+
+    def query_packed_recording_threshold_tail_batch_keys_device(self, packed, n_recordings: int, per_query: int, new_counts,
+                                                                threshold: float, capacity: int, max_new: int = None, range_: int = 0,
+                                                                index_base: int = 0, keys_out=None, lags_out=None, counts_out=None,
+                                                                want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedRecordingThresholdTailBatchKeysDevice: every entry a push has completed at or above
+        `threshold` on every recording -> (keys int64 [n_recordings, capacity], lags int32 of the same shape or None, counts int64
+        [n_recordings]) on the device, asynchronously on `stream`.  Row r is
+        query_packed_recording_threshold_batch_keys_device's selection over row r of recording_scores_tail_batch_device: ascending
+        index, the true count, zeros behind min(count, capacity), lag 0 for a zero key.  It names exactly the distinct entries of
+        row r of query_packed_occurrences_tail_batch_keys_device at the same threshold (while that row is not cut), each with the
+        key of its largest cell and the lag of the lowest offset that reaches it.  new_counts / max_new as the tail occurrences
+        method takes them.  Decode with decode_tail_matches and StreamBank.totals()."""
+        d_new, max_new = self._tail_new_counts(packed, int(n_recordings), new_counts, max_new, stream)
+        return self._batch_threshold_call(
+            "CorpusQueryPackedRecordingThresholdTailBatchKeysDevice", packed, n_recordings, per_query, capacity, keys_out, lags_out,
+            counts_out, want_lags, stream,
+            lambda R, per, cap, kp, lp, cp, sp: self._L.LBAudioDetectiveCorpusQueryPackedRecordingThresholdTailBatchKeysDevice(
+                self._ref, _dev_ptr(packed), R, per, _dev_ptr(d_new), max_new, range_, threshold, cap, index_base, kp, cp, lp, sp))
+
     # ---- recording timeline: the best entry at every offset of ONE query (a long recording) against a ragged corpus -- the
     # occurrences cells folded per offset over the entries not longer than the query.  One key per sub-fingerprint of the query,
     # whatever the corpus size.  Shards of contiguous index ranges merge by the element-wise maximum of their keys AS UNSIGNED
@@ -2122,6 +2257,23 @@ def debug_occurrences_tail_plan(n_recordings: int, per_query: int, shortest_entr
     return {"lanes": lanes.value, "recordings_per_workgroup": rpw.value, "window_records": win.value, "lds_bytes": lds.value,
             "recordings_per_pass": rpp.value, "entries_per_chunk": chunk.value, "scratch_bytes": scratch.value}
 
+
+def debug_recording_tail_plan(n_recordings: int, per_query: int, longest_entry: int, entries: int, max_new: int, scratch_limit: int = 0,
+                              key_form: bool = False) -> dict:
+    """LBAudioDetectiveDebugRecordingTailPlan: the host plan of one recording tail call (scores form, or with key_form the top-K
+    and threshold forms) -- the one the calls themselves take -- as a dict: lanes per recording, recordings_per_workgroup,
+    window_records of a recording in LDS, lds_bytes of a workgroup (those four are debug_occurrences_tail_plan's),
+    recordings_per_pass, scratch_bytes of a pass (the key forms' score and lag rows).  scratch_limit 0: the default.  Raises for a
+    shape the call refuses.  Needs no GPU."""
+    lanes, rpw, win, rpp = N.UInt32(0), N.UInt32(0), N.UInt32(0), N.UInt32(0)
+    lds, scratch = N.UInt64(0), N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveDebugRecordingTailPlan(int(n_recordings), int(per_query), int(longest_entry), int(entries), int(max_new),
+                                                          int(scratch_limit), 1 if key_form else 0, C.byref(lanes), C.byref(rpw),
+                                                          C.byref(win), C.byref(lds), C.byref(rpp), C.byref(scratch)),
+           "DebugRecordingTailPlan")
+    return {"lanes": lanes.value, "recordings_per_workgroup": rpw.value, "window_records": win.value, "lds_bytes": lds.value,
+            "recordings_per_pass": rpp.value, "scratch_bytes": scratch.value}
+
 class Comm:
     """An RCCL communicator made through the library's helpers (ncclCommInitRank with the current device).
     `unique_id()` on rank 0, the 128 bytes travel to the other ranks by whatever means the host has, then every
@@ -2280,6 +2432,28 @@ def decode_tail_occurrences(keys, lags, counts, totals, n: int, index_base: int 
     rows = []
     for r in range(cn.size):
         idx, sc, lag = decode_occurrence_keys(k[r], lg[r], cn[r])
+        rows.append((idx - int(index_base), sc, tt[r] - int(n) - lag.astype(np.int64)))
+    return rows
+
+
+def decode_tail_matches(keys, lags, totals, n: int, counts=None, index_base: int = 0):
+    """The rows of a recording tail key call (Corpus.query_packed_recording_topk_tail_batch_keys_device,
+    ...threshold_tail_batch_keys_device, StreamBank.new_best, StreamBank.new_matches_above) as a list with one (indices int64[m],
+    scores float32[m], starts int64[m]) per recording: the entry's index (global minus index_base), the score of its best new
+    cell and the ABSOLUTE sub-fingerprint at which that cell starts in the recording's life, totals[r] - n - lag.  m =
+    min(counts[r], slots) with the threshold call's counts; with counts=None the non-zero keys of a row count (the top-K call's
+    rows, or a threshold row).  keys / lags: [recordings, slots], any int sequence or device tensor."""
+    tt = np.asarray(totals).reshape(-1).astype(np.int64)
+    k = np.asarray(keys.cpu().numpy() if hasattr(keys, "cpu") else keys, dtype=np.int64).reshape(tt.size, -1)
+    lg = np.asarray(lags.cpu().numpy() if hasattr(lags, "cpu") else lags, dtype=np.int32).reshape(tt.size, -1)
+    cn = None
+    if counts is not None:
+        cn = np.asarray(counts.cpu().numpy() if hasattr(counts, "cpu") else counts).reshape(-1).astype(np.int64)
+        if cn.size != tt.size:
+            raise ValueError("counts must have one value per recording")
+    rows = []
+    for r in range(tt.size):
+        idx, sc, lag = decode_occurrence_keys(k[r], lg[r], None if cn is None else cn[r])
         rows.append((idx - int(index_base), sc, tt[r] - int(n) - lag.astype(np.int64)))
     return rows
 

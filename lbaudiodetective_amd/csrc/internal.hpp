@@ -589,6 +589,29 @@ bool occurrences_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, u
 hipError_t launch_occurrences_tail_chunk(const OccurrencesCall& call, const OccurrencesTailPlan& plan, uint32_t recordings,
                                          const uint32_t* d_new_counts, uint32_t max_new, void* d_scratch, uint64_t first_entry,
                                          uint64_t entries, uint32_t first_chunk, unsigned long long* d_counts);
+// recording tail (k_recording_tail.hip): the tail occurrences' cells folded per (recording, entry) to the best of them -- score =
+// max(+0, the largest q_o of the pair's tail cells), lag = -(the lowest tail offset that reaches it), +0 and 0 where the pair has no
+// tail cell -- as rows of `pitch` words, one per recording.  A fixed output shape: no counts, no scans, no scatter, and a pass
+// takes ALL entries in one launch.
+struct RecordingTailPlan {
+    uint32_t lanes = 0;                  // occurrences_tail_shape's four, unchanged
+    uint32_t recordings_per_workgroup = 0;
+    uint32_t window_records = 0;
+    uint64_t lds_bytes = 0;
+    uint32_t recordings_per_pass = 0;
+    uint64_t scratch_bytes = 0;          // key forms: recordings_per_pass x entries x 8, a score and a lag row per recording; else 0
+};
+// THE plan of a call, the debug symbol's and the real calls' (plan.cpp): the tail occurrences' shape; the recordings of a pass are
+// the smallest of the recordings, 65 535, what keeps the units (blocks of entries x recordings) within 32 bits and, for the key
+// forms, max(1, limit / (entries x 8)) (0: kJoinScratchDefault) -- the score and lag rows the selection reads, as
+// recording_batch_plan's key form has them.  An empty corpus: all recordings, no scratch.  1 <= max_new <= 64.
+void recording_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_max, uint64_t entries, uint32_t max_new, uint64_t limit_bytes,
+                         bool key_form, RecordingTailPlan* plan);
+// one pass: `recordings` recordings from call.d_qwords on with their new counts from d_new_counts on, every entry of the corpus;
+// call.d_scores (and d_lags, optional) are row 0 of the pass, rows `pitch` words apart, every word of `entries` per row written.
+// call.tiles == 1.  One launch on the call's stream, no scratch.
+hipError_t launch_recording_tail(const RecordingCall& call, const RecordingTailPlan& plan, uint32_t recordings, const uint32_t* d_new_counts,
+                                 uint32_t max_new, uint64_t entries, uint64_t pitch);
 
 // threshold selection over ANY number of rows (k_occurrences_batch.hip): launch_threshold_keys' results -- per row of n scores the
 // keys of the entries whose score is >= threshold in ascending entry index, the first min(count, capacity) of them to d_keys + r *

@@ -256,4 +256,31 @@ bool occurrences_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, u
     return true;
 }
 
+// The recording tail's plan (k_recording_tail.hip; internal.hpp states it): the shape above unchanged, and the recordings of a pass.
+// The fold keeps nothing per chunk, so a pass is ONE launch over all entries.
+void recording_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_max, uint64_t entries, uint32_t max_new, uint64_t limit_bytes,
+                         bool key_form, RecordingTailPlan* plan) {
+    *plan = RecordingTailPlan();
+    OccurrencesTailPlan shape;
+    occurrences_tail_shape(per, ne_max, max_new, &shape);
+    plan->lanes = shape.lanes;
+    plan->recordings_per_workgroup = shape.recordings_per_workgroup;
+    plan->window_records = shape.window_records;
+    plan->lds_bytes = shape.lds_bytes;
+    plan->recordings_per_pass = recordings;
+    if (entries == 0) return;
+    const uint64_t limit = limit_bytes ? limit_bytes : kJoinScratchDefault;
+    const uint64_t block = occurrences_block_entries();
+    const uint64_t blocks = (entries + block - 1) / block;
+    uint64_t recs = recordings;
+    if (recs > kTailMaxRecs) recs = kTailMaxRecs;
+    if (recs > kTailMaxItems / blocks) recs = kTailMaxItems / blocks;      // (>= 1: at most 2^26 blocks) units never exceed blocks x recs
+    if (key_form) {                                            // a score and a lag per entry and row of the selection
+        const uint64_t rows = limit / (entries * 8u);
+        if (recs > rows) recs = rows ? rows : 1;
+    }
+    plan->recordings_per_pass = (uint32_t)recs;
+    plan->scratch_bytes = key_form ? recs * entries * 8u : 0;
+}
+
 }  // namespace lbad

@@ -1116,6 +1116,50 @@ OSStatus LBAudioDetectiveDebugOccurrencesTailPlan(UInt32 inRecordings, UInt32 in
                                                   UInt32* outLanes, UInt32* outRecordingsPerWorkgroup, UInt32* outWindowRecords,
                                                   UInt64* outLdsBytes, UInt32* outRecordingsPerPass, UInt64* outEntriesPerChunk,
                                                   UInt64* outScratchBytes);
+/* Live peaks: the live occurrences above under the occurrences' PEAK RULE -- one event per airing, each once in a channel's life.
+ * The right neighbour of a cell exists one sub-fingerprint later, so this call judges every cell ONE SUB-FINGERPRINT LATE.  Every
+ * argument except inFinal is LBAudioDetectiveCorpusQueryPackedOccurrencesTailBatchKeysDevice's: queries, new counts (UInt32
+ * [inRecordings], 4-byte aligned, read on the stream) and outputs on the DEVICE, keys and lags [inRecordings][inCapacity], counts
+ * UInt64 [inRecordings], every word written.  With n = inSubfingerprints, d_r = min(inNewCounts[r], inMaxNew, n), 1 <= inMaxNew <=
+ * LBAD_OCCURRENCES_TAIL_PEAKS_MAX_NEW (62: a recording takes inMaxNew + 2 lanes of one wave of 64).  Entry j of n_j sub-fingerprints
+ * takes part when 1 <= n_j <= n; last = n - n_j.  The JUDGED cells of (r, j):
+ *   inFinal == 0: the offsets max(0, last - d_r) <= o <= last - 1 -- the cells whose entry ends inside the d_r sub-fingerprints in
+ *                 front of the newest one; none when d_r == 0 or last == 0;
+ *   inFinal != 0: max(0, last - d_r) <= o <= last -- the newest cell too; d_r == 0 gives the newest cell alone.  For the end of a
+ *                 stream, or before a channel is reset.
+ * A judged cell matches when q_o >= inThreshold as Float32, (o == 0 or q_o > q_(o-1)) and (o == last or q_o >= q_(o+1)), q the
+ * window's own LBAudioDetectiveCorpusMatchProfile values bit for bit: exactly the occurrences call's rule -- a plateau reports its
+ * first cell, and a neighbour below the threshold still takes part in the test.
+ * Row r is, bit for bit, row r of LBAudioDetectiveCorpusQueryPackedOccurrencesBatchKeysDevice with inPeaksOnly = 1 and the same other
+ * arguments with only the judged cells kept: the key format, lags -o, (entry ascending, offset ascending) order, zero keys and lags
+ * 0 behind min(count, inCapacity), the TRUE count in outCounts[r], nothing written next door on overflow, nothing of recording
+ * r +- 1 in a cell of r.  Shards merge per recording by concatenation.
+ * ONCE IN A CHANNEL'S LIFE: feed a channel in pushes d_1, d_2, ..., each at most inMaxNew; call with inFinal = 0 after each push,
+ * on a window that holds the channel's whole life so far or is at least (longest entry + d_k + 1) long -- TWO sub-fingerprints more
+ * than the peak-less call needs: the cell judged furthest back and its left neighbour --; make one last call with inFinal = 1 and
+ * new count 0 on the final window.  Moved to absolute positions (total - inSubfingerprints + o), the cells of all calls together
+ * are the cells of ONE occurrences call with peaks on over the whole recording, for the entries not longer than the windows: each
+ * appears exactly once, with equal key bits.
+ * Refusals in the tail call's order and with its codes; inMaxNew is refused at 0 or above 62.  An empty corpus, or no entry that
+ * takes part, is noErr with zero keys, lags and counts.
+ * Asynchronous on inStream, which it never awaits; it waits ON THE DEVICE for the corpus' latest append; nothing visits the host.
+ * Results do not depend on launch order, grid, passes, chunks or outLags, nor on inMaxNew beyond the clamp.  Nothing is carried
+ * from call to call: a pair computes d_r + 2 cells (k_occurrences_tail_peaks.hip).
+ * LBAudioDetectiveDebugOccurrencesTailPeaksPlan: the call's plan, arguments and outputs as LBAudioDetectiveDebugOccurrencesTailPlan
+ * -- it IS that plan at inMaxNew + 2 (D the next power of two >= inMaxNew + 2), from the same function as the call's. */
+#define LBAD_OCCURRENCES_TAIL_PEAKS_MAX_NEW 62
+OSStatus LBAudioDetectiveCorpusQueryPackedOccurrencesTailPeaksBatchKeysDevice(LBAudioDetectiveCorpusRef inCorpus,
+                                                                              const void* inPackedQueries, UInt32 inRecordings,
+                                                                              UInt32 inSubfingerprints, const void* inNewCounts,
+                                                                              UInt32 inMaxNew, UInt32 inFinal, UInt32 inRange,
+                                                                              Float32 inThreshold, UInt64 inCapacity, UInt64 inIndexBase,
+                                                                              void* outKeys, void* outLags, void* outCounts,
+                                                                              void* inStream);
+OSStatus LBAudioDetectiveDebugOccurrencesTailPeaksPlan(UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inShortestEntry,
+                                                       UInt32 inLongestEntry, UInt64 inEntries, UInt32 inMaxNew, UInt64 inScratchLimit,
+                                                       UInt32* outLanes, UInt32* outRecordingsPerWorkgroup, UInt32* outWindowRecords,
+                                                       UInt64* outLdsBytes, UInt32* outRecordingsPerPass, UInt64* outEntriesPerChunk,
+                                                       UInt64* outScratchBytes);
 /* Live best matches: the cells of the tail occurrences call above folded to ONE value per (recording, entry) -- which entries a
  * push completed on each channel, as per-entry scores, as the K best, or as all at or above a score -- in a fixed output shape.
  * Cells, d_r, the entries that take part and a cell's value are EXACTLY those of

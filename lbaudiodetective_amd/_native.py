@@ -262,6 +262,11 @@ _SIGNATURES = {
                                                                                    C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveDebugOccurrencesTailPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, UInt64, UInt32, UInt64, _P(UInt32), _P(UInt32),
                                                             _P(UInt32), _P(UInt64), _P(UInt32), _P(UInt64), _P(UInt64)]),
+    "LBAudioDetectiveCorpusQueryPackedOccurrencesTailPeaksBatchKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, C.c_void_p, UInt32,
+                                                                                        UInt32, UInt32, Float32, UInt64, UInt64, C.c_void_p,
+                                                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveDebugOccurrencesTailPeaksPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, UInt64, UInt32, UInt64, _P(UInt32),
+                                                                 _P(UInt32), _P(UInt32), _P(UInt64), _P(UInt32), _P(UInt64), _P(UInt64)]),
     "LBAudioDetectiveCorpusRecordingPackedScoresTailBatchDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, C.c_void_p, UInt32, UInt32,
                                                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusQueryPackedRecordingTopKTailBatchKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, C.c_void_p, UInt32,

@@ -715,6 +715,23 @@ class StreamBank:
                                                                       max_new=max_new, range_=range_, index_base=index_base,
                                                                       want_lags=want_lags, stream=stream)
 
+    def new_peaks(self, corpus: "Corpus", channels, n: int, new_counts, threshold: float, capacity: int, final: bool = False,
+                  max_new: int = None, range_: int = 0, index_base: int = 0, want_lags: bool = True, stream=None):
+        """One event per airing: the peaks among the cells the latest push made judgeable on every listed channel: window_device,
+        then Corpus.query_packed_occurrences_tail_peaks_batch_keys_device on its output, on ONE stream with nothing in between.
+        new_counts as new_occurrences takes them.  A cell is judged one sub-fingerprint late, when its right neighbour exists;
+        final=True also judges the newest cell -- call it (new counts 0) at the end of a stream or before reset.  Returns (keys
+        int64 [len(channels), capacity], lags int32 of the same shape or None, counts int64 [len(channels)]); each peak once in a
+        channel's life as long as n >= the longest entry + the push's new sub-fingerprints + 1.  Decode with
+        decode_tail_occurrences and totals()."""
+        if not hasattr(new_counts, "data_ptr"):
+            ch, _ = _u32_list(channels)
+            new_counts = np.asarray(new_counts).reshape(-1)[ch]
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.query_packed_occurrences_tail_peaks_batch_keys_device(packed, packed.shape[0], n, new_counts, threshold, capacity,
+                                                                            max_new=max_new, final=final, range_=range_,
+                                                                            index_base=index_base, want_lags=want_lags, stream=stream)
+
     def new_best(self, corpus: "Corpus", channels, n: int, new_counts, k: int = 1, max_new: int = None, aligned: bool = True,
                  range_: int = 0, index_base: int = 0, stream=None):
         """The k best entries the latest push completed on every listed channel: window_device, then
@@ -1573,6 +1590,27 @@ class Corpus:
             d_new = torch.from_numpy(host.astype(np.uint32).view(np.int32)).to(dev, non_blocking=False)
         return d_new, int(max_new)
 
+    def query_packed_occurrences_tail_peaks_batch_keys_device(self, packed, n_recordings: int, per_query: int, new_counts,
+                                                              threshold: float, capacity: int, max_new: int = None, final: bool = False,
+                                                              range_: int = 0, index_base: int = 0, keys_out=None, lags_out=None,
+                                                              counts_out=None, want_lags: bool = True, stream=None):
+        """LBAudioDetectiveCorpusQueryPackedOccurrencesTailPeaksBatchKeysDevice: of query_packed_occurrences_batch_keys_device with
+        peaks=True only the cells judged ONE sub-fingerprint late -- per recording r and entry of n_j <= per_query sub-fingerprints
+        the offsets max(0, last - d_r) .. last - 1, last = per_query - n_j, d_r = min(new_counts[r], max_new, per_query); with
+        final=True the newest cell `last` too (the end of a stream, or before a reset; new count 0 then gives it alone) -> (keys
+        int64 [n_recordings, capacity], lags int32 of the same shape or None, counts int64 [n_recordings]) on the device,
+        asynchronously on `stream`.  Row r is the batch call's row r with only those cells kept, bit for bit: a plateau reports its
+        first cell.  Each peak of a channel's life is reported once when every window holds the whole life so far or at least the
+        longest entry + the push's new sub-fingerprints + 1, and one final call closes the stream.  new_counts / max_new as the
+        tail occurrences method takes them, max_new 1 .. 62.  Decode with decode_tail_occurrences."""
+        d_new, max_new = self._tail_new_counts(packed, int(n_recordings), new_counts, max_new, stream)
+        return self._batch_threshold_call(
+            "CorpusQueryPackedOccurrencesTailPeaksBatchKeysDevice", packed, n_recordings, per_query, capacity, keys_out, lags_out,
+            counts_out, want_lags, stream,
+            lambda R, per, cap, kp, lp, cp, sp: self._L.LBAudioDetectiveCorpusQueryPackedOccurrencesTailPeaksBatchKeysDevice(
+                self._ref, _dev_ptr(packed), R, per, _dev_ptr(d_new), max_new, 1 if final else 0, range_, threshold, cap, index_base,
+                kp, lp, cp, sp))
+
     def recording_scores_tail_batch_device(self, packed, n_recordings: int, per_query: int, new_counts, max_new: int = None,
                                            range_: int = 0, scores_out=None, lags_out=None, want_lags: bool = True, stream=None):
         """LBAudioDetectiveCorpusRecordingPackedScoresTailBatchDevice: the cells of
@@ -2254,6 +2292,22 @@ def debug_occurrences_tail_plan(n_recordings: int, per_query: int, shortest_entr
                                                             int(entries), int(max_new), int(scratch_limit), C.byref(lanes), C.byref(rpw),
                                                             C.byref(win), C.byref(lds), C.byref(rpp), C.byref(chunk), C.byref(scratch)),
            "DebugOccurrencesTailPlan")
+    return {"lanes": lanes.value, "recordings_per_workgroup": rpw.value, "window_records": win.value, "lds_bytes": lds.value,
+            "recordings_per_pass": rpp.value, "entries_per_chunk": chunk.value, "scratch_bytes": scratch.value}
+
+
+def debug_occurrences_tail_peaks_plan(n_recordings: int, per_query: int, shortest_entry: int, longest_entry: int, entries: int,
+                                      max_new: int, scratch_limit: int = 0) -> dict:
+    """LBAudioDetectiveDebugOccurrencesTailPeaksPlan: the host plan of one tail peaks call -- the one the call itself takes -- with
+    debug_occurrences_tail_plan's fields: it is that plan at max_new + 2 (a recording's lanes hold the two neighbour cells),
+    max_new 1 .. 62.  Needs no GPU."""
+    lanes, rpw, win, rpp = N.UInt32(0), N.UInt32(0), N.UInt32(0), N.UInt32(0)
+    lds, chunk, scratch = N.UInt64(0), N.UInt64(0), N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveDebugOccurrencesTailPeaksPlan(int(n_recordings), int(per_query), int(shortest_entry),
+                                                                 int(longest_entry), int(entries), int(max_new), int(scratch_limit),
+                                                                 C.byref(lanes), C.byref(rpw), C.byref(win), C.byref(lds), C.byref(rpp),
+                                                                 C.byref(chunk), C.byref(scratch)),
+           "DebugOccurrencesTailPeaksPlan")
     return {"lanes": lanes.value, "recordings_per_workgroup": rpw.value, "window_records": win.value, "lds_bytes": lds.value,
             "recordings_per_pass": rpp.value, "entries_per_chunk": chunk.value, "scratch_bytes": scratch.value}
 

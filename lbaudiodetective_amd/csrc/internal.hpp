@@ -589,6 +589,17 @@ bool occurrences_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, u
 hipError_t launch_occurrences_tail_chunk(const OccurrencesCall& call, const OccurrencesTailPlan& plan, uint32_t recordings,
                                          const uint32_t* d_new_counts, uint32_t max_new, void* d_scratch, uint64_t first_entry,
                                          uint64_t entries, uint32_t first_chunk, unsigned long long* d_counts);
+// d_counts[r] = d_offsets[(r + 1) x stride] - d_offsets[r x stride] for the recordings of a pass: the scans' offsets, `stride` rows
+// a recording (k_occurrences_tail.hip's totals kernel, for both list forms)
+hipError_t launch_occurrences_tail_totals(const unsigned long long* d_offsets, uint32_t recordings, uint32_t stride,
+                                          unsigned long long* d_counts, hipStream_t stream);
+// tail occurrences under the peak rule (k_occurrences_tail_peaks.hip): per recording the cells whose entry ends inside the d_r
+// sub-fingerprints in FRONT of the newest one -- with `final` the newest cell too -- that are local peaks of the window's profile
+// (k_occurrences.hip's rule).  `plan` is occurrences_tail_plan's at max_new + 2 (a recording's lanes hold the two neighbour cells),
+// 1 <= max_new <= 62; everything else as launch_occurrences_tail_chunk.
+hipError_t launch_occurrences_tail_peaks_chunk(const OccurrencesCall& call, const OccurrencesTailPlan& plan, uint32_t recordings,
+                                               const uint32_t* d_new_counts, uint32_t max_new, bool final, void* d_scratch,
+                                               uint64_t first_entry, uint64_t entries, uint32_t first_chunk, unsigned long long* d_counts);
 // recording tail (k_recording_tail.hip): the tail occurrences' cells folded per (recording, entry) to the best of them -- score =
 // max(+0, the largest q_o of the pair's tail cells), lag = -(the lowest tail offset that reaches it), +0 and 0 where the pair has no
 // tail cell -- as rows of `pitch` words, one per recording.  A fixed output shape: no counts, no scans, no scatter, and a pass

@@ -19,13 +19,13 @@
 // waits for another, one writer per output word; the scatter computes again only units with a match and skips rows already full.
 // Nothing is read beyond an entry's records or a recording's words: every loop is bounded by a length from the record positions
 // clamped to the corpus' longest entry, or by a count the host has checked.
-// (OtPass, OtLane, ot_lane, ot_stage, ot_cell and ot_units: occurrences_tail_common.hpp, shared with k_recording_tail.hip)
+// (OtPass, OtLane, ot_lane, ot_stage, ot_cell and ot_units: occurrences_tail_common.hpp, shared with k_recording_tail.hip; kOtMaxRecs,
+// OtScratch and ot_carve: the same header, shared with k_occurrences_tail_peaks.hip)
 #include "occurrences_tail_common.hpp"
 
 namespace lbad {
 namespace {
 
-constexpr uint32_t kOtMaxRecs = 65535;                 // recordings of a pass
 constexpr uint32_t kOtThreads = 256;                   // the totals kernel
 constexpr uint32_t kOtCountFlight = 4;                 // steps of a cell whose reads are issued together: the count kernel's,
 constexpr uint32_t kOtScatterFlight = 2;               // and the scatter kernel's, which has fewer scalar registers to spare
@@ -123,29 +123,6 @@ __global__ __launch_bounds__(kOtThreads) void occurrences_tail_totals_kernel(con
     if (r < recs) out_counts[r] = offsets[(size_t)(r + 1u) * stride] - offsets[(size_t)r * stride];
 }
 
-// the scratch of a pass of `recs` recordings and chunks of at most `entries` entries, in this order (every block 8-byte aligned):
-// k_occurrences_batch.hip's with one tile
-struct OtScratch {
-    unsigned long long* state;       // 2 words: the total carried from chunk to chunk
-    unsigned long long* row_base;    // recs x entries: a row's first position
-    unsigned long long* offsets;     // recs x entries + 1: the same, and the total behind the last row
-    uint32_t* counts;                // recs x entries
-    uint32_t* tile_at;               // recs x entries (the scans': zeros)
-    uint32_t* any;                   // units: at most recs x blocks of entries
-};
-
-OtScratch ot_carve(void* d_scratch, uint64_t recs, uint64_t entries) {
-    const uint64_t rows = recs * entries;
-    OtScratch s;
-    s.state = static_cast<unsigned long long*>(d_scratch);
-    s.row_base = s.state + 2;
-    s.offsets = s.row_base + rows;
-    s.counts = reinterpret_cast<uint32_t*>(s.offsets + rows + 1);
-    s.tile_at = s.counts + (size_t)rows;
-    s.any = s.tile_at + (size_t)rows;
-    return s;
-}
-
 }  // namespace
 
 hipError_t launch_occurrences_tail_chunk(const OccurrencesCall& c, const OccurrencesTailPlan& plan, uint32_t recordings,
@@ -187,9 +164,14 @@ hipError_t launch_occurrences_tail_chunk(const OccurrencesCall& c, const Occurre
     launch_join_scans(s.counts, 1, rows, s.tile_at, s.row_base, s.state, first_chunk, s.offsets, c.stream);
     hipLaunchKernelGGL(occurrences_tail_scatter_kernel, grid, dim3(kOcThreads), lds, c.stream, a, p, s.counts, s.any, s.row_base,
                        (unsigned long long)c.capacity, 0xFFFFFFFFu - (uint32_t)c.index_base - a.first, c.d_keys, c.d_lags);
-    if (!chunked)
-        hipLaunchKernelGGL(occurrences_tail_totals_kernel, dim3((recordings + kOtThreads - 1) / kOtThreads), dim3(kOtThreads), 0, c.stream,
-                           s.offsets, recordings, a.entries, d_counts);
+    if (!chunked) return launch_occurrences_tail_totals(s.offsets, recordings, a.entries, d_counts, c.stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_occurrences_tail_totals(const unsigned long long* d_offsets, uint32_t recordings, uint32_t stride,
+                                          unsigned long long* d_counts, hipStream_t stream) {
+    hipLaunchKernelGGL(occurrences_tail_totals_kernel, dim3((recordings + kOtThreads - 1) / kOtThreads), dim3(kOtThreads), 0, stream, d_offsets,
+                       recordings, stride, d_counts);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // occurrences_tail_common.hpp -- the device side the tail kernels share: k_occurrences_tail.hip (the cells a push has completed as
-// a list) and k_recording_tail.hip (the same cells folded to the best per (recording, entry)).  k_occurrences_tail.hip's head states
+// a list), k_occurrences_tail_peaks.hip (that list under the peak rule, one sub-fingerprint late) and k_recording_tail.hip (the
+// same cells folded to the best per (recording, entry)).  k_occurrences_tail.hip's head states
 // the mapping: lanes are (recording, t) cells of ONE entry, D lanes per recording, a unit is (block of kOcEntries entries, group of
 // recordings) whose tail windows are staged once.  Everything here is per file (an unnamed namespace), as in occurrences_common.hpp.
 #pragma once
@@ -110,6 +111,32 @@ __device__ __forceinline__ bool ot_cell(const OcArgs& a, const OcLds& s, const O
 }
 
 __device__ __forceinline__ uint32_t ot_units(const OcArgs& a, const OtPass& p) { return ((a.entries + kOcEntries - 1u) / kOcEntries) * p.groups; }
+
+// ---- the host side of the two list forms (k_occurrences_tail.hip, k_occurrences_tail_peaks.hip)
+constexpr uint32_t kOtMaxRecs = 65535;                 // recordings of a pass
+
+// the scratch of a pass of `recs` recordings and chunks of at most `entries` entries, in this order (every block 8-byte aligned):
+// k_occurrences_batch.hip's with one tile
+struct OtScratch {
+    unsigned long long* state;       // 2 words: the total carried from chunk to chunk
+    unsigned long long* row_base;    // recs x entries: a row's first position
+    unsigned long long* offsets;     // recs x entries + 1: the same, and the total behind the last row
+    uint32_t* counts;                // recs x entries
+    uint32_t* tile_at;               // recs x entries (the scans': zeros)
+    uint32_t* any;                   // units: at most recs x blocks of entries
+};
+
+inline OtScratch ot_carve(void* d_scratch, uint64_t recs, uint64_t entries) {
+    const uint64_t rows = recs * entries;
+    OtScratch s;
+    s.state = static_cast<unsigned long long*>(d_scratch);
+    s.row_base = s.state + 2;
+    s.offsets = s.row_base + rows;
+    s.counts = reinterpret_cast<uint32_t*>(s.offsets + rows + 1);
+    s.tile_at = s.counts + (size_t)rows;
+    s.any = s.tile_at + (size_t)rows;
+    return s;
+}
 
 }  // namespace
 }  // namespace lbad

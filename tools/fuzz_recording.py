@@ -19,11 +19,17 @@ as 64-bit integers, lags, lengths, starts and counts exactly, scores as float bi
 and carries slack words behind it that must stay poison.  A library or HIP error ends the run.  Every trial has a generator of
 its own (seed, trial), so --only T replays trial T alone; --plan-only runs the generator and the reference without a device
 and prints how many trials land in each path bucket (tests/test_fuzz_recording_cpu.py holds those counts up).
+Every trial also makes the LIVE PEAKS call (k_occurrences_tail_peaks.hip) on its batch of recordings: new counts of 0 .. above the
+bound, a bound of 1 .. 62 (every width D of 4 .. 64 lanes), final on or off, the batch occurrences' threshold, a capacity around
+the reference's counts -- against recording_ref's peaks-on list with only the judged cells kept (expected_live).  Its axes are
+drawn LAST from the trial's generator, so every other draw of a trial is what it was before the call existed.
 
 The suite runs 200 trials with seed 20261002 (tests/test_gpu_parity.py).  Wall times on an MI355X machine, process start to exit:
 fuzz_ragged.py 400 20261002 takes 21.1 s (21.09 and 21.18 in two runs); this tool takes 6.3 s for 50 trials, 9.9 s for 100, 17.7 s
 for 200, 21.3 s for 250 and 26.0 s for 300 -- about 0.07 s a trial, five sixths of it the numpy reference -- so 200 is the largest
-multiple of 50 that stays below the ragged sweep.  The long run is recorded in profiles/fuzz_recording.txt."""
+multiple of 50 that stays below the ragged sweep (measured before the live peaks call joined the trials; it adds one call and one
+filter of a list the reference has already made).  The long runs are recorded in profiles/fuzz_recording.txt and, with the live
+peaks call, profiles/fuzz_recording_live_peaks.txt."""
 import os
 import sys
 import time
@@ -43,6 +49,7 @@ PER_VALUES = (1, 1, 2, 17, 60, 100, 125, 126, 127, 200, 251, 252, 253, 300, 378,
 BUDGET = 10000                                   # profile steps, weighted by the recording's length, a trial's reference may take
 FAMILIES = ("occurrences", "recording", "timeline")
 POISON, POISON32, SLACK = -0x0123456789ABCDEF, 0x5A5A5A5A, 5
+LIVE_MAX_NEW = (1, 2, 5, 6, 7, 8, 14, 30, 31, 62)   # the live peaks' bound: 4, 4, 8, 8, 16, 16, 16, 32, 64 and 64 lanes a recording
 
 
 def rand_fp(rng, n, L, p_zero, p_both):
@@ -296,7 +303,14 @@ def make_trial(rng):
                       ("all_empty", not any(max(c) for c in counts.values()) and not any(timeline_counts))):
         if hit:
             paths.add(name)
-    return {"L": L, "entries": entries, "recordings": recordings, "single": single, "cut": int(rng.integers(0, n + 1)), "range": range_,
+    # the live peaks call, drawn last: per recording a new count (0, 1, the bound, above it, anything up to it), final or not
+    max_new = int(rng.choice(LIVE_MAX_NEW))
+    live = {"max_new": max_new, "final": bool(rng.integers(0, 2)),
+            "new": [int(rng.choice([0, 1, max_new, max_new + 3, int(rng.integers(0, max_new + 1))])) for _ in rows]}
+    found = [live_peaks(cells[r], lens, per, min(live["new"][r], max_new, per), live["final"], thresholds["occurrences_batch"], None, 0)[2]
+             for r in rows]
+    live["capacity"] = _capacity(rng, min(found), max(found))
+    return {"live": live, "L": L, "entries": entries, "recordings": recordings, "single": single, "cut": int(rng.integers(0, n + 1)), "range": range_,
             "thresholds": thresholds, "capacities": capacities, "k": k, "index_base": index_base, "peaks": (False, True),
             "scratch_limit": scratch_limit, "grid_ceiling": grid_ceiling, "force_shared": force_shared, "handles": False,
             "cells": cells, "paths": sorted(paths)}
@@ -328,12 +342,35 @@ def expected(trial, only=None):
     return out
 
 
+def live_peaks(cs, lens, per, d, final, t, capacity, base):
+    """one row of the live peaks call: recording_ref's peaks-on list with only the judged cells kept -- the entries not longer
+    than the recording, the offsets max(0, last - d) .. last - 1, with `final` .. last, last = per - the entry's length -- as
+    (keys, lags, true count), cut at `capacity` (None: the whole list)"""
+    keys, lags = ref.occurrences_all(cs, t, True, base)
+    n_j = np.asarray(lens, np.int64)[(ref.LOW - (keys & np.uint64(ref.LOW))).astype(np.int64) - base]
+    last, o = per - n_j, -lags.astype(np.int64)
+    keep = (n_j <= per) & (lags <= 0) & (o >= last - d) & (o <= (last if final else last - 1))
+    keys, lags = keys[keep], lags[keep]
+    if capacity is None:
+        return keys, lags, len(keys)
+    return (*ref._cut(capacity, keys, lags), len(keys))
+
+
+def expected_live(trial):
+    """name -> tuple of arrays: what the live peaks call of the trial must write, from recording_ref alone"""
+    per, lv = len(trial["recordings"][0]), trial["live"]
+    lens = [len(e) for e in trial["entries"]]
+    return {"live_peaks_batch": ref.batch([live_peaks(cs, lens, per, min(d, lv["max_new"], per), lv["final"],
+                                                      trial["thresholds"]["occurrences_batch"], lv["capacity"], trial["index_base"])
+                                           for cs, d in zip(trial["cells"], lv["new"])])}
+
+
 def describe(trial):
     lens = [len(e) for e in trial["entries"]]
     return (f"L {trial['L']} range {trial['range']} entries {len(lens)} of {min(lens)}..{max(lens)} recordings {len(trial['recordings'])} x "
             f"{len(trial['recordings'][0])} single {trial['single']} base {trial['index_base']} k {trial['k']} grid {trial['grid_ceiling']} "
             f"force {trial['force_shared']} limit {trial['scratch_limit']} thresholds { {a: float(b) for a, b in trial['thresholds'].items()} } "
-            f"capacities {trial['capacities']} paths {trial['paths']}")
+            f"capacities {trial['capacities']} live {trial['live']} paths {trial['paths']}")
 
 
 # ---- the device half ---------------------------------------------------------------------------------------------------------------
@@ -405,6 +442,14 @@ def run_trial(torch, trial, want):
         corpus.query_packed_occurrences_batch_keys_device(block, R, per, float(ts["occurrences_batch"]), c, peaks=peaks, range_=rg,
                                                           index_base=base, keys_out=keys, lags_out=lags, counts_out=count)
         check(name + "_batch", (_host(keys, R * c, (R, c), u64), _host(lags, R * c, (R, c), i32), _host(count, R, (R,), i64)))
+    lv = trial["live"]                                                       # (the live peaks: the occurrences' limit)
+    c = lv["capacity"]
+    o = _Outputs(torch)
+    keys, lags, count = o.new(R * c, "i64"), o.new(R * c, "i32"), o.new(R, "i64")
+    corpus.query_packed_occurrences_tail_peaks_batch_keys_device(block, R, per, lv["new"], float(ts["occurrences_batch"]), c,
+                                                                 max_new=lv["max_new"], final=lv["final"], range_=rg, index_base=base,
+                                                                 keys_out=keys, lags_out=lags, counts_out=count)
+    check("live_peaks_batch", (_host(keys, R * c, (R, c), u64), _host(lags, R * c, (R, c), i32), _host(count, R, (R,), i64)))
     c = cap["threshold_batch"]                                               # (the batch threshold: the occurrences' switch and limit)
     o = _Outputs(torch)
     keys, lags, count = o.new(R * c, "i64"), o.new(R * c, "i32"), o.new(R, "i64")
@@ -503,6 +548,7 @@ def main(argv):
         trial = make_trial(trial_rng(seed, t))
         trial["handles"] = t % 3 == 0
         want = expected(trial)
+        want.update(expected_live(trial))
         t_ref += time.time() - t1
         for p in trial["paths"]:
             buckets[p] = buckets.get(p, 0) + 1

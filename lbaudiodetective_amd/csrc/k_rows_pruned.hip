@@ -121,20 +121,58 @@ __device__ __forceinline__ void load_points(cplx (&x)[64], const float* src) {
 
 // 7-butterfly reduction over the 8 lanes' values of one stage-6 row (DIT stages 7, 8, 9).  Operands
 // and evaluation are separate so that a pass can have the reads of all its rounds in flight at once.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 struct TreeIn {
-    float4 q0, q1, q2, q3;
+    f32x4 q0, q1, q2, q3;
 };
 struct TreeTw {     // twiddles of one tree: W_128^k, W_256^k, W_512^k (or their mirror forms)
     f32x2 t0, t1, t2;
 };
-__device__ __forceinline__ TreeIn tree_load(const float* row) {
+// LDS reads after the span prefetch of an iteration are written out: the compiler cannot tell the buffers carved out of the
+// one dynamic LDS array apart, so it orders every LDS load of its own behind the outstanding global_load_lds (s_waitcnt
+// vmcnt(0) in the middle of the unit), although the prefetch writes the span buffer only.  A read issued here is invisible to
+// that bookkeeping and to the compiler's lgkmcnt counting: whoever issues one waits for it with lds_wait before the first use.
+// LDS serves a wave's operations in order, so lgkmcnt(N) is enough for a read that at least N later LDS operations follow; the
+// "memory" clobbers keep the reads, the waits and the stores around them in program order.
+typedef __attribute__((address_space(3))) const float lds_cf32;
+__device__ __forceinline__ uint32_t lds_addr(const float* p) { return (uint32_t)(size_t)(lds_cf32*)p; }
+template <int BYTES>
+__device__ __forceinline__ f32x4 lds_read128(uint32_t addr) {
+    f32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(BYTES) : "memory");
+    return v;
+}
+template <int BYTES>
+__device__ __forceinline__ float lds_read32(uint32_t addr) {
+    float v;
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(BYTES) : "memory");
+    return v;
+}
+// the row BYTES behind LDS address `a` (rows a fixed distance apart share one address register)
+template <int BYTES = 0>
+__device__ __forceinline__ TreeIn tree_load(uint32_t a) {
     TreeIn in;
-    in.q0 = *reinterpret_cast<const float4*>(row);
-    in.q1 = *reinterpret_cast<const float4*>(row + 4);
-    in.q2 = *reinterpret_cast<const float4*>(row + 8);
-    in.q3 = *reinterpret_cast<const float4*>(row + 12);
+    in.q0 = lds_read128<BYTES>(a);
+    in.q1 = lds_read128<BYTES + 16>(a);
+    in.q2 = lds_read128<BYTES + 32>(a);
+    in.q3 = lds_read128<BYTES + 48>(a);
     return in;
 }
+// at most N LDS operations of the wave still outstanding: the operands are defined from here on
+template <int N>
+__device__ __forceinline__ void lds_wait(TreeIn& in) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(in.q0), "+v"(in.q1), "+v"(in.q2), "+v"(in.q3) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lds_wait(TreeIn (&in)[3]) {
+    asm volatile("s_waitcnt lgkmcnt(%12)"
+                 : "+v"(in[0].q0), "+v"(in[0].q1), "+v"(in[0].q2), "+v"(in[0].q3), "+v"(in[1].q0), "+v"(in[1].q1),
+                   "+v"(in[1].q2), "+v"(in[1].q3), "+v"(in[2].q0), "+v"(in[2].q1), "+v"(in[2].q2), "+v"(in[2].q3)
+                 : "n"(N)
+                 : "memory");
+}
+// pass 1: the mirror-row stores follow the twelve reads, and the counter saturates at 15
+constexpr int kPass1Wait = kRows - kRowsA < 15 ? kRows - kRowsA : 15;
 __device__ __forceinline__ TreeTw tree_twiddles(const float* tw) {
     TreeTw t;
     t.t0 = *reinterpret_cast<const f32x2*>(tw);
@@ -157,7 +195,8 @@ __device__ __forceinline__ cplx tree_eval(const TreeIn& in, const TreeTw& t) {
 // The span of the quarter frame starting at sample `first` goes to LDS skewed by 16 dwords per 64
 // samples (so that the 4 windows of a 32-lane group hit disjoint bank quarters when the points are read).
 // FMT 0 (float32): one global_load_lds_dword per 64 samples -- the data never passes through VGPRs
-// and the wave does not wait for it; FMT 1 / 2 (int16 / 32768, int32 / 2^31) convert in registers.
+// and the wave does not wait for it before the head of the next iteration (the LDS reads in between are issued by hand,
+// see lds_read128: tests/test_isa_rows_waits.py); FMT 1 / 2 (int16 / 32768, int32 / 2^31) convert in registers.
 typedef __attribute__((address_space(1))) const void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
 
@@ -206,11 +245,15 @@ __device__ __forceinline__ void span_to_lds(const void* __restrict__ pcm_raw, ui
 // counter (the waves of a workgroup do not land evenly on the SIMDs, so equal static shares finish up
 // to 40 % apart).  As soon as every wave holds its points of quarter frame u in registers, the span of
 // the next one streams into the same LDS buffer behind the arithmetic; the claim for the frame after
-// is in flight for three iterations, and the rows of u drain to HBM during u + 1.
+// is in flight for three iterations (a global atomic: nothing waits for it or in front of it before the loop head), and
+// the rows of u drain to HBM during u + 1.
 // No memset node in front of a launch: every workgroup takes a ticket when it is done with the counters (its last claim
 // has returned), and the last one leaves the counters and the ticket at zero for the next launch.  Launches that share
 // the counters never overlap: they belong to one plan, whose calls are serialised (StreamOrder orders different
 // streams, a captured graph keeps its stream's order).
+// The claim goes through a global address-space pointer: an atomic on a generic one is a flat instruction, which may touch LDS,
+// and the compiler then drains the span prefetch issued just before it (s_waitcnt vmcnt(0)) in front of the claim.
+typedef __attribute__((address_space(1))) uint32_t claim_ctr_t;
 __device__ __forceinline__ void claims_done(uint32_t* claim_ctr) {
     __threadfence();
     if (atomicAdd(claim_ctr + 8, 1u) == gridDim.x - 1u) {
@@ -261,7 +304,7 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
     };
     // the claimer keeps its counter's address in vector registers: the scalar file is full, and as a scalar pair
     // it was spilled to vector lanes and fetched back at every claim
-    uint32_t* my_ctr = claim_ctr + (blockIdx.x & 7);
+    claim_ctr_t* my_ctr = (claim_ctr_t*)(claim_ctr + (blockIdx.x & 7));
     asm volatile("" : "+v"(my_ctr));
     const bool claimer = threadIdx.x == 0;
     uint32_t claimed = 0;
@@ -280,7 +323,12 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
     // where the band's mean of row w goes inside a frame of frame_dw floats: w * b_mult + b_off -- rows of 32 bands, or
     // the compact frame of plan.sparse (128 rows of the bands that can be non-zero; b_off = 0xFFFFFFFF: a band that is +0.0
     // in every window and that nobody reads)
-    const uint32_t b_mult = band_tbl[place_tbl * kBands + band], b_off = band_tbl[(place_tbl + 1) * kBands + band];
+    // Two words, unpacked where they are used (the empty asm hides that they never change): with b_lo, b_hi, b_mult and b_off
+    // in registers of their own, and what the compiler derived from them ahead of the loop, the kernel took 250 VGPRs, with
+    // the packed words 241.  A band reads bins below kBins, a row has at most kBands words.
+    const uint32_t b_range = b_lo | (b_hi << 8);
+    const uint32_t b_mult0 = band_tbl[place_tbl * kBands + band], b_off0 = band_tbl[(place_tbl + 1) * kBands + band];
+    const uint32_t b_place = b_off0 != 0xFFFFFFFFu ? b_mult0 | (b_off0 << 8) : 0xFFFFFFFFu;
 
     const int w8 = lane >> 3, r = lane & 7;
     const float inv_norm = 1.0f / (float)(kW / 4);
@@ -301,6 +349,9 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
 #pragma unroll
     for (int rd = 0; rd < 3; ++rd) tk[rd] = rr + 8 * rd < kBins ? rr + 8 * rd : kBins - 1;
     const bool last_valid = rr + 16 < kBins;
+    // LDS addresses of the rows a lane's trees read: tasks 0 and 1 are always eight rows apart (rr + 8 < kBins)
+    const uint32_t row01 = lds_addr(tbuf + w8 * kWinDw + tk[0] * kRowDw), row2 = lds_addr(tbuf + w8 * kWinDw + tk[2] * kRowDw);
+    const uint32_t mrow10 = lds_addr(tbuf + w8 * kWinDw + (21 - tk[1]) * kRowDw), mrow2 = lds_addr(tbuf + w8 * kWinDw + (21 - tk[2]) * kRowDw);
 
     // a lane serves the same three (window, bin) tasks in every quarter frame: their twiddles stay in registers
     __syncthreads();
@@ -322,6 +373,14 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
 #else
 #define STAMP(i)
 #endif
+    auto store_out = [&]() {
+        if (!out_ptr) return;
+        uint32_t place = b_place;
+        asm volatile("" : "+v"(place));
+        const uint32_t b_mult = place & 0xFFu;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) out_ptr[q * 2 * b_mult] = out[q];
+    };
     for (;;) {
         STAMP(0);
 #ifdef LBAD_EXP_TIMELINE
@@ -340,12 +399,9 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
         const uint64_t next = quarter == 3 ? xcd_begin + 4 * ((uint64_t)wg_per_xcd + claim_slot[0]) : unit + 1;
         __syncthreads();
         if (next < xcd_end) span_to_lds<FMT>(pcm_raw, span_start(next), span, wave, lane);
-        if (quarter == 0 && claimer) claimed = atomicAdd(my_ctr, 1u);
+        if (quarter == 0 && claimer) claimed = __hip_atomic_fetch_add(my_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifndef LBAD_EXP_TIMELINE
-        if (out_ptr) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) out_ptr[q * 2 * b_mult] = out[q];
-        }
+        store_out();
 #endif
         STAMP(2);
 
@@ -371,12 +427,14 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
         cplx za[3];
         {
             TreeIn in[3];
-#pragma unroll
-            for (int rd = 0; rd < 3; ++rd) in[rd] = tree_load(tbuf + w8 * kWinDw + tk[rd] * kRowDw);
+            in[0] = tree_load(row01);
+            in[1] = tree_load<4 * 8 * kRowDw>(row01);
+            in[2] = tree_load(row2);
             // ---- pass 2: the mirror rows reuse the same buffer.  LDS executes a wave's operations in
             //      order, so these stores cannot pass the reads above, and they are on their way while
             //      the trees of pass 1 are evaluated. ------------------------------------------------------
             store_held<0, kRows - kRowsA>(held, tbuf + w8 * kWinDw + 2 * r);
+            lds_wait<kPass1Wait>(in);
 #pragma unroll
             for (int rd = 0; rd < 3; ++rd) za[rd] = tree_eval(in[rd], twp[rd]);
         }
@@ -384,16 +442,17 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
         float pw[3];
         {
             TreeIn in[3];
+            // mirror bin 512 - k is stage-6 row 43 - k, i.e. row 21 - k of this pass (bin 0 has no mirror:
+            // its lane reads the stale row 21, which keeps the stride, and drops the result)
+            in[0] = tree_load<4 * 8 * kRowDw>(mrow10);
+            in[1] = tree_load(mrow10);
+            in[2] = tree_load(mrow2);
 #pragma unroll
             for (int rd = 0; rd < 3; ++rd) {
                 const int k = tk[rd];
-                // mirror bin 512 - k is stage-6 row 43 - k, i.e. row 21 - k of this pass (bin 0 has no mirror:
-                // its lane reads the stale row 21, which keeps the stride, and drops the result)
-                in[rd] = tree_load(tbuf + w8 * kWinDw + (21 - k) * kRowDw);
-            }
-#pragma unroll
-            for (int rd = 0; rd < 3; ++rd) {
-                const int k = tk[rd];
+                if (rd == 0) lds_wait<8>(in[0]);        // four reads per round: two, one, no round behind this one
+                else if (rd == 1) lds_wait<4>(in[1]);
+                else lds_wait<0>(in[2]);
                 const cplx b = tree_eval(in[rd], twm[rd]);
                 const cplx a = za[rd];
                 float re, im;
@@ -423,13 +482,28 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
         //      together: one LDS round trip per bin instead of four. -----------------------------------
         float p[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         const float* vb = vbuf + (lane >> 5) * 24;
-        for (uint32_t k = b_lo; k < b_hi; ++k) {
+        uint32_t range = b_range;
+        asm volatile("" : "+v"(range));
+        for (uint32_t k = range & 0xFFu, k_end = range >> 8; k < k_end; ++k) {
             float v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = vb[q * 48 + k];
+            const uint32_t va = lds_addr(vb + k);
+            v[0] = lds_read32<0>(va);
+            v[1] = lds_read32<4 * 48>(va);
+            v[2] = lds_read32<4 * 96>(va);
+            v[3] = lds_read32<4 * 144>(va);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]) : : "memory");
 #pragma unroll
             for (int q = 0; q < 4; ++q)
                 if (v[q] == v[q] && fabsf(v[q]) != INFINITY) p[q] = __fadd_rn(p[q], v[q]);
+        }
+        // row = quarter * 32 + 8 * wave + 2 q + (lane >> 5)
+        {
+            uint32_t place = b_place;
+            asm volatile("" : "+v"(place));
+            const uint32_t b_mult = place & 0xFFu, b_off = place >> 8;
+            out_ptr = place != 0xFFFFFFFFu
+                          ? frames + (unit >> 2) * frame_dw + (quarter * kUnitWindows + 8 * wave + (lane >> 5)) * b_mult + b_off
+                          : nullptr;
         }
         // three instructions per quotient where every lane of the wave has a proven divisor and dividends that are +0 or
         // in [kBandDivLo, kBandDivHi]; otherwise (tiny sums, +inf by overflow, other divisors) the wave divides
@@ -445,10 +519,6 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
 #pragma unroll
             for (int q = 0; q < 4; ++q) out[q] = div_c<false>(p[q], b_div, b_rcp);
         }
-        // row = quarter * 32 + 8 * wave + 2 q + (lane >> 5)
-        out_ptr = b_off != 0xFFFFFFFFu
-                      ? frames + (unit >> 2) * frame_dw + (quarter * kUnitWindows + 8 * wave + (lane >> 5)) * b_mult + b_off
-                      : nullptr;
 #ifdef LBAD_EXP_TIMELINE
         STAMP(6);
         if (lane == 0) {
@@ -464,10 +534,7 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_pruned_kernel(c
         unit = next;
     }
 #ifndef LBAD_EXP_TIMELINE
-    if (out_ptr) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) out_ptr[q * 2 * b_mult] = out[q];
-    }
+    store_out();
 #endif
     if (claimer) claims_done(claim_ctr);
 }
@@ -580,7 +647,7 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_lanes_kernel(co
         const uint32_t fi = frame - clip * frames_per_clip;
         return (uint64_t)clip * samples_per_clip + (uint64_t)(fi * 128 + (uint32_t)(u & 3) * kUnitWindows) * kStride;
     };
-    uint32_t* my_ctr = claim_ctr + (blockIdx.x & 7);
+    claim_ctr_t* my_ctr = (claim_ctr_t*)(claim_ctr + (blockIdx.x & 7));
     asm volatile("" : "+v"(my_ctr));
     const bool claimer = threadIdx.x == 0;
     uint32_t claimed = 0;
@@ -606,6 +673,8 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_lanes_kernel(co
     int tk[3];      // transpose positions read, as before: j, j + 8, j + 16 (clamped to a valid row)
 #pragma unroll
     for (int rd = 0; rd < 3; ++rd) tk[rd] = rr + 8 * rd < kBins ? rr + 8 * rd : kBins - 1;
+    // LDS addresses of the rows a lane's trees read: tasks 0 and 1 are always eight rows apart (rr + 8 < kBins)
+    const uint32_t row01 = lds_addr(tbuf + w8 * kWinDw + tk[0] * kRowDw), row2 = lds_addr(tbuf + w8 * kWinDw + tk[2] * kRowDw);
 
     // per-task constants: divisor, RN(1 / divisor), place in a row; one "proven" word per lane
     const uint32_t* task_tbl = band_tbl + kLanesFirstRow * kBands;
@@ -687,7 +756,7 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_lanes_kernel(co
         const uint64_t next = quarter == 3 ? *next_slot : unit + 1;
         __syncthreads();
         if (next < xcd_end) span_to_lds<FMT>(pcm_raw, span_start(next), span, wave, lane);
-        if (quarter == 0 && claimer) claimed = atomicAdd(my_ctr, 1u);
+        if (quarter == 0 && claimer) claimed = __hip_atomic_fetch_add(my_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifndef LBAD_EXP_TIMELINE
         store_out();
 #endif
@@ -710,11 +779,13 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_lanes_kernel(co
         cplx za[3];
         {
             TreeIn in[3];
-#pragma unroll
-            for (int rd = 0; rd < 3; ++rd) in[rd] = tree_load(tbuf + w8 * kWinDw + tk[rd] * kRowDw);
+            in[0] = tree_load(row01);
+            in[1] = tree_load<4 * 8 * kRowDw>(row01);
+            in[2] = tree_load(row2);
             // pass 2: the mirror row of a bin takes the bin's position (bin 0 has none: its position keeps the stale "+" row,
             // whose tree is dropped below)
             store_held_lanes<0, kRows - kRowsA>(held, tbuf + w8 * kWinDw + 2 * r);
+            lds_wait<kPass1Wait>(in);
 #pragma unroll
             for (int rd = 0; rd < 3; ++rd) za[rd] = tree_eval(in[rd], twp[rd]);
         }
@@ -722,10 +793,14 @@ __global__ __launch_bounds__(kThreads, kWgPerCu) void frame_rows_lanes_kernel(co
         float pw[3];
         {
             TreeIn in[3];
-#pragma unroll
-            for (int rd = 0; rd < 3; ++rd) in[rd] = tree_load(tbuf + w8 * kWinDw + tk[rd] * kRowDw);
+            in[0] = tree_load(row01);
+            in[1] = tree_load<4 * 8 * kRowDw>(row01);
+            in[2] = tree_load(row2);
 #pragma unroll
             for (int rd = 0; rd < 3; ++rd) {
+                if (rd == 0) lds_wait<8>(in[0]);        // four reads per round: two, one, no round behind this one
+                else if (rd == 1) lds_wait<4>(in[1]);
+                else lds_wait<0>(in[2]);
                 const cplx b = tree_eval(in[rd], twm[rd]);
                 const cplx a = za[rd];
                 float re, im;

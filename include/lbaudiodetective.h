@@ -1144,7 +1144,7 @@ OSStatus LBAudioDetectiveDebugOccurrencesTailPlan(UInt32 inRecordings, UInt32 in
  * takes part, is noErr with zero keys, lags and counts.
  * Asynchronous on inStream, which it never awaits; it waits ON THE DEVICE for the corpus' latest append; nothing visits the host.
  * Results do not depend on launch order, grid, passes, chunks or outLags, nor on inMaxNew beyond the clamp.  Nothing is carried
- * from call to call: a pair computes d_r + 2 cells (k_occurrences_tail_peaks.hip).
+ * from call to call: a pair computes d_r + 2 cells (k_occurrences_tail.hip).
  * LBAudioDetectiveDebugOccurrencesTailPeaksPlan: the call's plan, arguments and outputs as LBAudioDetectiveDebugOccurrencesTailPlan
  * -- it IS that plan at inMaxNew + 2 (D the next power of two >= inMaxNew + 2), from the same function as the call's. */
 #define LBAD_OCCURRENCES_TAIL_PEAKS_MAX_NEW 62

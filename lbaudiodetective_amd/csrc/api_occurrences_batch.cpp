@@ -3,11 +3,11 @@
 // corpus at or above a score per recording, and every entry whose best cell reaches a score per recording, as rows of keys and
 // lags with a count per recording.  The plan is occurrences_batch_plan's, here and in the debug symbol (the threshold form runs the
 // batch scores pass under recording_batch_plan's key form, as the batch top-K does); the corpus' checks, the events, the staging
-// buffer and the scratch are the single calls' (recording_pass.cpp, api_occurrences.cpp, api_recording.cpp), which stay as they are.
+// buffer and the scratch are the single calls' (recording_pass.cpp, api_occurrences.cpp, api_recording.cpp), which stay as they are;
+// the argument checks, the zeros and the occurrences' pass loop are recording_pass.cpp's for every list of key rows (key_rows_call).
 #include "internal.hpp"
 
 #include <atomic>
-#include <cmath>
 
 namespace lbad {
 namespace {
@@ -17,51 +17,10 @@ std::atomic<uint32_t> g_force_shared{0};       // LBAudioDetectiveDebugSetOccurr
 const PassFamily kFamily = {occurrences_tiles, occurrences_chunk_entries, occurrences_block_entries};
 const PassFamily kScoresFamily = {occurrences_tiles, recording_chunk_entries, occurrences_block_entries};
 
-// what needs neither handle nor device: the blocks, one or more recordings whose sub-fingerprints and slots stay within 32-bit
-// indices, a finite threshold above 0, 1 .. 2^31 slots per recording, an index base a corpus can lie behind
-bool batch_args_ok(const void* c, const void* d_rows, const void* keys, const void* counts, uint32_t recordings, uint32_t per,
-                   float threshold, uint64_t capacity, uint64_t index_base) {
-    return c && d_rows && keys && counts && recordings != 0 && per != 0 && (uint64_t)recordings * per <= 0x7FFFFFFFull &&
-           std::isfinite(threshold) && threshold > 0.0f && capacity != 0 && capacity <= 0x80000000ull &&
-           (uint64_t)recordings * capacity <= 0x80000000ull && index_base <= 0x100000000ull;
-}
-
-OSStatus zero_outputs(uint32_t recordings, uint64_t capacity, unsigned long long* keys, int32_t* lags, unsigned long long* counts,
-                      hipStream_t stream) {
-    const size_t slots = (size_t)recordings * capacity;
-    LBAD_HIP(hipMemsetAsync(keys, 0, slots * sizeof(unsigned long long), stream));
-    if (lags) LBAD_HIP(hipMemsetAsync(lags, 0, slots * sizeof(int32_t), stream));
-    if (counts) LBAD_HIP(hipMemsetAsync(counts, 0, (size_t)recordings * sizeof(unsigned long long), stream));
-    return noErr;
-}
-
-// everything behind the wait, on the call's stream: the zeros, then pass by pass the recordings' rows and the compaction -- one
-// chunk of the whole corpus for several recordings, the single call's chunks and carried total for one
-OSStatus occurrences_batch_launch(LBAudioDetectiveCorpus* c, const OccurrencesBatchPlan& plan, OccurrencesCall call, const uint32_t* d_rows,
-                                  uint32_t recordings, unsigned long long* keys, int32_t* lags, unsigned long long* counts) {
-    const uint32_t per = call.n_query;
-    if (c->append_event.ev) LBAD_HIP(hipStreamWaitEvent(call.stream, c->append_event, 0));
-    OSStatus st = zero_outputs(recordings, call.capacity, keys, lags, nullptr, call.stream);
-    if (st != noErr) return st;
-    for (uint32_t r0 = 0; r0 < recordings; r0 += plan.recordings_per_pass) {
-        const uint32_t n = recordings - r0 < plan.recordings_per_pass ? recordings - r0 : plan.recordings_per_pass;
-        LBAD_HIP(launch_build_query_rows(d_rows + (size_t)r0 * per * kPackedWords, n, per, c->subfp_len, true, c->d_pq, nullptr, call.stream));
-        call.d_keys = keys + (size_t)r0 * call.capacity;
-        call.d_lags = lags ? lags + (size_t)r0 * call.capacity : nullptr;
-        LBAD_HIP(pass_chunks(c->count, plan.entries_per_chunk, [&](uint64_t e0, uint64_t m) {
-            return launch_occurrences_batch_chunk(call, plan, n, c->d_join_scratch, e0, m, e0 == 0 ? 1u : 0u, counts + r0);
-        }));
-        // a pass of one recording: the running total behind the last chunk is the recording's count
-        if (plan.recordings_per_pass == 1)
-            LBAD_HIP(hipMemcpyAsync(counts + r0, c->d_join_scratch.get(), sizeof(unsigned long long), hipMemcpyDeviceToDevice, call.stream));
-    }
-    return noErr;
-}
-
 OSStatus occurrences_batch_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t recordings, uint32_t per, uint32_t range,
                                 float threshold, uint32_t peaks, uint64_t capacity, uint64_t index_base, unsigned long long* keys,
                                 int32_t* lags, unsigned long long* counts, hipStream_t stream) {
-    if (!batch_args_ok(c, d_rows, keys, counts, recordings, per, threshold, capacity, index_base)) return kLBAudioDetectiveArgumentInvalid;
+    if (!key_rows_args_ok(c, d_rows, keys, counts, recordings, per, threshold, capacity, index_base)) return kLBAudioDetectiveArgumentInvalid;
     if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
     // what the corpus decides (pass_plan's checks, the single call's), before anything is reserved or launched
     PassQuery pq;
@@ -73,18 +32,16 @@ OSStatus occurrences_batch_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_row
     if (!occurrences_batch_plan(recordings, per, single.call.ne_min, c->ne_max, c->count, c->join_scratch_limit, g_force_shared.load() != 0,
                                 &plan))
         return kLBAudioDetectiveArgumentInvalid;
-    if (c->count == 0) return zero_outputs(recordings, capacity, keys, lags, counts, stream);     // nothing to compare: zeros
-    PassGuard guard(c, pq, false);
-    st = guard.wait();                                     // (the scratch and the staged rows are the previous call's until then)
-    if (st == noErr) st = c->d_join_scratch.reserve(plan.scratch_bytes);
-    if (st == noErr) st = c->d_pq.reserve((size_t)plan.recordings_per_pass * per * kPackedWords);
-    if (st != noErr) return st;
-    OccurrencesCall call;
-    static_cast<OcPassCall&>(call) = single.call;
-    call.tiles = plan.tiles; call.stream = stream;
-    call.d_qwords = c->d_pq;
-    call.threshold = threshold; call.peaks = peaks != 0; call.capacity = capacity; call.index_base = index_base;
-    return guard.finish(stream, occurrences_batch_launch(c, plan, call, d_rows, recordings, keys, lags, counts));
+    if (c->count == 0) return zero_key_rows(recordings, capacity, keys, lags, counts, stream);    // nothing to compare: zeros
+    KeyRows rows;
+    rows.d_rows = d_rows; rows.recordings = recordings; rows.threshold = threshold; rows.peaks = peaks != 0; rows.capacity = capacity;
+    rows.index_base = index_base; rows.keys = keys; rows.lags = lags; rows.counts = counts; rows.stream = stream;
+    const KeyRowsPasses passes = {plan.recordings_per_pass, plan.entries_per_chunk, plan.scratch_bytes};
+    return key_rows_call(c, pq, single, passes, plan.tiles, rows,
+                         [&](const OccurrencesCall& call, uint32_t, uint32_t n, uint64_t e0, uint64_t m, uint32_t first,
+                             unsigned long long* d_counts) {
+                             return launch_occurrences_batch_chunk(call, plan, n, c->d_join_scratch, e0, m, first, d_counts);
+                         });
 }
 
 // the threshold form behind the wait: pass by pass the recordings' rows, the batch scores pass into the pass' score (and lag)
@@ -117,7 +74,7 @@ OSStatus threshold_batch_launch(LBAudioDetectiveCorpus* c, const RecordingBatchP
 OSStatus threshold_batch_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows, uint32_t recordings, uint32_t per, uint32_t range,
                               float threshold, uint64_t capacity, uint64_t index_base, unsigned long long* keys,
                               unsigned long long* counts, int32_t* lags, hipStream_t stream) {
-    if (!batch_args_ok(c, d_rows, keys, counts, recordings, per, threshold, capacity, index_base)) return kLBAudioDetectiveArgumentInvalid;
+    if (!key_rows_args_ok(c, d_rows, keys, counts, recordings, per, threshold, capacity, index_base)) return kLBAudioDetectiveArgumentInvalid;
     if (!device_ready()) return kLBAudioDetectiveDeviceUnavailable;
     PassQuery pq;
     pq.d_rows = d_rows; pq.per = per; pq.range = range;
@@ -128,7 +85,7 @@ OSStatus threshold_batch_impl(LBAudioDetectiveCorpus* c, const uint32_t* d_rows,
     if (!recording_batch_plan(recordings, per, single.call.ne_min, c->ne_max, c->count, c->join_scratch_limit, true,
                               g_force_shared.load() != 0, &plan))
         return kLBAudioDetectiveArgumentInvalid;
-    if (c->count == 0) return zero_outputs(recordings, capacity, keys, lags, counts, stream);     // nothing to score: zeros
+    if (c->count == 0) return zero_key_rows(recordings, capacity, keys, lags, counts, stream);    // nothing to score: zeros
     PassGuard guard(c, pq, true);
     st = guard.wait();                                     // (the scratch and the staged rows are the previous call's until then)
     if (st == noErr) st = c->d_join_scratch.reserve(plan.scratch_bytes);

@@ -46,11 +46,7 @@ OSStatus zero_outputs(const TailSelect& sel, uint32_t recordings, uint64_t entri
         if (sel.lags) LBAD_HIP(hipMemsetAsync(sel.lags, 0, words * sizeof(int32_t), stream));
         return noErr;
     }
-    const size_t slots = (size_t)recordings * sel.slots();
-    LBAD_HIP(hipMemsetAsync(sel.keys, 0, slots * sizeof(unsigned long long), stream));
-    if (sel.lags) LBAD_HIP(hipMemsetAsync(sel.lags, 0, slots * sizeof(int32_t), stream));
-    if (sel.counts) LBAD_HIP(hipMemsetAsync(sel.counts, 0, (size_t)recordings * sizeof(unsigned long long), stream));
-    return noErr;
+    return zero_key_rows(recordings, sel.slots(), sel.keys, sel.lags, sel.counts, stream);
 }
 
 // everything behind the wait, on the call's stream: pass by pass the recordings' rows, the fold into the pass' score (and lag)

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <new>
 #include <stdexcept>
 #include <map>
@@ -563,6 +564,10 @@ bool occurrences_batch_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, 
 hipError_t launch_occurrences_batch_chunk(const OccurrencesCall& call, const OccurrencesBatchPlan& plan, uint32_t recordings,
                                           void* d_scratch, uint64_t first_entry, uint64_t entries, uint32_t first_chunk,
                                           unsigned long long* d_counts);
+// d_counts[r] = d_offsets[(r + 1) x stride] - d_offsets[r x stride] for the recordings of a pass: the scans' offsets, `stride` rows
+// a recording (k_occurrences_batch.hip's totals kernel, for the batch and the tail lists)
+hipError_t launch_occurrences_totals(const unsigned long long* d_offsets, uint32_t recordings, uint32_t stride, unsigned long long* d_counts,
+                                     hipStream_t stream);
 // tail occurrences (k_occurrences_tail.hip): the batch occurrences' rows with only the cells whose entry ends inside a recording's
 // newest d_r = min(new count on the device, max_new, n_query) sub-fingerprints, for the entries not longer than the recording; no
 // peak rule.  A call runs in passes over recordings and, within a pass of ONE recording, in chunks over entries.
@@ -585,21 +590,13 @@ bool occurrences_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, u
                            uint64_t limit_bytes, OccurrencesTailPlan* plan);
 // one chunk of one pass: `recordings` recordings from call.d_qwords on with their new counts from d_new_counts on, `entries` entries
 // from `first_entry`; call.tiles == 1, call.peaks unused; keys, lags, counts, scratch and chunks as launch_occurrences_batch_chunk.
+// `peaks`: the list under the peak rule -- per recording the cells whose entry ends inside the d_r sub-fingerprints in FRONT of the
+// newest one, with `final` the newest cell too, that are local peaks of the window's profile (k_occurrences.hip's rule); `plan` is
+// then occurrences_tail_plan's at max_new + 2 (a recording's lanes hold the two neighbour cells), 1 <= max_new <= 62.
 // Four or five launches on the call's stream, nothing visits the host.
 hipError_t launch_occurrences_tail_chunk(const OccurrencesCall& call, const OccurrencesTailPlan& plan, uint32_t recordings,
-                                         const uint32_t* d_new_counts, uint32_t max_new, void* d_scratch, uint64_t first_entry,
-                                         uint64_t entries, uint32_t first_chunk, unsigned long long* d_counts);
-// d_counts[r] = d_offsets[(r + 1) x stride] - d_offsets[r x stride] for the recordings of a pass: the scans' offsets, `stride` rows
-// a recording (k_occurrences_tail.hip's totals kernel, for both list forms)
-hipError_t launch_occurrences_tail_totals(const unsigned long long* d_offsets, uint32_t recordings, uint32_t stride,
-                                          unsigned long long* d_counts, hipStream_t stream);
-// tail occurrences under the peak rule (k_occurrences_tail_peaks.hip): per recording the cells whose entry ends inside the d_r
-// sub-fingerprints in FRONT of the newest one -- with `final` the newest cell too -- that are local peaks of the window's profile
-// (k_occurrences.hip's rule).  `plan` is occurrences_tail_plan's at max_new + 2 (a recording's lanes hold the two neighbour cells),
-// 1 <= max_new <= 62; everything else as launch_occurrences_tail_chunk.
-hipError_t launch_occurrences_tail_peaks_chunk(const OccurrencesCall& call, const OccurrencesTailPlan& plan, uint32_t recordings,
-                                               const uint32_t* d_new_counts, uint32_t max_new, bool final, void* d_scratch,
-                                               uint64_t first_entry, uint64_t entries, uint32_t first_chunk, unsigned long long* d_counts);
+                                         const uint32_t* d_new_counts, uint32_t max_new, bool peaks, bool final, void* d_scratch,
+                                         uint64_t first_entry, uint64_t entries, uint32_t first_chunk, unsigned long long* d_counts);
 // recording tail (k_recording_tail.hip): the tail occurrences' cells folded per (recording, entry) to the best of them -- score =
 // max(+0, the largest q_o of the pair's tail cells), lag = -(the lowest tail offset that reaches it), +0 and 0 where the pair has no
 // tail cell -- as rows of `pitch` words, one per recording.  A fixed output shape: no counts, no scans, no scatter, and a pass
@@ -691,6 +688,41 @@ hipError_t pass_chunks(uint64_t count, uint64_t chunk, Launch launch) {
     for (uint64_t e0 = 0; e0 < count && e == hipSuccess; e0 += chunk) e = launch(e0, count - e0 < chunk ? count - e0 : chunk);
     return e;
 }
+// The list forms whose results are rows of keys, one per recording (api_occurrences_batch.cpp's occurrences and both lists of
+// api_occurrences_tail.cpp; the key forms of api_recording_tail.cpp take the zeros).  What needs neither handle nor device: the
+// blocks, one or more recordings whose sub-fingerprints and slots stay within 32-bit indices, a finite threshold above 0, 1 .. 2^31
+// slots per recording, an index base a corpus can lie behind
+bool key_rows_args_ok(const void* c, const void* d_rows, const void* keys, const void* counts, uint32_t recordings, uint32_t per,
+                      float threshold, uint64_t capacity, uint64_t index_base);
+// zero keys and, where given, lags over recordings x slots, and zero counts where given
+OSStatus zero_key_rows(uint32_t recordings, uint64_t slots, unsigned long long* keys, int32_t* lags, unsigned long long* counts,
+                       hipStream_t stream);
+struct KeyRows {
+    const uint32_t* d_rows = nullptr;    // the recordings' packed sub-fingerprints, on the device
+    uint32_t recordings = 0;
+    float threshold = 0.0f;
+    bool peaks = false;                  // the call's peaks flag (the tail lists': false, their rule is the kernel instance's)
+    uint64_t capacity = 0, index_base = 0;
+    unsigned long long* keys = nullptr;  // [recordings][capacity]
+    int32_t* lags = nullptr;             // optional: likewise
+    unsigned long long* counts = nullptr;    // [recordings]
+    hipStream_t stream = nullptr;
+};
+// the three fields of a family's plan the host path goes by
+struct KeyRowsPasses {
+    uint32_t recordings_per_pass = 0;
+    uint64_t entries_per_chunk = 0;
+    uint64_t scratch_bytes = 0;
+};
+// one chunk of one pass: the family's launch_*_chunk with `call`'s keys and lags at the pass' row 0
+using KeyRowsChunk = std::function<hipError_t(const OccurrencesCall& call, uint32_t first_recording, uint32_t recordings, uint64_t first_entry,
+                                              uint64_t entries, uint32_t first_chunk, unsigned long long* d_counts)>;
+// One call behind its plan and a corpus that is not empty: the events (PassGuard without the top-K's), the scratch and the staging
+// buffer reserved, the call filled from the single plan with `tiles`, and on the stream the corpus' latest append awaited, the zero
+// keys and lags, then pass by pass the recordings' rows (launch_build_query_rows) and the chunks -- one chunk of the whole corpus
+// for several recordings, entry chunks and the carried total, copied to the recording's count, for one.
+OSStatus key_rows_call(struct ::LBAudioDetectiveCorpus* c, const PassQuery& q, const PassPlan& single, const KeyRowsPasses& passes,
+                       uint64_t tiles, const KeyRows& rows, const KeyRowsChunk& chunk);
 // The block of a host-returning form in the corpus' key buffer, for the null stream: n_keys keys and, behind them, n_words 32-bit
 // values, once the buffer's previous user (a top-K, threshold or join call) has left it.
 struct KeyBlock {

@@ -58,13 +58,7 @@ __global__ __launch_bounds__(kOcThreads) void occurrences_count_kernel(const OcA
         if (n.tile < a.tiles) {
             const uint32_t first = n.tile * kOcKeep;
             for (uint32_t e = n.e0; e < n.e1; ++e) {
-                uint32_t rec0, ne, c = 0u;
-                oc_entry(a, e, &rec0, &ne);
-                if (first < oc_offsets(a, ne)) {
-                    float q0, q1;
-                    const uint32_t m = oc_cells<FULL>(a, s, n.wb, rec0, ne, first - 1u + 2u * lane, &q0, &q1);
-                    c = (uint32_t)__popcll(__ballot(m & 1u)) + (uint32_t)__popcll(__ballot(m & 2u));
-                }
+                const uint32_t c = oc_count_cells<FULL>(a, s, n.wb, e, first, lane);
                 if (lane == 0u) counts[e * a.tiles + n.tile] = c;
                 some |= c;
             }
@@ -106,47 +100,12 @@ __global__ __launch_bounds__(kOcThreads) void occurrences_scatter_kernel(const O
             const uint32_t o = first - 1u + 2u * lane;
             float q0, q1;
             const uint32_t m = oc_cells<FULL>(a, s, n.wb, rec0, ne, o, &q0, &q1);
-            const unsigned long long b0 = __ballot(m & 1u), b1 = __ballot(m & 2u);
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u)) +
-                                   __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u));
-            const bool entry_long = a.nq < ne;
-            const unsigned long long low = (unsigned long long)(key_base - e);
-            unsigned long long slot = at + below;
-            if ((m & 1u) && slot < capacity) {
-                keys[slot] = ((unsigned long long)__float_as_uint(q0) << 32) | low;
-                if (lags) lags[slot] = entry_long ? (int32_t)o : -(int32_t)o;
-            }
-            slot += m & 1u;
-            if ((m & 2u) && slot < capacity) {
-                keys[slot] = ((unsigned long long)__float_as_uint(q1) << 32) | low;
-                if (lags) lags[slot] = entry_long ? (int32_t)(o + 1u) : -(int32_t)(o + 1u);
-            }
+            oc_emit(a, e, ne, m, o, o + 1u, q0, q1, at, capacity, key_base, keys, lags);
         }
     }
 }
 
-// the scratch of a chunk of `entries` entries, in this order (every block 8-byte aligned)
-struct OcScratch {
-    unsigned long long* state;       // 2 words: the total carried from chunk to chunk
-    unsigned long long* row_base;    // entries: an entry's first slot
-    unsigned long long* offsets;     // entries + 1: what launch_join_scans hands a join's caller; nothing reads it here -- 8 bytes
-                                     // per entry are the price of using the joins' scans as they are
-    uint32_t* counts;                // entries x tiles
-    uint32_t* tile_at;               // entries x tiles
-    uint32_t* any;                   // entry blocks x tile groups
-};
-
-OcScratch oc_carve(void* d_scratch, uint64_t entries, uint64_t tiles) {
-    OcScratch s;
-    s.state = static_cast<unsigned long long*>(d_scratch);
-    s.row_base = s.state + 2;
-    s.offsets = s.row_base + entries;
-    s.counts = reinterpret_cast<uint32_t*>(s.offsets + entries + 1);
-    s.tile_at = s.counts + (size_t)entries * tiles;
-    s.any = s.tile_at + (size_t)entries * tiles;
-    return s;
-}
-
+// (the scratch of a chunk: OcScratch with a row per entry of the chunk)
 template <bool FULL>
 hipError_t launch_oc(const OccurrencesCall& c, const OcScratch& s, const OcArgs& a, size_t lds, uint32_t first_chunk) {
     static size_t ready[kMaxDevices] = {};                     // (both kernels of this instance)

@@ -29,7 +29,6 @@
 namespace lbad {
 namespace {
 
-constexpr uint32_t kObMaxRecs = 65535;                 // recordings of a pass
 constexpr uint64_t kObLdsBudget = 160 * 1024 - 64;     // occurrences_common.hpp's static assertion: a CU's LDS less 64 bytes
 constexpr uint32_t kObThreads = 256;                   // the small kernels
 constexpr uint32_t kObScoreTile = 64;                  // entries of a (recording, entry tile) of the threshold compaction: a wave's
@@ -140,13 +139,7 @@ __global__ __launch_bounds__(kOcThreads) void occurrences_batch_count_kernel(con
             const uint32_t e0 = n.eb * kOcEntries, e1 = a.entries - e0 < kOcEntries ? a.entries : e0 + kOcEntries;
             uint32_t* __restrict__ row = counts + (size_t)n.rec * a.entries * a.tiles;
             for (uint32_t e = e0; e < e1; ++e) {
-                uint32_t rec0, ne, c = 0u;
-                oc_entry(a, e, &rec0, &ne);
-                if (first < oc_offsets(a, ne)) {
-                    float q0, q1;
-                    const uint32_t m = oc_cells<FULL>(b, s, n.wb, rec0, ne, first - 1u + 2u * lane, &q0, &q1);
-                    c = (uint32_t)__popcll(__ballot(m & 1u)) + (uint32_t)__popcll(__ballot(m & 2u));
-                }
+                const uint32_t c = oc_count_cells<FULL>(b, s, n.wb, e, first, lane);
                 if (lane == 0u) row[(size_t)e * a.tiles + n.tile] = c;
                 some |= c;
             }
@@ -202,21 +195,7 @@ __global__ __launch_bounds__(kOcThreads) void occurrences_batch_scatter_kernel(c
             const uint32_t o = first - 1u + 2u * lane;
             float q0, q1;
             const uint32_t m = oc_cells<FULL>(b, s, n.wb, rec0, ne, o, &q0, &q1);
-            const unsigned long long b0 = __ballot(m & 1u), b1 = __ballot(m & 2u);
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u)) +
-                                   __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u));
-            const bool entry_long = a.nq < ne;
-            const unsigned long long low = (unsigned long long)(key_base - e);
-            unsigned long long slot = at + below;
-            if ((m & 1u) && slot < capacity) {
-                out_keys[slot] = ((unsigned long long)__float_as_uint(q0) << 32) | low;
-                if (out_lags) out_lags[slot] = entry_long ? (int32_t)o : -(int32_t)o;
-            }
-            slot += m & 1u;
-            if ((m & 2u) && slot < capacity) {
-                out_keys[slot] = ((unsigned long long)__float_as_uint(q1) << 32) | low;
-                if (out_lags) out_lags[slot] = entry_long ? (int32_t)(o + 1u) : -(int32_t)(o + 1u);
-            }
+            oc_emit(a, e, ne, m, o, o + 1u, q0, q1, at, capacity, key_base, out_keys, out_lags);
         }
     }
 }
@@ -274,33 +253,11 @@ __global__ __launch_bounds__(kObThreads) void threshold_batch_scatter_kernel(con
     }
 }
 
-// the scratch of a pass of `recs` recordings and chunks of at most `entries` entries, in this order (every block 8-byte aligned);
-// with one recording k_occurrences.hip's
-struct ObScratch {
-    unsigned long long* state;       // 2 words: the total carried from chunk to chunk
-    unsigned long long* row_base;    // recs x entries: a row's first position
-    unsigned long long* offsets;     // recs x entries + 1: the same, and the total behind the last row
-    uint32_t* counts;                // recs x entries x tiles
-    uint32_t* tile_at;               // recs x entries x tiles
-    uint32_t* any;                   // units
-};
-
-ObScratch ob_carve(void* d_scratch, uint64_t recs, uint64_t entries, uint64_t tiles) {
-    const uint64_t rows = recs * entries;
-    ObScratch s;
-    s.state = static_cast<unsigned long long*>(d_scratch);
-    s.row_base = s.state + 2;
-    s.offsets = s.row_base + rows;
-    s.counts = reinterpret_cast<uint32_t*>(s.offsets + rows + 1);
-    s.tile_at = s.counts + (size_t)rows * tiles;
-    s.any = s.tile_at + (size_t)rows * tiles;
-    return s;
-}
-
+// (the scratch of a pass: OcScratch with a row per (recording, entry); with one recording k_occurrences.hip's)
 size_t ob_wave_lds(uint32_t ne_max) { return (size_t)kOcWaves * (kOcTile + 2u + ne_max) * kOcRecBytes + kTriSize * sizeof(float); }
 
 template <bool FULL, bool WAVE>
-hipError_t launch_ob(const OccurrencesCall& c, const ObScratch& s, const OcArgs& a, const ObPass& p, size_t lds, uint32_t first_chunk,
+hipError_t launch_ob(const OccurrencesCall& c, const OcScratch& s, const OcArgs& a, const ObPass& p, size_t lds, uint32_t first_chunk,
                      unsigned long long* d_counts) {
     static size_t ready[kMaxDevices] = {};                     // (both kernels of this instance)
     const hipError_t e = oc_allow_lds(ready, lds, occurrences_batch_count_kernel<FULL, WAVE>, occurrences_batch_scatter_kernel<FULL, WAVE>);
@@ -314,13 +271,18 @@ hipError_t launch_ob(const OccurrencesCall& c, const ObScratch& s, const OcArgs&
     hipLaunchKernelGGL((occurrences_batch_scatter_kernel<FULL, WAVE>), grid, dim3(kOcThreads), lds, c.stream, a, p, s.counts, s.any,
                        s.tile_at, s.row_base, (unsigned long long)c.capacity, 0xFFFFFFFFu - (uint32_t)c.index_base - a.first, c.d_keys,
                        c.d_lags);
-    if (!p.chunked)
-        hipLaunchKernelGGL(occurrences_batch_totals_kernel, dim3((p.recs + kObThreads - 1) / kObThreads), dim3(kObThreads), 0, c.stream,
-                           s.offsets, p.recs, a.entries, d_counts);
+    if (!p.chunked) return launch_occurrences_totals(s.offsets, p.recs, a.entries, d_counts, c.stream);
     return hipGetLastError();
 }
 
 }  // namespace
+
+hipError_t launch_occurrences_totals(const unsigned long long* d_offsets, uint32_t recordings, uint32_t stride, unsigned long long* d_counts,
+                                     hipStream_t stream) {
+    hipLaunchKernelGGL(occurrences_batch_totals_kernel, dim3((recordings + kObThreads - 1) / kObThreads), dim3(kObThreads), 0, stream,
+                       d_offsets, recordings, stride, d_counts);
+    return hipGetLastError();
+}
 
 bool occurrences_batch_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uint32_t ne_max, uint64_t entries, uint64_t limit_bytes,
                             bool force_shared, OccurrencesBatchPlan* plan) {
@@ -341,7 +303,7 @@ bool occurrences_batch_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, 
         recs = limit / one;
         const uint64_t items = kOcMaxItems / (entries * tiles);            // (>= 1: occurrences_chunk_entries kept the chunk within it)
         if (recs > items) recs = items;
-        if (recs > kObMaxRecs) recs = kObMaxRecs;
+        if (recs > kOcMaxRecs) recs = kOcMaxRecs;
         if (recs > recordings) recs = recordings;
     }
     plan->tiles = tiles;
@@ -359,14 +321,9 @@ hipError_t launch_occurrences_batch_chunk(const OccurrencesCall& c, const Occurr
                                           uint64_t first_entry, uint64_t entries, uint32_t first_chunk, unsigned long long* d_counts) {
     if (entries == 0 || recordings == 0) return hipSuccess;
     const bool chunked = plan.recordings_per_pass == 1;
-    // (oc_call_ok's, and what ties the launch to the plan: the scratch, the 32-bit row and unit indices, the keys' rows; more than
-    // one recording takes the whole corpus in one chunk)
+    // (oc_call_ok's, and what ties the launch to the plan: oc_rows_call_ok's)
     if (!oc_call_ok(c, occurrences_tiles(c.n_query, c.ne_min, c.ne_max), first_entry, entries) || plan.tiles != c.tiles ||
-        recordings > plan.recordings_per_pass || recordings > kObMaxRecs || entries > plan.entries_per_chunk ||
-        (!chunked && (first_entry != 0 || first_chunk == 0)) || (uint64_t)recordings * entries * c.tiles > kOcMaxItems ||
-        (uint64_t)recordings * c.n_query > 0x7FFFFFFFull || (uint64_t)recordings * c.capacity > 0x80000000ull ||
-        (uint64_t)recordings * occurrences_scratch_bytes(entries, c.tiles) > plan.scratch_bytes ||
-        c.index_base + first_entry + entries > 0x100000000ull || !c.d_keys || !d_counts)
+        !oc_rows_call_ok(c, plan, recordings, first_entry, entries, first_chunk, d_counts))
         return hipErrorInvalidValue;
     size_t lds = 0;
     OcArgs a = oc_args(c, first_entry, entries, c.threshold, c.peaks, &lds);
@@ -381,7 +338,7 @@ hipError_t launch_occurrences_batch_chunk(const OccurrencesCall& c, const Occurr
     ObPass p;
     p.recs = recordings; p.chunked = chunked ? 1u : 0u;
     // (a chunked pass keeps ONE carving for all its chunks: the state word is carried)
-    const ObScratch s = ob_carve(d_scratch, chunked ? 1 : recordings, chunked ? plan.entries_per_chunk : entries, c.tiles);
+    const OcScratch s = oc_carve(d_scratch, chunked ? plan.entries_per_chunk : (uint64_t)recordings * entries, c.tiles);
     const bool full = c.range >= c.subfp_len;
     if (wave) return full ? launch_ob<true, true>(c, s, a, p, lds, first_chunk, d_counts) : launch_ob<false, true>(c, s, a, p, lds, first_chunk, d_counts);
     return full ? launch_ob<true, false>(c, s, a, p, lds, first_chunk, d_counts) : launch_ob<false, false>(c, s, a, p, lds, first_chunk, d_counts);
@@ -397,7 +354,7 @@ hipError_t launch_threshold_batch_keys(const float* d_scores, uint64_t n, uint32
                                        hipStream_t stream) {
     if (rows == 0) return hipSuccess;
     const uint64_t etiles = (n + kObScoreTile - 1) / kObScoreTile;
-    if (!(threshold > 0.0f) || capacity == 0 || n == 0 || n > 0xFFFFFFFFull || index_base + n > 0x100000000ull || rows > kObMaxRecs ||
+    if (!(threshold > 0.0f) || capacity == 0 || n == 0 || n > 0xFFFFFFFFull || index_base + n > 0x100000000ull || rows > kOcMaxRecs ||
         (uint64_t)rows * etiles > 0x7FFFFFFFull || (uint64_t)rows * capacity > 0x80000000ull)
         return hipErrorInvalidValue;
     unsigned long long* state = static_cast<unsigned long long*>(d_scratch);

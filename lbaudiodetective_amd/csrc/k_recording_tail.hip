@@ -22,7 +22,6 @@
 namespace lbad {
 namespace {
 
-constexpr uint32_t kRtMaxRecs = 65535;                 // recordings of a pass
 constexpr uint32_t kRtFlight = 4;                      // steps of a cell whose reads are issued together: the count kernel's
 static_assert(kTriSize * sizeof(float) == 20604 && kOcRecBytes == 36 && kOcThreads == 256 && kOcEntries == 64,
               "occurrences_tail_shape (plan.cpp) counts the LDS and the lanes with these");
@@ -76,16 +75,12 @@ __global__ __launch_bounds__(kOcThreads) void recording_tail_kernel(const OcArgs
 hipError_t launch_recording_tail(const RecordingCall& c, const RecordingTailPlan& plan, uint32_t recordings, const uint32_t* d_new_counts,
                                  uint32_t max_new, uint64_t entries, uint64_t pitch) {
     if (entries == 0 || recordings == 0) return hipSuccess;
-    // (oc_call_ok's with one tile, and what ties the launch to the plan: the lanes, the sub-windows and the LDS, the 32-bit unit
-    // indices, the rows)
-    OccurrencesTailPlan again;
+    // (oc_call_ok's with one tile, and what ties the launch to the plan: the lanes, the sub-windows and the LDS (ot_shape_ok), the
+    // 32-bit unit indices, the rows)
     if (!oc_call_ok(c, 1, 0, entries) || max_new == 0 || max_new > LBAD_OCCURRENCES_TAIL_MAX_NEW) return hipErrorInvalidValue;
-    occurrences_tail_shape(c.n_query, c.ne_max, max_new, &again);
-    if (again.lanes != plan.lanes || again.recordings_per_workgroup != plan.recordings_per_workgroup ||
-        again.window_records != plan.window_records || again.lds_bytes != plan.lds_bytes || plan.lds_bytes > 160 * 1024 - 64 ||
-        plan.lanes == 0 || plan.lanes > 64 || (plan.lanes & (plan.lanes - 1u)) != 0 || plan.recordings_per_workgroup == 0 ||
-        plan.recordings_per_workgroup * plan.lanes > kOcThreads || plan.window_records > c.n_query ||
-        recordings > plan.recordings_per_pass || recordings > kRtMaxRecs || oc_blocks(entries) * recordings > kOcMaxItems ||
+    if (!ot_shape_ok(c, plan, max_new) || plan.lanes == 0 || plan.lanes > 64 || (plan.lanes & (plan.lanes - 1u)) != 0 ||
+        plan.recordings_per_workgroup == 0 || plan.recordings_per_workgroup * plan.lanes > kOcThreads ||
+        recordings > plan.recordings_per_pass || recordings > kOcMaxRecs || oc_blocks(entries) * recordings > kOcMaxItems ||
         (uint64_t)recordings * c.n_query > 0x7FFFFFFFull || entries > pitch || !c.d_scores || !d_new_counts)
         return hipErrorInvalidValue;
     size_t lds = 0;
@@ -93,10 +88,7 @@ hipError_t launch_recording_tail(const RecordingCall& c, const RecordingTailPlan
     if (!a.tri) return hipErrorOutOfMemory;
     a.win = plan.window_records;
     lds = (size_t)plan.lds_bytes;
-    OtPass p;
-    p.fresh = d_new_counts; p.recs = recordings; p.chunked = 0u; p.max_new = max_new; p.lanes = plan.lanes;
-    p.shift = (uint32_t)__builtin_ctz(plan.lanes); p.per_group = plan.recordings_per_workgroup;
-    p.groups = (recordings + p.per_group - 1u) / p.per_group;
+    const OtPass p = ot_pass(plan, recordings, d_new_counts, max_new, false, false);
     static size_t ready[kMaxDevices] = {};
     const hipError_t e = oc_allow_lds(ready, lds, recording_tail_kernel);
     if (e != hipSuccess) return e;

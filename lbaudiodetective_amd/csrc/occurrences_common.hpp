@@ -1,6 +1,8 @@
 // occurrences_common.hpp -- the pair loop of the occurrences pass, shared by the files whose kernels run it: k_occurrences.hip
 // (the cells at or above a score as a list), k_recording.hip (the cells folded to a maximum per entry) and k_timeline.hip (to
-// the best entry per offset) -- its device side, the head of their kernels and the launch side of a chunk.  k_occurrences.hip's
+// the best entry per offset) -- its device side, the head of their kernels and the launch side of a chunk -- and what the list
+// families share beyond it (k_occurrences.hip, k_occurrences_batch.hip, k_occurrences_tail.hip): the count of an item, the emission
+// of a lane's two cells, the scratch and the checks of a pass of rows.  k_occurrences.hip's
 // head states the loop: a work item is (entry, tile of kOcTile offsets), a wave computes the tile's cells and one more on each
 // side, a lane owns two neighbouring offsets, the query's window is prepared once per block of kOcEntries entries into LDS and
 // fingerprint2's record of a step comes through the scalar unit.  Everything here is per file (an unnamed namespace), as in
@@ -19,6 +21,7 @@ constexpr uint32_t kOcTileGroup = kOcWaves * kOcTile;  // offsets of one entry a
 constexpr uint32_t kOcEntries = 64;                    // entries a workgroup walks with one window (k_occurrences.hip: kOcBlock)
 constexpr uint32_t kOcMaxGrid = 1u << 16;              // units beyond this many workgroups are walked with a grid stride
 constexpr uint64_t kOcMaxItems = 0xFFFFFFFFull - 4096; // entries x tiles of a chunk: 32-bit indices
+constexpr uint32_t kOcMaxRecs = 65535;                 // recordings of a pass, in every batch and tail family
 constexpr uint32_t kOcCap = LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS;
 constexpr uint32_t kOcTriLast = kTriPairs * (kTriPairs + 1) / 2;   // the table's last row
 constexpr uint32_t kOcRecBytes = 36;                   // a prepared record in LDS: P, N, the row
@@ -195,6 +198,50 @@ __device__ __forceinline__ void oc_entry(const OcArgs& a, uint32_t e, uint32_t* 
 // offsets of the pair (query, entry of ne sub-fingerprints)
 __device__ __forceinline__ uint32_t oc_offsets(const OcArgs& a, uint32_t ne) { return a.nq < ne ? ne - a.nq + 1u : a.nq - ne + 1u; }
 
+// The count of one item (entry e of the chunk, the tile whose first offset is `first`): its matching cells, 0 where the pair has no
+// offset in the tile.  a: the wave's recording (its query; the corpus and the chunk are the call's); lane: the kernel's own
+// threadIdx.x & 63.  Called by whole waves.
+template <bool FULL>
+__device__ __forceinline__ uint32_t oc_count_cells(const OcArgs& a, const OcLds& s, uint32_t wb, uint32_t e, uint32_t first,
+                                                   uint32_t lane) {
+    uint32_t rec0, ne, c = 0u;
+    oc_entry(a, e, &rec0, &ne);
+    if (first < oc_offsets(a, ne)) {
+        float q0, q1;
+        const uint32_t m = oc_cells<FULL>(a, s, wb, rec0, ne, first - 1u + 2u * lane, &q0, &q1);
+        c = (uint32_t)__popcll(__ballot(m & 1u)) + (uint32_t)__popcll(__ballot(m & 2u));
+    }
+    return c;
+}
+
+// The lane's two cells of one item (oc_cells' match bits m and quotients q0 and q1; offsets o and o1 = o + 1, the caller's sum:
+// the value oc_cells tests) into the list: the item's first slot is `at`, a cell's slot that plus the matching cells in lower lanes
+// (and the lane's own first cell), written where it is below the capacity.  A key is  quotient bits << 32 | key_base - e, a lag
+// +offset where the entry is the longer (case A), -offset otherwise.  Called by whole waves (the ballots).
+__device__ __forceinline__ void oc_emit(const OcArgs& a, uint32_t e, uint32_t ne, uint32_t m, uint32_t o, uint32_t o1, float q0, float q1,
+                                        unsigned long long at, unsigned long long capacity, uint32_t key_base,
+                                        unsigned long long* keys, int32_t* lags) {
+    const unsigned long long b0 = __ballot(m & 1u), b1 = __ballot(m & 2u);
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u)) +
+                           __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u));
+    const bool entry_long = a.nq < ne;
+    const unsigned long long low = (unsigned long long)(key_base - e);
+    const auto put = [&](unsigned long long slot, float q, uint32_t off) {
+        keys[slot] = ((unsigned long long)__float_as_uint(q) << 32) | low;
+        if (lags) {
+            // (tools/isa_diff.py asks for this form: with a plain `lags[slot] = ...` the six scatter kernels schedule the select in
+            // front of the address and are no longer, instruction for instruction, the kernels that wrote this out themselves.
+            // Passing o1 in, not adding 1 here, is for the same check.  Once that comparison no longer matters, write it plainly.)
+            int32_t& lag = lags[slot];
+            lag = entry_long ? (int32_t)off : -(int32_t)off;
+        }
+    };
+    unsigned long long slot = at + below;
+    if ((m & 1u) && slot < capacity) put(slot, q0, o);
+    slot += m & 1u;
+    if ((m & 2u) && slot < capacity) put(slot, q1, o1);
+}
+
 // The head of a pair-loop kernel.  The table into LDS (a unit's first barrier stands between this and the first read):
 __device__ __forceinline__ void oc_load_tri(const OcArgs& a, const OcLds& s) {
     for (uint32_t i = threadIdx.x; i < kTriSize; i += kOcThreads) s.tri[i] = a.tri[i];
@@ -233,6 +280,41 @@ inline dim3 oc_grid(uint64_t units) { return dim3(strided_grid(units, kOcMaxGrid
 inline bool oc_call_ok(const OcPassCall& c, uint64_t tiles, uint64_t first_entry, uint64_t entries) {
     return c.n_query != 0 && c.n_query <= 0x7FFFFFFFu && c.ne_max != 0 && c.ne_max <= kOcCap && c.tiles != 0 && c.tiles == tiles &&
            entries * c.tiles <= kOcMaxItems && first_entry + entries <= kMaxRaggedEntries;
+}
+// The scratch of the list families (k_occurrences.hip, k_occurrences_batch.hip, k_occurrences_tail.hip), in this order (every block
+// 8-byte aligned; occurrences_scratch_bytes sizes it): `rows` rows of the joins' two scans -- the entries of a chunk, or recordings x
+// entries of a pass -- of `tiles` columns each (the tail lists: one)
+struct OcScratch {
+    unsigned long long* state;       // 2 words: the total carried from chunk to chunk
+    unsigned long long* row_base;    // rows: a row's first position
+    unsigned long long* offsets;     // rows + 1: the same, and the total behind the last row (the single call reads none of it: 8
+                                     // bytes per entry are the price of using the joins' scans as they are)
+    uint32_t* counts;                // rows x tiles
+    uint32_t* tile_at;               // rows x tiles
+    uint32_t* any;                   // units
+};
+inline OcScratch oc_carve(void* d_scratch, uint64_t rows, uint64_t tiles) {
+    OcScratch s;
+    s.state = static_cast<unsigned long long*>(d_scratch);
+    s.row_base = s.state + 2;
+    s.offsets = s.row_base + rows;
+    s.counts = reinterpret_cast<uint32_t*>(s.offsets + rows + 1);
+    s.tile_at = s.counts + (size_t)rows * tiles;
+    s.any = s.tile_at + (size_t)rows * tiles;
+    return s;
+}
+// What ties a chunk of the rows-of-keys families (batch and tail lists) to its plan -- Plan: recordings_per_pass, entries_per_chunk,
+// scratch_bytes -- behind oc_call_ok: the recordings against the plan's pass, the entries against its chunk, more than one recording
+// takes the whole corpus in one chunk, the 32-bit item, row and slot indices, the scratch, the index base, the outputs
+template <typename Plan>
+inline bool oc_rows_call_ok(const OccurrencesCall& c, const Plan& plan, uint32_t recordings, uint64_t first_entry, uint64_t entries,
+                            uint32_t first_chunk, const void* d_counts) {
+    const bool chunked = plan.recordings_per_pass == 1;
+    return recordings <= plan.recordings_per_pass && recordings <= kOcMaxRecs && entries <= plan.entries_per_chunk &&
+           (chunked || (first_entry == 0 && first_chunk != 0)) && (uint64_t)recordings * entries * c.tiles <= kOcMaxItems &&
+           (uint64_t)recordings * c.n_query <= 0x7FFFFFFFull && (uint64_t)recordings * c.capacity <= 0x80000000ull &&
+           (uint64_t)recordings * occurrences_scratch_bytes(entries, c.tiles) <= plan.scratch_bytes &&
+           c.index_base + first_entry + entries <= 0x100000000ull && c.d_keys && d_counts;
 }
 // the kernels' arguments for `entries` entries from `first_entry` (a.tri == nullptr: no table), and the LDS of a workgroup
 inline OcArgs oc_args(const OcPassCall& c, uint64_t first_entry, uint64_t entries, float threshold, bool peaks, size_t* lds) {

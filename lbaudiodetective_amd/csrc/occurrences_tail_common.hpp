@@ -1,8 +1,9 @@
-// occurrences_tail_common.hpp -- the device side the tail kernels share: k_occurrences_tail.hip (the cells a push has completed as
-// a list), k_occurrences_tail_peaks.hip (that list under the peak rule, one sub-fingerprint late) and k_recording_tail.hip (the
-// same cells folded to the best per (recording, entry)).  k_occurrences_tail.hip's head states
-// the mapping: lanes are (recording, t) cells of ONE entry, D lanes per recording, a unit is (block of kOcEntries entries, group of
-// recordings) whose tail windows are staged once.  Everything here is per file (an unnamed namespace), as in occurrences_common.hpp.
+// occurrences_tail_common.hpp -- what the tail kernels share: k_occurrences_tail.hip (the cells a push has completed as a list, and
+// that list under the peak rule, one sub-fingerprint late) and k_recording_tail.hip (the same cells folded to the best per
+// (recording, entry)) -- the device side, and on the host the plan's shape held against the call and the pass' arguments.
+// k_occurrences_tail.hip's head states the mapping: lanes are (recording, t) cells of ONE entry, D lanes per recording, a unit is
+// (block of kOcEntries entries, group of recordings) whose tail windows are staged once.  Everything here is per file (an unnamed
+// namespace), as in occurrences_common.hpp.
 #pragma once
 
 #include "occurrences_common.hpp"
@@ -19,7 +20,9 @@ struct OtPass {
     uint32_t lanes, shift;        // D = 1 << shift
     uint32_t per_group;           // recordings of a workgroup: 1 .. kOcThreads / D
     uint32_t groups;              // groups of per_group recordings in the pass
+    uint32_t final;               // the peaks list: the newest cell is judged too (the last of eight words: 40 bytes with or without it)
 };
+static_assert(sizeof(OtPass) == 40, "a pointer and eight words: the kernels' arguments lie where they lay with seven");
 
 // a lane's place in a unit
 struct OtLane {
@@ -112,30 +115,26 @@ __device__ __forceinline__ bool ot_cell(const OcArgs& a, const OcLds& s, const O
 
 __device__ __forceinline__ uint32_t ot_units(const OcArgs& a, const OtPass& p) { return ((a.entries + kOcEntries - 1u) / kOcEntries) * p.groups; }
 
-// ---- the host side of the two list forms (k_occurrences_tail.hip, k_occurrences_tail_peaks.hip)
-constexpr uint32_t kOtMaxRecs = 65535;                 // recordings of a pass
+// ---- the host side
+// the plan's shape is occurrences_tail_shape's for this call at `shape_max_new` cells a recording (1 .. 64, the caller's check), and
+// a workgroup's windows fit the LDS and the recordings
+template <typename Plan>
+inline bool ot_shape_ok(const OcPassCall& c, const Plan& plan, uint32_t shape_max_new) {
+    OccurrencesTailPlan again;
+    occurrences_tail_shape(c.n_query, c.ne_max, shape_max_new, &again);
+    return again.lanes == plan.lanes && again.recordings_per_workgroup == plan.recordings_per_workgroup &&
+           again.window_records == plan.window_records && again.lds_bytes == plan.lds_bytes && plan.lds_bytes <= 160 * 1024 - 64 &&
+           plan.window_records <= c.n_query;
+}
 
-// the scratch of a pass of `recs` recordings and chunks of at most `entries` entries, in this order (every block 8-byte aligned):
-// k_occurrences_batch.hip's with one tile
-struct OtScratch {
-    unsigned long long* state;       // 2 words: the total carried from chunk to chunk
-    unsigned long long* row_base;    // recs x entries: a row's first position
-    unsigned long long* offsets;     // recs x entries + 1: the same, and the total behind the last row
-    uint32_t* counts;                // recs x entries
-    uint32_t* tile_at;               // recs x entries (the scans': zeros)
-    uint32_t* any;                   // units: at most recs x blocks of entries
-};
-
-inline OtScratch ot_carve(void* d_scratch, uint64_t recs, uint64_t entries) {
-    const uint64_t rows = recs * entries;
-    OtScratch s;
-    s.state = static_cast<unsigned long long*>(d_scratch);
-    s.row_base = s.state + 2;
-    s.offsets = s.row_base + rows;
-    s.counts = reinterpret_cast<uint32_t*>(s.offsets + rows + 1);
-    s.tile_at = s.counts + (size_t)rows;
-    s.any = s.tile_at + (size_t)rows;
-    return s;
+// the pass of `recordings` recordings under a plan whose shape ot_shape_ok has accepted
+template <typename Plan>
+inline OtPass ot_pass(const Plan& plan, uint32_t recordings, const uint32_t* d_new_counts, uint32_t max_new, bool chunked, bool final) {
+    OtPass p;
+    p.fresh = d_new_counts; p.recs = recordings; p.chunked = chunked ? 1u : 0u; p.max_new = max_new; p.lanes = plan.lanes;
+    p.shift = (uint32_t)__builtin_ctz(plan.lanes); p.per_group = plan.recordings_per_workgroup;
+    p.groups = (recordings + p.per_group - 1u) / p.per_group; p.final = final ? 1u : 0u;
+    return p;
 }
 
 }  // namespace

@@ -1,8 +1,10 @@
 // recording_pass.cpp -- the host side that the three families of the occurrences pass share (api_occurrences.cpp,
 // api_recording.cpp, api_timeline.cpp): the plan of a call, the staging of its query, the events that keep one call's scratch
-// from the next call on another stream, and the key block of the host-returning forms.  internal.hpp states each piece.
+// from the next call on another stream, the host path of the list forms that return rows of keys (api_occurrences_batch.cpp,
+// api_occurrences_tail.cpp), and the key block of the host-returning forms.  internal.hpp states each piece.
 #include "internal.hpp"
 
+#include <cmath>
 #include <cstring>
 
 namespace lbad {
@@ -68,6 +70,65 @@ OSStatus pass_stage_query(LBAudioDetectiveCorpus* c, const PassQuery& q, hipStre
     call->stream = stream;
     if (st == noErr && c->append_event.ev) LBAD_HIP(hipStreamWaitEvent(stream, c->append_event, 0));
     return st;
+}
+
+bool key_rows_args_ok(const void* c, const void* d_rows, const void* keys, const void* counts, uint32_t recordings, uint32_t per,
+                      float threshold, uint64_t capacity, uint64_t index_base) {
+    return c && d_rows && keys && counts && recordings != 0 && per != 0 && (uint64_t)recordings * per <= 0x7FFFFFFFull &&
+           std::isfinite(threshold) && threshold > 0.0f && capacity != 0 && capacity <= 0x80000000ull &&
+           (uint64_t)recordings * capacity <= 0x80000000ull && index_base <= 0x100000000ull;
+}
+
+OSStatus zero_key_rows(uint32_t recordings, uint64_t slots, unsigned long long* keys, int32_t* lags, unsigned long long* counts,
+                       hipStream_t stream) {
+    const size_t n = (size_t)recordings * slots;
+    LBAD_HIP(hipMemsetAsync(keys, 0, n * sizeof(unsigned long long), stream));
+    if (lags) LBAD_HIP(hipMemsetAsync(lags, 0, n * sizeof(int32_t), stream));
+    if (counts) LBAD_HIP(hipMemsetAsync(counts, 0, (size_t)recordings * sizeof(unsigned long long), stream));
+    return noErr;
+}
+
+namespace {
+
+// everything behind the wait, on the call's stream
+OSStatus key_rows_launch(LBAudioDetectiveCorpus* c, const KeyRowsPasses& passes, OccurrencesCall call, const KeyRows& rows,
+                         const KeyRowsChunk& chunk) {
+    const uint32_t per = call.n_query;
+    if (c->append_event.ev) LBAD_HIP(hipStreamWaitEvent(call.stream, c->append_event, 0));
+    OSStatus st = zero_key_rows(rows.recordings, call.capacity, rows.keys, rows.lags, nullptr, call.stream);
+    if (st != noErr) return st;
+    for (uint32_t r0 = 0; r0 < rows.recordings; r0 += passes.recordings_per_pass) {
+        const uint32_t n = rows.recordings - r0 < passes.recordings_per_pass ? rows.recordings - r0 : passes.recordings_per_pass;
+        LBAD_HIP(launch_build_query_rows(rows.d_rows + (size_t)r0 * per * kPackedWords, n, per, c->subfp_len, true, c->d_pq, nullptr,
+                                         call.stream));
+        call.d_keys = rows.keys + (size_t)r0 * call.capacity;
+        call.d_lags = rows.lags ? rows.lags + (size_t)r0 * call.capacity : nullptr;
+        LBAD_HIP(pass_chunks(c->count, passes.entries_per_chunk, [&](uint64_t e0, uint64_t m) {
+            return chunk(call, r0, n, e0, m, e0 == 0 ? 1u : 0u, rows.counts + r0);
+        }));
+        // a pass of one recording: the running total behind the last chunk is the recording's count
+        if (passes.recordings_per_pass == 1)
+            LBAD_HIP(hipMemcpyAsync(rows.counts + r0, c->d_join_scratch.get(), sizeof(unsigned long long), hipMemcpyDeviceToDevice,
+                                    call.stream));
+    }
+    return noErr;
+}
+
+}  // namespace
+
+OSStatus key_rows_call(LBAudioDetectiveCorpus* c, const PassQuery& q, const PassPlan& single, const KeyRowsPasses& passes, uint64_t tiles,
+                       const KeyRows& rows, const KeyRowsChunk& chunk) {
+    PassGuard guard(c, q, false);
+    OSStatus st = guard.wait();                            // (the scratch and the staged rows are the previous call's until then)
+    if (st == noErr) st = c->d_join_scratch.reserve(passes.scratch_bytes);
+    if (st == noErr) st = c->d_pq.reserve((size_t)passes.recordings_per_pass * q.per * kPackedWords);
+    if (st != noErr) return st;
+    OccurrencesCall call;
+    static_cast<OcPassCall&>(call) = single.call;
+    call.tiles = tiles; call.stream = rows.stream;
+    call.d_qwords = c->d_pq;
+    call.threshold = rows.threshold; call.peaks = rows.peaks; call.capacity = rows.capacity; call.index_base = rows.index_base;
+    return guard.finish(rows.stream, key_rows_launch(c, passes, call, rows, chunk));
 }
 
 OSStatus key_block_reserve(LBAudioDetectiveCorpus* c, size_t n_keys, size_t n_words, KeyBlock* b) {

@@ -1,5 +1,5 @@
-"""GPU tests of the tail peaks (LBAudioDetectiveCorpusQueryPackedOccurrencesTailPeaksBatchKeysDevice, k_occurrences_tail_peaks.hip,
-StreamBank.new_peaks): the occurrences' peak rule for the cells a push has made judgeable, each judged one sub-fingerprint late.
+"""GPU tests of the tail peaks (LBAudioDetectiveCorpusQueryPackedOccurrencesTailPeaksBatchKeysDevice, k_occurrences_tail.hip's PEAKS
+instances, StreamBank.new_peaks): the occurrences' peak rule for the cells a push has made judgeable, each judged one sub-fingerprint late.
 Every key, lag and count is compared exactly against numpy (occurrences_tail_peaks_ref: align_ref.profile with the judged cells and
 the peak rule restated) AND against the batch occurrences call, peaks ON, filtered on the host: nothing needs a tolerance.  Output
 buffers are poison-filled before every call.  The corpus and the windows are test_gpu_occurrences_tail.py's: 150 ragged entries of 32

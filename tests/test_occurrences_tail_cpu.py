@@ -289,8 +289,9 @@ def _makefile_flags(stem):
 
 
 def test_tail_kernels_use_no_scratch(tmp_path):
-    """k_occurrences_tail.hip compiles for gfx950 with the flags read from the Makefile; its three kernels -- count, scatter and
-    totals -- report 0 bytes of private segment and no spilled register, scalar or vector (the metadata only)."""
+    """k_occurrences_tail.hip compiles for gfx950 with the flags read from the Makefile; its four kernels -- the plain and the
+    peaks instance of the count and of the scatter kernel -- report 0 bytes of private segment and no spilled register, scalar or
+    vector (the metadata only)."""
     if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
     out = tmp_path / "k_occurrences_tail.s"
@@ -305,11 +306,13 @@ def test_tail_kernels_use_no_scratch(tmp_path):
     for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?"
                          r"\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", isa):
         meta[m.group(1)] = (int(m.group(2)), int(m.group(3)), int(m.group(4)))
-    for kernel in ("occurrences_tail_count_kernel", "occurrences_tail_scatter_kernel", "occurrences_tail_totals_kernel"):
+    for kernel in ("occurrences_tail_count_kernel", "occurrences_tail_scatter_kernel"):
         hits = {k: v for k, v in meta.items() if kernel in k}
-        assert len(hits) == 1, (kernel, sorted(meta))
+        # the two instances of the template: PEAKS false and true in the mangled name
+        assert len(hits) == 2 and sorted("ILb1E" in k for k in hits) == [False, True], (kernel, sorted(meta))
+        assert all(("ILb0E" in k) != ("ILb1E" in k) for k in hits), sorted(hits)
         assert all(v == (0, 0, 0) for v in hits.values()), hits
-    assert len(meta) == 3, sorted(meta)
+    assert len(meta) == 4, sorted(meta)
 
 
 # ---- the reference against itself ------------------------------------------------------------------------------------------------

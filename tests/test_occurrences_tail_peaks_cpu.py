@@ -67,9 +67,17 @@ def test_python_names(lb):
 
 
 def test_the_kernel_file_is_built():
+    """the peaks kernels are instances of k_occurrences_tail.hip's kernel pair: that file is built, the peaks' own file is gone
+    from the build and from the tree, and the surviving file instantiates the PEAKS form"""
     text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
-    assert re.search(r"^SRCS\s*:=.*\bk_occurrences_tail_peaks\.hip\b", text, re.M)
-    assert os.path.exists(os.path.join(CSRC, "k_occurrences_tail_peaks.hip"))
+    assert re.search(r"^SRCS\s*:=.*\bk_occurrences_tail\.hip\b", text, re.M)
+    assert not re.search(r"^SRCS\s*:=.*\bk_occurrences_tail_peaks\.hip\b", text, re.M)
+    assert not os.path.exists(os.path.join(CSRC, "k_occurrences_tail_peaks.hip"))
+    src = open(os.path.join(CSRC, "k_occurrences_tail.hip")).read()
+    for kernel in ("occurrences_tail_count_kernel", "occurrences_tail_scatter_kernel"):
+        assert re.search(r"template\s*<bool PEAKS>\s*__global__[^{;]*\b" + kernel + r"\b", src), kernel
+        assert kernel + "<PEAKS>" in src, kernel
+    assert re.search(r"\blaunch_ot<true>\(", src) and re.search(r"\blaunch_ot<false>\(", src)
 
 
 def _fakes():

@@ -19,9 +19,9 @@ as 64-bit integers, lags, lengths, starts and counts exactly, scores as float bi
 and carries slack words behind it that must stay poison.  A library or HIP error ends the run.  Every trial has a generator of
 its own (seed, trial), so --only T replays trial T alone; --plan-only runs the generator and the reference without a device
 and prints how many trials land in each path bucket (tests/test_fuzz_recording_cpu.py holds those counts up).
-Every trial also makes the LIVE PEAKS call (k_occurrences_tail_peaks.hip) on its batch of recordings: new counts of 0 .. above the
-bound, a bound of 1 .. 62 (every width D of 4 .. 64 lanes), final on or off, the batch occurrences' threshold, a capacity around
-the reference's counts -- against recording_ref's peaks-on list with only the judged cells kept (expected_live).  Its axes are
+Every trial also makes the LIVE PEAKS call (k_occurrences_tail.hip's PEAKS instances) on its batch of recordings: new counts of
+0 .. above the bound, a bound of 1 .. 62 (every width D of 4 .. 64 lanes), final on or off, the batch occurrences' threshold, a
+capacity around the reference's counts -- against recording_ref's peaks-on list with only the judged cells kept (expected_live).  Its axes are
 drawn LAST from the trial's generator, so every other draw of a trial is what it was before the call existed.
 
 The suite runs 200 trials with seed 20261002 (tests/test_gpu_parity.py).  Wall times on an MI355X machine, process start to exit:

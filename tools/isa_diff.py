@@ -6,7 +6,11 @@ the .amdhsa_kernel descriptor block.  Exits non-zero when a kernel differs or is
 
     python tools/isa_diff.py OLD_TREE NEW_TREE --old k_sliding.hip --new k_sliding.hip k_sliding_short.hip k_records.hip
 
-(a refactor that moves kernels between files: every kernel of the old files must be found, identical, in the new ones)."""
+(a refactor that moves kernels between files: every kernel of the old files must be found, identical, in the new ones).
+
+    --pair OLD_REGEX=NEW_REGEX   (repeatable) a kernel whose symbol changed, such as one that became a template instance: each side
+                                 must match exactly one kernel symbol of its tree; the two are compared with their own symbol name
+                                 replaced by a placeholder in the code and in the descriptor, and reported under "old -> new"."""
 import argparse
 import os
 import re
@@ -83,16 +87,36 @@ def collect(tree, files, jobs):
     return all_kernels
 
 
+def take_pairs(pairs, old, new):
+    """--pair: the two kernels of each pair leave `old` and `new` and come back under one name, their own symbols a placeholder"""
+    for pair in pairs:
+        if "=" not in pair:
+            sys.exit("isa_diff: --pair wants OLD_REGEX=NEW_REGEX, not %r" % pair)
+        found = []
+        for rx, side, what in zip(pair.split("=", 1), (old, new), ("old", "new")):
+            hits = [sym for sym in side if re.search(rx, sym)]
+            if len(hits) != 1:
+                sys.exit("isa_diff: --pair %r matches %d kernels of the %s tree, not one: %s" % (rx, len(hits), what, sorted(hits)))
+            found.append(hits[0])
+        name = "%s -> %s" % tuple(found)
+        for side, sym in zip((old, new), found):
+            code, desc, file = side.pop(sym)
+            side[name] = ([l.replace(sym, "<kernel>") for l in code], [l.replace(sym, "<kernel>") for l in desc], file)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("old_tree")
     ap.add_argument("new_tree")
     ap.add_argument("--old", nargs="+", required=True, metavar="FILE", help=".hip files of the old tree (names inside " + CSRC + ")")
     ap.add_argument("--new", nargs="+", metavar="FILE", help=".hip files of the new tree (default: the same names)")
+    ap.add_argument("--pair", action="append", default=[], metavar="OLD_REGEX=NEW_REGEX",
+                    help="a kernel whose symbol changed: one kernel each side, compared with its own name as a placeholder (repeatable)")
     ap.add_argument("--jobs", type=int, default=4)
     args = ap.parse_args()
     old = collect(args.old_tree, args.old, args.jobs)
     new = collect(args.new_tree, args.new or args.old, args.jobs)
+    take_pairs(args.pair, old, new)
     bad = 0
     for sym in sorted(set(old) | set(new)):
         if sym not in new or sym not in old:
@@ -101,7 +125,7 @@ def main():
             continue
         (code_a, desc_a, _), (code_b, desc_b, file_b) = old[sym], new[sym]
         if code_a != code_b or desc_a != desc_b:
-            what = "instructions" if code_a != code_b else "descriptor"
+            what = "descriptor" if code_a == code_b else "instructions, the descriptor " + ("too" if desc_a != desc_b else "is the same")
             first = next((n for n, (x, y) in enumerate(zip(code_a, code_b)) if x != y), min(len(code_a), len(code_b)))
             print("DIFFERENT %s (%s, now in %s; %d / %d lines, first difference at %d)" % (sym, what, file_b, len(code_a), len(code_b), first))
             bad += 1

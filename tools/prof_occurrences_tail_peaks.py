@@ -21,7 +21,8 @@ Times: a host clock around the call and the synchronise that ends it, and device
 at least 5) with [min, max] in ms, one warm-up round in front.  After the clock stops (a)'s rows must equal (c)'s rows with only the
 judged cells kept, wherever (c)'s row holds every peak.  No ratio is required: peaks_below_batch / peaks_below_short record whether
 (a)'s maximum lies below the other leg's minimum in device time.  One JSON object per shape, printed and merged into
-DIR/occurrences_tail_peaks.json (default DIR: profiles).
+DIR/occurrences_tail_peaks.json (default DIR: profiles); with --shape that one shape runs in this process and is only printed.
+Legs (a) and (b) are the two instances of ONE kernel pair (k_occurrences_tail.hip, PEAKS on and off).
     timeout -k 10 900 python3 tools/prof_occurrences_tail_peaks.py 5"""
 import json
 import os

@@ -1221,6 +1221,57 @@ OSStatus LBAudioDetectiveDebugRecordingTailPlan(UInt32 inRecordings, UInt32 inSu
                                                 UInt32 inMaxNew, UInt64 inScratchLimit, UInt32 inKeyForm, UInt32* outLanes,
                                                 UInt32* outRecordingsPerWorkgroup, UInt32* outWindowRecords, UInt64* outLdsBytes,
                                                 UInt32* outRecordingsPerPass, UInt64* outScratchBytes);
+/* Live timeline: every channel's timeline kept current from each push.  A cell's value depends only on the entry and the
+ * sub-fingerprints under it, so the timeline of a window after a push is the previous timeline shifted left by the push's count,
+ * merged by element-wise UNSIGNED maximum with the cells the push completed; no window-length condition applies and nothing is
+ * computed again.  inPackedQueries ([inRecordings][n][32] bytes, n = inSubfingerprints: the windows AFTER the push, as
+ * LBAudioDetectiveStreamBankWindowDevice writes them), inNewCounts (DEVICE, UInt32 [inRecordings], 4-byte aligned, read on the
+ * stream), inMaxNew (1 .. LBAD_OCCURRENCES_TAIL_MAX_NEW), inRange and inStream are the tail occurrences call's; inThreshold (finite,
+ * > 0) and inIndexBase are the batch timeline's.  inPrevKeys (may be NULL) and outKeys are UInt64 [inRecordings][n], outLengths
+ * (may be NULL) UInt32 [inRecordings][n], all on the device.  With shift_r = min(inNewCounts[r], n) and cells_r =
+ * min(inNewCounts[r], inMaxNew, n):
+ *   T_r[o] = the unsigned maximum of  q_o(j) bits << 32 | 0xFFFFFFFF - (inIndexBase + j)  over the tail occurrences call's cells of
+ *            (r, j) at cells_r that reach inThreshold -- the entries with 1 <= n_j <= n at the offsets max(0, n - n_j - cells_r + 1)
+ *            <= o <= n - n_j, q_o as LBAudioDetectiveCorpusMatchProfile gives it --, 0 where none does;
+ *   P_r[o] = inPrevKeys[r][o + shift_r] while o + shift_r < n, else 0; 0 everywhere when inPrevKeys is NULL;
+ *   outKeys[r][o] = max(T_r[o], P_r[o]);
+ *   outLengths[r][o] = n_j of the entry the key names, looked up in the corpus: 0 for a zero key or an index outside the corpus.
+ * Every word of both outputs is written.  With inPrevKeys == NULL row r is the batch timeline's row r with only the tail cells
+ * counting: the form shards exchange, and shards merge by element-wise unsigned maximum as the timeline's do.
+ * INVARIANT: seed inPrevKeys with LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice on a channel's window; after every
+ * push whose new count is <= inMaxNew call this with the new window and the previous output.  Then outKeys and outLengths equal,
+ * bit for bit, what the batch timeline call writes for the new window -- for the same corpus contents, threshold, range and index
+ * base; ties go to the lowest index as there.  A count ABOVE inMaxNew still shifts by the true count but adds only the newest
+ * inMaxNew cells: the row then lacks the cells in between until they have slid out of the window (seed again instead).  The
+ * caller also seeds again after entries were removed from the corpus or a channel was reset; the state is the caller's two
+ * buffers, nothing is kept in the corpus.
+ * INDEPENDENCE: results do not depend on grid, launch order, passes, outLengths, or inMaxNew beyond the clamp.
+ * Refusals in the tail calls' order: what needs no handle first (a NULL pointer other than inPrevKeys and outLengths, inNewCounts
+ * not 4-byte aligned, inMaxNew 0 or above the cap, inThreshold, inIndexBase > 2^32, inRecordings x n > 2^31 - 1, and [inPrevKeys,
+ * + inRecordings x n x 8) overlapping [outKeys, + inRecordings x n x 8)), then kLBAudioDetectiveDeviceUnavailable, then what needs
+ * the corpus (not ragged, an entry above LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS, inIndexBase + entries > 2^32, a join scratch
+ * limit that holds no strip of one recording).  An empty corpus, or one with no entry that takes part, is noErr with the shifted
+ * previous rows and lengths looked up as above -- zeros without inPrevKeys.
+ * Asynchronous on inStream, which it never awaits; it waits ON THE DEVICE for the corpus' latest append; nothing visits the host.
+ * Per pass of recordings: the strips zeroed, one compute launch over all entries, one finishing launch (k_timeline_tail.hip).
+ * LBAudioDetectiveDebugTimelineTailPlan is the call's plan on the host -- it takes its own from the same function --; it needs
+ * neither device nor handle: the lanes per recording and the records of a recording's LDS window as
+ * LBAudioDetectiveDebugOccurrencesTailPlan gives them; the strip width min(longest entry, n) - shortest entry + lanes (0 where no
+ * entry takes part); the recordings per workgroup -- 256 / lanes, fewer where that many windows (36 bytes a record) and strips (8
+ * bytes a slot) with the table do not fit 160 KiB - 64 --; the LDS of a workgroup; the recordings per pass -- at most 65 535,
+ * blocks of 64 entries x recordings within 32 bits, and limit / (strip width x 8) (inScratchLimit 0: the default) --; and the
+ * scratch of a pass (recordings per pass x strip width x 8 bytes).  kLBAudioDetectiveArgumentInvalid for a shape the call refuses,
+ * a limit below one strip, or a NULL pointer. */
+OSStatus LBAudioDetectiveCorpusRecordingPackedTimelineTailBatchKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inPackedQueries,
+                                                                          UInt32 inRecordings, UInt32 inSubfingerprints,
+                                                                          const void* inNewCounts, UInt32 inMaxNew, UInt32 inRange,
+                                                                          Float32 inThreshold, UInt64 inIndexBase,
+                                                                          const void* inPrevKeys /* may be NULL */, void* outKeys,
+                                                                          void* outLengths /* may be NULL */, void* inStream);
+OSStatus LBAudioDetectiveDebugTimelineTailPlan(UInt32 inRecordings, UInt32 inSubfingerprints, UInt32 inShortestEntry, UInt32 inLongestEntry,
+                                               UInt64 inEntries, UInt32 inMaxNew, UInt64 inScratchLimit, UInt32* outLanes,
+                                               UInt32* outRecordingsPerWorkgroup, UInt32* outWindowRecords, UInt32* outStripWidth,
+                                               UInt64* outLdsBytes, UInt32* outRecordingsPerPass, UInt64* outScratchBytes);
 /* Recording segments: "what played when" from a timeline's per-offset winners, on the device -- non-overlapping spans per
  * recording, for one recording (inRecordings == 1) or a batch.  inKeys ([inRecordings][inSubfingerprints] UInt64) and inLengths
  * (the same shape, UInt32) are what LBAudioDetectiveCorpusRecordingPackedTimelineBatchKeysDevice or the single timeline calls

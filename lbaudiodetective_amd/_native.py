@@ -277,6 +277,11 @@ _SIGNATURES = {
                                                                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveDebugRecordingTailPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt64, UInt32, UInt64, UInt32, _P(UInt32), _P(UInt32),
                                                           _P(UInt32), _P(UInt64), _P(UInt32), _P(UInt64)]),
+    "LBAudioDetectiveCorpusRecordingPackedTimelineTailBatchKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt32, UInt32, C.c_void_p, UInt32, UInt32,
+                                                                                    Float32, UInt64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                                    C.c_void_p]),
+    "LBAudioDetectiveDebugTimelineTailPlan": (OSStatus, [UInt32, UInt32, UInt32, UInt32, UInt64, UInt32, UInt64, _P(UInt32), _P(UInt32),
+                                                         _P(UInt32), _P(UInt32), _P(UInt64), _P(UInt32), _P(UInt64)]),
     "LBAudioDetectiveTimelineSegmentsFromKeysDevice": (OSStatus, [C.c_void_p, C.c_void_p, UInt32, UInt32, UInt32, C.c_void_p, C.c_void_p,
                                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusRemoveIndices":(OSStatus, [Ref, _P(UInt64), UInt64, _P(UInt32), _P(UInt64)]),

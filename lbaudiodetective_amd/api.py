@@ -1756,6 +1756,45 @@ class Corpus:
             _dev_ptr(lengths_out) if lengths_out is not None else None, _stream_ptr(stream)), "CorpusRecordingPackedTimelineBatchKeysDevice")
         return keys_out, lengths_out
 
+    def recording_timeline_tail_batch_keys_device(self, packed, n_recordings: int, per_query: int, new_counts, threshold: float,
+                                                  max_new: int = None, prev_keys=None, keys_out=None, lengths_out=None,
+                                                  want_lengths: bool = True, range_: int = 0, index_base: int = 0, stream=None):
+        """LBAudioDetectiveCorpusRecordingPackedTimelineTailBatchKeysDevice: the timeline of n_recordings windows AFTER a push from
+        the timeline before it -> (keys int64 [n_recordings, per_query], lengths int32 of the same shape or None) on the device,
+        asynchronously on `stream`.  keys[r][o] is the unsigned maximum of prev_keys[r][o + min(new_counts[r], per_query)] (0
+        beyond the row, or without prev_keys) and the best cell at or above `threshold` among the cells the push completed at
+        offset o: the entries that end inside the newest min(new_counts[r], max_new, per_query) sub-fingerprints, keyed as
+        recording_timeline_batch_keys_device keys them; lengths[r][o] is the length of the entry the key names (0 for a zero key
+        or an index outside the corpus).  Seeded with recording_timeline_batch_keys_device and called after every push whose
+        counts are <= max_new, the output equals that call on the new windows, bit for bit.  A count above max_new shifts by the
+        true count but adds only the newest max_new cells: seed again instead (LiveTimeline does).  prev_keys must not overlap
+        keys_out.  new_counts / max_new as the tail occurrences method takes them.  want_lengths=False (and no lengths_out)
+        passes NULL: the keys are the same.  Shards of contiguous index ranges merge by torch.maximum of their keys.  Decode
+        with decode_timeline_batch_keys."""
+        R, per = int(n_recordings), int(per_query)
+        _packed_ok(packed, R, per)
+        d_new, max_new = self._tail_new_counts(packed, R, new_counts, max_new, stream)
+        dev = packed.device if hasattr(packed, "device") else "cuda"
+        n = R * per
+        if prev_keys is not None:
+            _out_ok(prev_keys, n, "prev_keys")
+        if keys_out is None or (want_lengths and lengths_out is None):
+            import torch
+            with torch.cuda.stream(stream):              # (the blocks belong to the stream that fills them)
+                if keys_out is None:
+                    keys_out = torch.empty(max(1, n), dtype=torch.int64, device=dev)[:n].reshape(R, per)
+                if want_lengths and lengths_out is None:
+                    lengths_out = torch.empty(max(1, n), dtype=torch.int32, device=dev)[:n].reshape(R, per)
+        _out_ok(keys_out, n, "keys_out")
+        if lengths_out is not None:
+            _out_ok(lengths_out, n, "lengths_out")
+        _check(self._L.LBAudioDetectiveCorpusRecordingPackedTimelineTailBatchKeysDevice(
+            self._ref, _dev_ptr(packed), R, per, _dev_ptr(d_new), max_new, range_, threshold, index_base,
+            _dev_ptr(prev_keys) if prev_keys is not None else None, _dev_ptr(keys_out),
+            _dev_ptr(lengths_out) if lengths_out is not None else None, _stream_ptr(stream)),
+            "CorpusRecordingPackedTimelineTailBatchKeysDevice")
+        return keys_out, lengths_out
+
     def recording_segments_batch_keys_device(self, packed, n_recordings: int, per_query: int, threshold: float, capacity: int,
                                              range_: int = 0, index_base: int = 0, stream=None):
         """What played when in n_recordings recordings at once: recording_timeline_batch_keys_device, then
@@ -2327,6 +2366,78 @@ def debug_recording_tail_plan(n_recordings: int, per_query: int, longest_entry: 
            "DebugRecordingTailPlan")
     return {"lanes": lanes.value, "recordings_per_workgroup": rpw.value, "window_records": win.value, "lds_bytes": lds.value,
             "recordings_per_pass": rpp.value, "scratch_bytes": scratch.value}
+
+
+def debug_timeline_tail_plan(n_recordings: int, per_query: int, shortest_entry: int, longest_entry: int, entries: int, max_new: int,
+                             scratch_limit: int = 0) -> dict:
+    """LBAudioDetectiveDebugTimelineTailPlan: the host plan of one timeline tail call -- the one the call itself takes -- as a dict:
+    lanes per recording and window_records of a recording in LDS (debug_occurrences_tail_plan's), strip_width (the 64-bit
+    accumulators of a recording: min(longest_entry, per_query) - shortest_entry + lanes; 0 where no entry takes part),
+    recordings_per_workgroup (fewer than the tail plan's where the strips do not fit beside the windows), lds_bytes of a workgroup,
+    recordings_per_pass, scratch_bytes of a pass (its strips).  scratch_limit 0: the default.  Raises for a shape the call refuses
+    or a limit below one recording's strip.  Needs no GPU."""
+    lanes, rpw, win, width, rpp = N.UInt32(0), N.UInt32(0), N.UInt32(0), N.UInt32(0), N.UInt32(0)
+    lds, scratch = N.UInt64(0), N.UInt64(0)
+    _check(N.lib().LBAudioDetectiveDebugTimelineTailPlan(int(n_recordings), int(per_query), int(shortest_entry), int(longest_entry),
+                                                         int(entries), int(max_new), int(scratch_limit), C.byref(lanes), C.byref(rpw),
+                                                         C.byref(win), C.byref(width), C.byref(lds), C.byref(rpp), C.byref(scratch)),
+           "DebugTimelineTailPlan")
+    return {"lanes": lanes.value, "recordings_per_workgroup": rpw.value, "window_records": win.value, "strip_width": width.value,
+            "lds_bytes": lds.value, "recordings_per_pass": rpp.value, "scratch_bytes": scratch.value}
+
+
+class LiveTimeline:
+    """The timeline of the n most recent sub-fingerprints of the listed channels of a StreamBank, kept current from each push:
+    what StreamBank.timeline(corpus, channels, n, threshold, ...) returns after every push, bit for bit, for the work of the
+    push's new cells alone.  The state is two pairs of device buffers that take turns; nothing is kept in the bank or the corpus,
+    and nothing is read back.  The CALLER calls reseed() after entries were removed from the corpus (the keys name indices) or a
+    listed channel was reset; entries appended to the corpus count from the push behind them on, for the cells that push
+    completes -- reseed() to have them judged against the whole window."""
+
+    def __init__(self, bank: "StreamBank", corpus: "Corpus", channels, n: int, threshold: float, max_new: int = 8, range_: int = 0,
+                 index_base: int = 0):
+        self.bank, self.corpus = bank, corpus
+        self.channels = _u32_list(channels)[0].copy()
+        self.n, self.threshold, self.max_new = int(n), float(threshold), int(max_new)
+        self.range_, self.index_base = int(range_), int(index_base)
+        if not 1 <= self.max_new <= 64:
+            raise ValueError("max_new must be 1 .. 64")
+        self._state = None                               # (keys, lengths) of the latest update
+        self._spare = None                               # the pair the next update writes
+
+    def reseed(self) -> None:
+        """The next update computes the whole timeline again (StreamBank.timeline)."""
+        self._state = None
+
+    def update(self, new_counts, stream=None):
+        """After a push: new_counts is what push / push_device returned (one value per channel of the BANK, on the host).
+        Returns (keys int64 [len(channels), n], lengths int32 of the same shape) on the device, asynchronously on `stream`: the
+        current timeline.  The first call, the call after reseed() and any call where a listed channel's count exceeds max_new
+        go through StreamBank.timeline; every other call is window_device and
+        Corpus.recording_timeline_tail_batch_keys_device from the previous state, on ONE stream with nothing in between.  The
+        tensors returned are the state: they are read by the next update and written again by the one after it."""
+        mine = np.asarray(new_counts).reshape(-1)[self.channels].astype(np.int64)
+        out = self._spare
+        if self._state is None or (mine.size and int(mine.max()) > self.max_new):
+            packed = self.bank.window_device(self.channels, self.n, stream=stream)
+            fresh = self.corpus.recording_timeline_batch_keys_device(
+                packed, packed.shape[0], self.n, self.threshold, range_=self.range_, index_base=self.index_base,
+                keys_out=out[0] if out else None, lengths_out=out[1] if out else None, stream=stream)
+        else:
+            packed = self.bank.window_device(self.channels, self.n, stream=stream)
+            fresh = self.corpus.recording_timeline_tail_batch_keys_device(
+                packed, packed.shape[0], self.n, mine, self.threshold, max_new=self.max_new, prev_keys=self._state[0],
+                keys_out=out[0] if out else None, lengths_out=out[1] if out else None, range_=self.range_,
+                index_base=self.index_base, stream=stream)
+        self._spare, self._state = self._state, fresh
+        return fresh
+
+    def segments(self, capacity: int, stream=None):
+        """timeline_segments_device on the current state: what StreamBank.segments returns for the same windows."""
+        if self._state is None:
+            raise RuntimeError("LiveTimeline.segments before the first update")
+        return timeline_segments_device(self._state[0], self._state[1], capacity, stream=stream)
+
 
 class Comm:
     """An RCCL communicator made through the library's helpers (ncclCommInitRank with the current device).

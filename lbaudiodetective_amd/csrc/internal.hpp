@@ -620,6 +620,39 @@ void recording_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_max, uin
 // call.tiles == 1.  One launch on the call's stream, no scratch.
 hipError_t launch_recording_tail(const RecordingCall& call, const RecordingTailPlan& plan, uint32_t recordings, const uint32_t* d_new_counts,
                                  uint32_t max_new, uint64_t entries, uint64_t pitch);
+// timeline tail (k_timeline_tail.hip): the tail occurrences' cells at or above a threshold folded per (recording, OFFSET) to the
+// largest key  q_o bits << 32 | 0xFFFFFFFF - (index base + entry)  -- the batch timeline's key of that cell -- and merged by
+// unsigned maximum with the previous timeline shifted left by the recording's new count.  A cell of an entry of n_j sub-fingerprints
+// at offset o lies at slot (n_query - o) - shortest entry of a recording's STRIP of `strip_width` 64-bit accumulators.
+struct TimelineTailPlan {
+    uint32_t lanes = 0;                  // occurrences_tail_shape's lanes and sub-window
+    uint32_t recordings_per_workgroup = 0;   // 256 / D, fewer where that many sub-windows AND strips do not fit the LDS (at least 1)
+    uint32_t window_records = 0;
+    uint32_t strip_width = 0;            // min(ne_max, n_query) - ne_min + D; 0: no entry takes part
+    uint64_t lds_bytes = 0;              // windows + table, rounded up to 8 bytes, + recordings_per_workgroup x strip_width x 8
+    uint32_t recordings_per_pass = 0;
+    uint64_t scratch_bytes = 0;          // recordings_per_pass x strip_width x 8: the pass' strips
+};
+// the five fields a workgroup's shape is (plan.cpp): what the launch holds the plan against
+void timeline_tail_shape(uint32_t per, uint32_t ne_min, uint32_t ne_max, uint32_t max_new, TimelineTailPlan* plan);
+// THE plan of a call, the debug symbol's and the real call's (plan.cpp): the shape above; the recordings of a pass are the smallest
+// of the recordings, 65 535, what keeps the units (blocks of entries x recordings) within 32 bits, and limit / (strip_width x 8)
+// (0: kJoinScratchDefault).  The strips do not grow with the entries, so a pass takes ALL entries in one launch.  false: the limit
+// holds no strip of one recording.  An empty corpus or ne_min > per: no strip, all recordings, no scratch.  1 <= max_new <= 64.
+bool timeline_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uint32_t ne_max, uint64_t entries, uint32_t max_new,
+                        uint64_t limit_bytes, TimelineTailPlan* plan);
+// one pass' cells: `recordings` recordings from call.d_qwords on with their new counts from d_new_counts on, every entry of the
+// corpus, into d_strips [recordings][plan.strip_width], ZEROED by the caller, with atomic maxima.  call.tiles == 1, call.ne_min <=
+// call.n_query.  One launch on the call's stream.
+hipError_t launch_timeline_tail_cells(const TimelineCall& call, const TimelineTailPlan& plan, uint32_t recordings,
+                                      const uint32_t* d_new_counts, uint32_t max_new, uint64_t entries, unsigned long long* d_strips);
+// one pass' rows: keys[r][o] = max(strip of r at (per - o) - ne_min (0 outside it, or with d_strips == nullptr), d_prev[r][o +
+// min(new count, per)] (0 beyond the row, or with d_prev == nullptr)), and where wanted the lengths of the entries the keys name
+// (0 for a zero key or an index outside the corpus).  Every word of `recordings` rows written.  One launch.
+hipError_t launch_timeline_tail_finish(const unsigned long long* d_strips, uint32_t strip_width, uint32_t ne_min, uint32_t recordings,
+                                       uint32_t per, const uint32_t* d_new_counts, const unsigned long long* d_prev, uint64_t index_base,
+                                       uint64_t count, const uint32_t* d_off, unsigned long long* d_keys, uint32_t* d_lengths,
+                                       hipStream_t stream);
 
 // threshold selection over ANY number of rows (k_occurrences_batch.hip): launch_threshold_keys' results -- per row of n scores the
 // keys of the entries whose score is >= threshold in ascending entry index, the first min(count, capacity) of them to d_keys + r *

@@ -283,4 +283,46 @@ void recording_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_max, uin
     plan->scratch_bytes = key_form ? recs * entries * 8u : 0;
 }
 
+// The timeline tail's plan (k_timeline_tail.hip; internal.hpp states it): the tail occurrences' lanes and sub-window, a strip of
+// 64-bit accumulators beside every sub-window of a workgroup, and the recordings of a pass.  The strips do not grow with the
+// entries, so a pass is ONE launch over all entries.
+void timeline_tail_shape(uint32_t per, uint32_t ne_min, uint32_t ne_max, uint32_t max_new, TimelineTailPlan* plan) {
+    OccurrencesTailPlan shape;
+    occurrences_tail_shape(per, ne_max, max_new, &shape);
+    const uint64_t ne_b = ne_max < per ? ne_max : per;
+    const uint64_t width = ne_min != 0 && ne_min <= ne_b ? ne_b - ne_min + shape.lanes : 0;
+    const uint64_t win = shape.window_records;
+    uint64_t fit = kTailThreads / shape.lanes;
+    const uint64_t one = win * kTailRecBytes + width * 8u;     // a recording's sub-window and strip
+    if (one != 0 && (kTailLdsBudget - kTailTableBytes - 4u) / one < fit) fit = (kTailLdsBudget - kTailTableBytes - 4u) / one;
+    plan->lanes = shape.lanes;
+    plan->recordings_per_workgroup = (uint32_t)fit;
+    plan->window_records = (uint32_t)win;
+    plan->strip_width = (uint32_t)width;
+    plan->lds_bytes = ((fit * win * kTailRecBytes + kTailTableBytes + 7u) & ~7ull) + fit * width * 8u;
+}
+static_assert((uint64_t)(LBAD_OCCURRENCES_MAX_ENTRY_SUBFINGERPRINTS + LBAD_OCCURRENCES_TAIL_MAX_NEW - 1) * (kTailRecBytes + 8u) + kTailTableBytes + 4u <=
+                  kTailLdsBudget,
+              "one recording's longest sub-window, its widest strip and the table fit a CU's LDS");
+
+bool timeline_tail_plan(uint32_t recordings, uint32_t per, uint32_t ne_min, uint32_t ne_max, uint64_t entries, uint32_t max_new,
+                        uint64_t limit_bytes, TimelineTailPlan* plan) {
+    *plan = TimelineTailPlan();
+    timeline_tail_shape(per, entries ? ne_min : 0, ne_max, max_new, plan);
+    plan->recordings_per_pass = recordings;
+    if (entries == 0 || plan->strip_width == 0) return true;
+    const uint64_t limit = limit_bytes ? limit_bytes : kJoinScratchDefault;
+    const uint64_t one = (uint64_t)plan->strip_width * 8u;
+    if (limit < one) return false;                             // the limit holds no strip of ONE recording
+    const uint64_t block = occurrences_block_entries();
+    const uint64_t blocks = (entries + block - 1) / block;
+    uint64_t recs = recordings;
+    if (recs > kTailMaxRecs) recs = kTailMaxRecs;
+    if (recs > kTailMaxItems / blocks) recs = kTailMaxItems / blocks;      // (>= 1: at most 2^26 blocks) units never exceed blocks x recs
+    if (recs > limit / one) recs = limit / one;
+    plan->recordings_per_pass = (uint32_t)recs;
+    plan->scratch_bytes = recs * one;
+    return true;
+}
+
 }  // namespace lbad

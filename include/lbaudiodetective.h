@@ -1303,6 +1303,64 @@ OSStatus LBAudioDetectiveTimelineSegmentsFromKeysDevice(const void* inKeys /* de
                                                         void* outKeys /* device, [inRecordings][inCapacity] UInt64 */,
                                                         void* outLengths /* device, [inRecordings][inCapacity] UInt32, may be NULL */,
                                                         void* outCounts /* device, [inRecordings] UInt32 */, void* inStream);
+/* Occurrence segments: "what played when" over ALL matching cells, on the device -- the call above sees one candidate per offset
+ * (the timeline's winner) and so never reports the second best entry at an offset, even where the winner there loses to a better
+ * overlapping span; this call runs the same greedy over the rows of an occurrences call, where any number of entries may start
+ * at one offset.  inKeys / inLags ([inRecordings][inCapacity] UInt64 / SInt32) are what
+ * LBAudioDetectiveCorpusQueryPackedOccurrencesBatchKeysDevice or the single occurrences calls write (with inPeaksOnly one cell per
+ * airing), inLengths (same shape, UInt32) the sub-fingerprints of the entry each key names, as
+ * LBAudioDetectiveCorpusEntryLengthsFromKeysDevice (below) writes them, inCounts ([inRecordings] UInt64, may be NULL) the
+ * occurrences calls' counts.  Shards concatenate their rows, each with the lengths of its own keys, and pass inCounts NULL: zero
+ * keys between the shards' cells are no candidates.
+ * Independently per recording r.  The slots p < m are considered, m = min(inCounts[r], inCapacity), or inCapacity without
+ * inCounts; non-zero keys behind m are ignored.  A slot is a candidate when its key is non-zero, its length is non-zero and its
+ * span [s, e) is not empty: s = max(0, -lag), e = min(inSubfingerprints, -lag + length), in 64-bit signed arithmetic (any lag
+ * word is harmless), with s < inSubfingerprints and s < e.  With the occurrences' lag convention lag = -o places the entry at
+ * offset o of the recording, and lag = +o says that the recording lies inside a longer entry, which then spans the whole
+ * recording.  The candidates are visited in descending 64-bit key order (higher score bits, then lower entry index), equal keys
+ * at the lower s first, equal keys and s at the lower slot first, and a candidate is accepted when its span meets no span
+ * accepted before it -- spans that only touch do not meet, and nothing of another recording ever blocks an offset.  This is what
+ * occurrence_segments of the Python interface computes on the host.
+ * Row r of outStarts / outKeys / outLags / outLengths ([inRecordings][inOutCapacity]; outLags and outLengths may each be NULL and
+ * change nothing else) holds the accepted spans in ascending start order in slots 0 .. min(count, inOutCapacity) - 1: s, then
+ * key, lag and length UNCHANGED -- so LBAudioDetectiveCorpusIdsFromKeysDevice, ...GatherKeysDevice, ...AlignKeysDevice and
+ * ...RemoveKeysDevice read outKeys as it is; accepted spans do not overlap, so the starts are distinct.  Zeros stand behind them
+ * and every word of every row is written.  outCounts[r] is the TRUE number of spans, never cut.  A row of the occurrences call
+ * that overflowed (its count above inCapacity) was cut in (entry, offset) order before this greedy ran: raise the capacity or the
+ * threshold, or ask for peaks only.
+ * The call takes no handle and needs no scratch: one launch (k_occurrence_segments.hip: a workgroup per recording, its state in
+ * 14 x n2 + 2.25 x inSubfingerprints bytes of LDS and a little, n2 the power of two >= max(inCapacity, 64) -- 133 640 bytes at
+ * both caps), asynchronous on inStream, which it never awaits.  Results do not depend on grid, launch order, stream or which of
+ * the optional outputs are NULL.  The outputs must overlap no input.
+ * Refusals, each kLBAudioDetectiveArgumentInvalid and decided before anything touches a device: a NULL pointer other than
+ * inCounts, outLags or outLengths; inRecordings, inCapacity, inSubfingerprints or inOutCapacity 0; inSubfingerprints >
+ * LBAD_SEGMENTS_MAX_SUBFINGERPRINTS; inCapacity > LBAD_OCCURRENCE_SEGMENTS_MAX_CANDIDATES; inRecordings x inCapacity,
+ * inRecordings x inSubfingerprints or inRecordings x inOutCapacity above 2^31 - 1; a pointer not aligned to its element (8 bytes
+ * for the key blocks and inCounts, 4 for the others); outKeys == inKeys, outLags == inLags or outLengths == inLengths.  Then a
+ * missing device is kLBAudioDetectiveDeviceUnavailable.
+ * LBAudioDetectiveCorpusEntryLengthsFromKeysDevice: outLengths[i] (UInt32, device) = the sub-fingerprints of the entry inKeys[i]
+ * names (the low word is 0xFFFFFFFF - (inIndexBase + index), the score word is ignored), 0 for a zero key and for an index
+ * outside [inIndexBase, inIndexBase + entries) -- a ragged corpus' own entry lengths, a uniform corpus' one length.  A shard
+ * serves exactly the keys of its own range.  1 <= inCount <= 2^31 - 1; asynchronous on inStream, which it never awaits; it waits
+ * ON THE DEVICE for the corpus' latest append, and like every other call it must not run concurrently with a removal.  A NULL
+ * handle or pointer, inCount 0 or above 2^31 - 1, inIndexBase > 2^32 and a pointer not aligned to its element are
+ * kLBAudioDetectiveArgumentInvalid, decided before a handle is read; then a missing device is
+ * kLBAudioDetectiveDeviceUnavailable; then inIndexBase + entries > 2^32 is kLBAudioDetectiveArgumentInvalid. */
+#define LBAD_OCCURRENCE_SEGMENTS_MAX_CANDIDATES 8192
+OSStatus LBAudioDetectiveOccurrenceSegmentsFromKeysDevice(const void* inKeys /* device, [inRecordings][inCapacity] UInt64 */,
+                                                          const void* inLags /* device, same shape, SInt32 */,
+                                                          const void* inLengths /* device, same shape, UInt32 */,
+                                                          const void* inCounts /* device, [inRecordings] UInt64, may be NULL */,
+                                                          UInt32 inRecordings, UInt32 inCapacity, UInt32 inSubfingerprints,
+                                                          UInt32 inOutCapacity,
+                                                          void* outStarts /* device, [inRecordings][inOutCapacity] UInt32 */,
+                                                          void* outKeys /* device, same shape, UInt64 */,
+                                                          void* outLags /* device, same shape, SInt32, may be NULL */,
+                                                          void* outLengths /* device, same shape, UInt32, may be NULL */,
+                                                          void* outCounts /* device, [inRecordings] UInt32 */, void* inStream);
+OSStatus LBAudioDetectiveCorpusEntryLengthsFromKeysDevice(LBAudioDetectiveCorpusRef inCorpus, const void* inKeys /* device */,
+                                                          UInt64 inCount, UInt64 inIndexBase, void* outLengths /* device */,
+                                                          void* inStream);
 /* Removal: entries taken out of a corpus on the device, the other half of the corpus life cycle -- the take-down of one
  * recording, or the action behind a join's duplicate pairs.  Both forms, both kinds of corpus (uniform of any shape, ragged):
  * the named entries go, the others keep their relative order and close up -- the entry at old index i gets the new index

@@ -26,6 +26,7 @@ PACKED_BYTES = 32
 SHARD_KEYS = 4096          # LBAD_SHARD_KEYS: queries per exchange of a sharded query
 ROWS_PER_FRAME = 128
 SEGMENTS_MAX_SUBFINGERPRINTS = 8192   # LBAD_SEGMENTS_MAX_SUBFINGERPRINTS: offsets of one recording of the segments call
+OCCURRENCE_SEGMENTS_MAX_CANDIDATES = 8192   # LBAD_OCCURRENCE_SEGMENTS_MAX_CANDIDATES: slots of one row of the occurrence segments call
 
 
 class AudioStreamBasicDescription(C.Structure):
@@ -284,6 +285,10 @@ _SIGNATURES = {
                                                          _P(UInt32), _P(UInt32), _P(UInt64), _P(UInt32), _P(UInt64)]),
     "LBAudioDetectiveTimelineSegmentsFromKeysDevice": (OSStatus, [C.c_void_p, C.c_void_p, UInt32, UInt32, UInt32, C.c_void_p, C.c_void_p,
                                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveOccurrenceSegmentsFromKeysDevice": (OSStatus, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, UInt32, UInt32, UInt32,
+                                                                    UInt32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                    C.c_void_p]),
+    "LBAudioDetectiveCorpusEntryLengthsFromKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveCorpusRemoveIndices":(OSStatus, [Ref, _P(UInt64), UInt64, _P(UInt32), _P(UInt64)]),
     "LBAudioDetectiveCorpusRemoveKeysDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, _P(UInt64), C.c_void_p]),
     "LBAudioDetectiveCorpusSetRemoveScratchLimit": (OSStatus, [Ref, UInt64]),

@@ -698,6 +698,18 @@ class StreamBank:
                                                                  range_=range_, index_base=index_base, want_lags=want_lags,
                                                                  stream=stream)
 
+    def occurrence_segments(self, corpus: "Corpus", channels, n: int, threshold: float, capacity: int, out_capacity: int,
+                            peaks: bool = True, range_: int = 0, index_base: int = 0, stream=None):
+        """What played when on every listed channel, over ALL matching cells: window_device, then
+        Corpus.recording_occurrence_segments_batch_keys_device on its output, on ONE stream with nothing in between.  Returns
+        (starts int32, keys int64, lags int32, lengths int32, all [len(channels), out_capacity], counts int32 [len(channels)],
+        occurrence_counts int64 [len(channels)]): per channel the non-overlapping spans of its window of n sub-fingerprints in
+        start order, and the number of cells its occurrences row would hold -- above `capacity` the row was cut before the
+        greedy ran."""
+        packed = self.window_device(channels, n, stream=stream)
+        return corpus.recording_occurrence_segments_batch_keys_device(packed, packed.shape[0], n, threshold, capacity, out_capacity,
+                                                                      peaks=peaks, range_=range_, index_base=index_base, stream=stream)
+
     def new_occurrences(self, corpus: "Corpus", channels, n: int, new_counts, threshold: float, capacity: int, max_new: int = None,
                         range_: int = 0, index_base: int = 0, want_lags: bool = True, stream=None):
         """The matches the latest push completed on every listed channel: window_device, then
@@ -1837,6 +1849,58 @@ class Corpus:
         an overlapping better span."""
         return timeline_segments(*self.recording_timeline(fp, threshold, range_))
 
+    def entry_lengths_from_keys_device(self, keys, index_base: int = 0, out=None, stream=None):
+        """LBAudioDetectiveCorpusEntryLengthsFromKeysDevice: 64-bit keys on the device, exactly as every key call writes them -> an
+        int32 device tensor in the keys' shape (the bits of a UInt32): the sub-fingerprints of the entry each key names, 0 for a
+        zero key or an index outside [index_base, index_base + len(self)).  What occurrence_segments_device takes as lengths; a
+        shard serves the keys of its own range.  Asynchronous on `stream`."""
+        import torch
+        assert keys.is_cuda and keys.is_contiguous() and keys.element_size() == 8
+        n = keys.numel()
+        if out is None:
+            with torch.cuda.stream(stream):              # (the block belongs to the stream that fills it)
+                out = torch.empty(max(1, n), dtype=torch.int32, device=keys.device)[:n].reshape(keys.shape)
+        assert out.element_size() == 4
+        _out_ok(out, n, "out")
+        _check(self._L.LBAudioDetectiveCorpusEntryLengthsFromKeysDevice(self._ref, _dev_ptr(keys), n, index_base, _dev_ptr(out),
+                                                                       _stream_ptr(stream)), "CorpusEntryLengthsFromKeysDevice")
+        return out
+
+    def recording_occurrence_segments_batch_keys_device(self, packed, n_recordings: int, per_query: int, threshold: float, capacity: int,
+                                                        out_capacity: int, peaks: bool = True, range_: int = 0, index_base: int = 0,
+                                                        stream=None):
+        """What played when in n_recordings recordings at once, over ALL matching cells: query_packed_occurrences_batch_keys_device
+        (rows of `capacity` slots, <= 8192; with peaks one cell per airing), entry_lengths_from_keys_device on its keys, then
+        occurrence_segments_device, on ONE stream with nothing read back (per_query <= 8192).  Returns (starts int32, keys int64,
+        lags int32, lengths int32, all [n_recordings, out_capacity], counts int32 [n_recordings], occurrence_counts int64
+        [n_recordings]) on the device: row r holds the non-overlapping spans of recording r in start order, zeros behind them;
+        counts are never cut.  occurrence_counts are the occurrences call's own: where occurrence_counts[r] > capacity the row
+        was CUT in (entry, offset) order before the greedy ran, and its spans are those of the cells that were kept -- raise the
+        capacity or the threshold.  Decode with decode_occurrence_segments(..., index_base).  The blocks in between are allocated
+        under `stream`, like the outputs."""
+        R, per = int(n_recordings), int(per_query)
+        keys, lags, occ_counts = self.query_packed_occurrences_batch_keys_device(packed, R, per, threshold, capacity, peaks=peaks,
+                                                                                 range_=range_, index_base=index_base, stream=stream)
+        lengths = self.entry_lengths_from_keys_device(keys, index_base=index_base, stream=stream)
+        return occurrence_segments_device(keys, lags, lengths, occ_counts, per, out_capacity, stream=stream) + (occ_counts,)
+
+    def recording_occurrence_segments(self, fp: Fingerprint, threshold: float, range_: int = 0, peaks: bool = True):
+        """What played when, over ALL matching cells: (start, index, score, lag, length) arrays of non-overlapping spans of the
+        query sorted by start -- occurrence_segments of the query's occurrences (with peaks, the default, one cell per airing),
+        computed on the device and decoded.  Where recording_segments sees the best entry per offset only, this reports the second
+        best at an offset when the winner there loses to a better overlapping span.  The query has at most 8192 sub-fingerprints;
+        more than 8192 matching cells raise ValueError: raise the threshold or keep peaks on."""
+        n = fp.number_of_subfingerprints
+        cap = N.OCCURRENCE_SEGMENTS_MAX_CANDIDATES
+        if not 1 <= n <= N.SEGMENTS_MAX_SUBFINGERPRINTS:
+            raise ValueError(f"the query must have 1 .. {N.SEGMENTS_MAX_SUBFINGERPRINTS} sub-fingerprints")
+        keys, lags, count = self.query_occurrences_keys_device(fp, threshold, cap, peaks=peaks, range_=range_)
+        lengths = self.entry_lengths_from_keys_device(keys)
+        rows = occurrence_segments_device(keys, lags, lengths, count, n, n)
+        if int(count.cpu().reshape(-1)[0]) > cap:
+            raise ValueError(f"more than {cap} matching cells: raise the threshold or use peaks")
+        return decode_occurrence_segments(*rows)
+
     def set_join_scratch_limit(self, n_bytes: int):
         """bytes of device memory the join's scratch may take, and thereby the rows per chunk; 0 restores the default"""
         _check(self._L.LBAudioDetectiveCorpusSetJoinScratchLimit(self._ref, n_bytes), "CorpusSetJoinScratchLimit")
@@ -2731,6 +2795,121 @@ def decode_segments(starts, keys, lengths, counts, index_base: int = 0):
         idx = (0xFFFFFFFF - (k[r, :m] & np.uint64(0xFFFFFFFF))).astype(np.int64) - int(index_base)
         sc = (k[r, :m] >> np.uint64(32)).astype(np.uint32).view(np.float32)
         out.append((st[r, :m].copy(), idx, sc, ln[r, :m].copy() if ln is not None else None))
+    return out[0] if one else out
+
+
+def occurrence_segments(indices, scores, lags, lengths, n):
+    """Non-overlapping spans over ALL cells of one recording of n sub-fingerprints, from an occurrences call's matches (indices,
+    scores and lags as Corpus.query_occurrences or decode_occurrence_keys give them; an index below 0 is no cell) and the
+    sub-fingerprints of the entry each cell names.  Cell p spans [s, e) with s = max(0, -lag), e = min(n, -lag + length); cells
+    with length 0, s >= n or e <= s are no candidates.  The candidates are visited in descending key order (higher score bits,
+    then lower index), ties to the lower s, then the lower position p, and one is accepted when its span meets no accepted span
+    (spans that only touch do not meet).  Returns (start int64[m], index int64[m], score float32[m], lag int32[m], length
+    uint32[m]) sorted by start.  Unlike timeline_segments this sees every cell, so the second best entry at an offset is
+    reported where the winner there loses to a better overlapping span."""
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    sc = np.ascontiguousarray(np.asarray(scores, dtype=np.float32).reshape(-1))
+    lg = np.asarray(lags).reshape(-1).astype(np.int64)
+    ln = np.asarray(lengths).reshape(-1).astype(np.int64) & 0xFFFFFFFF
+    n = int(n)
+    s = np.maximum(0, -lg)
+    e = np.minimum(n, -lg + ln)
+    at = np.flatnonzero((idx >= 0) & (ln > 0) & (s < n) & (e > s))
+    bits = sc.view(np.uint32).astype(np.int64)
+    # (descending score bits, ascending index, ascending start, ascending position; lexsort's last key is the primary one)
+    order = at[np.lexsort((at, s[at], idx[at], -bits[at]))]
+    taken = np.zeros(max(n, 0), dtype=bool)
+    kept = []
+    for p in order:
+        if taken[s[p]:e[p]].any():
+            continue
+        taken[s[p]:e[p]] = True
+        kept.append(int(p))
+    kept = np.asarray(sorted(kept, key=lambda p: s[p]), dtype=np.int64)
+    return s[kept].astype(np.int64), idx[kept], sc[kept], lg[kept].astype(np.int32), ln[kept].astype(np.uint32)
+
+
+def occurrence_segments_device(keys, lags, lengths, counts, n: int, capacity: int, starts_out=None, keys_out=None, lags_out=None,
+                               lengths_out=None, counts_out=None, want_lags: bool = True, want_lengths: bool = True, stream=None):
+    """LBAudioDetectiveOccurrenceSegmentsFromKeysDevice: occurrence_segments on the device, for the rows of an occurrences call --
+    keys int64 / lags int32 / lengths int32 (Corpus.entry_lengths_from_keys_device of the keys), [slots] for one recording of n
+    sub-fingerprints or [recordings, slots] for a batch (slots <= 8192, n <= 8192), and counts: the occurrences call's int64
+    counts ([recordings] or one value), or None for every slot of a row (concatenated shards' rows) -> (starts int32, keys int64,
+    lags int32 or None, lengths int32 or None, all [recordings, capacity], counts int32 [recordings]) on the device,
+    asynchronously on `stream`; for 1-D input the rows themselves ([capacity], ..., a scalar tensor).  A row holds its recording's
+    non-overlapping spans in start order, key, lag and length unchanged -- ids_from_keys_device, gather_keys_device,
+    align_keys_device and remove_keys_device read the key block as it is -- zeros behind them; counts are the true numbers of
+    spans, never cut at `capacity`.  want_lags=False / want_lengths=False (and no such output given) pass NULL: the other outputs
+    are the same.  Decode with decode_occurrence_segments."""
+    import torch
+    if keys.dim() not in (1, 2) or tuple(lags.shape) != tuple(keys.shape) or tuple(lengths.shape) != tuple(keys.shape):
+        raise ValueError("keys, lags and lengths must be 1-D or 2-D tensors of one shape")
+    for x, kinds, what in ((keys, (torch.int64, getattr(torch, "uint64", torch.int64)), "keys (int64 or uint64)"),
+                           (lags, (torch.int32,), "lags (int32)"),
+                           (lengths, (torch.int32, getattr(torch, "uint32", torch.int32)), "lengths (int32 or uint32)")):
+        if not (x.is_cuda and x.is_contiguous() and x.dtype in kinds):
+            raise ValueError(f"{what} must be a contiguous device tensor")
+    R, slots = (1, keys.shape[0]) if keys.dim() == 1 else (keys.shape[0], keys.shape[1])
+    if counts is not None:
+        if not (counts.is_cuda and counts.is_contiguous() and counts.dtype in (torch.int64, getattr(torch, "uint64", torch.int64))
+                and counts.numel() >= R):
+            raise ValueError("counts must be a contiguous int64 device tensor with one value per recording")
+    cap = int(capacity)
+    if (starts_out is None or keys_out is None or counts_out is None or (want_lags and lags_out is None)
+            or (want_lengths and lengths_out is None)):
+        with torch.cuda.stream(stream):                 # (the blocks belong to the stream that fills them)
+            shape = (max(1, R), max(1, cap))
+            if starts_out is None:
+                starts_out = torch.empty(shape, dtype=torch.int32, device=keys.device)
+            if keys_out is None:
+                keys_out = torch.empty(shape, dtype=torch.int64, device=keys.device)
+            if want_lags and lags_out is None:
+                lags_out = torch.empty(shape, dtype=torch.int32, device=keys.device)
+            if want_lengths and lengths_out is None:
+                lengths_out = torch.empty(shape, dtype=torch.int32, device=keys.device)
+            if counts_out is None:
+                counts_out = torch.empty(max(1, R), dtype=torch.int32, device=keys.device)
+    _out_ok(starts_out, R * cap, "starts_out")
+    _out_ok(keys_out, R * cap, "keys_out")
+    _out_ok(counts_out, R, "counts_out")
+    for x, what in ((lags_out, "lags_out"), (lengths_out, "lengths_out")):
+        if x is not None:
+            _out_ok(x, R * cap, what)
+    _check(N.lib().LBAudioDetectiveOccurrenceSegmentsFromKeysDevice(
+        _dev_ptr(keys), _dev_ptr(lags), _dev_ptr(lengths), _dev_ptr(counts) if counts is not None else None, R, slots, int(n), cap,
+        _dev_ptr(starts_out), _dev_ptr(keys_out), _dev_ptr(lags_out) if lags_out is not None else None,
+        _dev_ptr(lengths_out) if lengths_out is not None else None, _dev_ptr(counts_out), _stream_ptr(stream)),
+        "OccurrenceSegmentsFromKeysDevice")
+    if keys.dim() == 1:                                  # (outputs given as [capacity] or [1, capacity]: the row either way)
+        def row(x):
+            return x.reshape(-1)[:cap] if hasattr(x, "reshape") else x
+        return (row(starts_out), row(keys_out), (row(lags_out) if lags_out is not None else None),
+                (row(lengths_out) if lengths_out is not None else None),
+                counts_out.reshape(-1)[0] if hasattr(counts_out, "reshape") else counts_out)
+    return starts_out, keys_out, lags_out, lengths_out, counts_out
+
+
+def decode_occurrence_segments(starts, keys, lags, lengths, counts, index_base: int = 0):
+    """The rows of occurrence_segments_device on the host: per recording the (start int64[m], index int64[m], score float32[m],
+    lag int32[m], length uint32[m]) arrays occurrence_segments returns, m = min(count, capacity), the index global minus
+    index_base; a list with one tuple per recording, or the one tuple for 1-D rows.  Without lags or lengths that array is None."""
+    def host(x, dtype):
+        return np.asarray(x.cpu().numpy() if hasattr(x, "cpu") else x).astype(dtype)
+
+    k = host(keys, np.int64).astype(np.uint64)
+    one = k.ndim == 1
+    k = k.reshape(1, -1) if one else k
+    st = host(starts, np.int64).reshape(k.shape)
+    lg = host(lags, np.int32).reshape(k.shape) if lags is not None else None
+    ln = host(lengths, np.int64).astype(np.uint32).reshape(k.shape) if lengths is not None else None
+    cnt = host(counts, np.int64).reshape(-1)
+    out = []
+    for r in range(k.shape[0]):
+        m = min(int(cnt[r]), k.shape[1])
+        idx = (0xFFFFFFFF - (k[r, :m] & np.uint64(0xFFFFFFFF))).astype(np.int64) - int(index_base)
+        sc = (k[r, :m] >> np.uint64(32)).astype(np.uint32).view(np.float32)
+        out.append((st[r, :m].copy(), idx, sc, lg[r, :m].copy() if lg is not None else None,
+                    ln[r, :m].copy() if ln is not None else None))
     return out[0] if one else out
 
 

@@ -674,6 +674,22 @@ hipError_t launch_timeline_segments(const unsigned long long* d_keys, const uint
                                     uint32_t capacity, uint32_t* d_starts, unsigned long long* d_out_keys, uint32_t* d_out_lengths,
                                     uint32_t* d_counts, hipStream_t stream);
 
+// occurrence segments (k_occurrence_segments.hip): per recording the non-overlapping spans over ALL cells of an occurrences row --
+// d_keys / d_lags / d_lengths [recordings][cap_in] (the lengths of the entries the keys name), the first min(d_counts[r], cap_in)
+// slots of a row (all of them with d_counts null), cap_in <= LBAD_OCCURRENCE_SEGMENTS_MAX_CANDIDATES, per <=
+// LBAD_SEGMENTS_MAX_SUBFINGERPRINTS, the three products with `recordings` below 2^31 -- greedy in descending key order (ties to
+// the lower start, then the lower slot), in start order to the rows of `cap_out` slots of d_starts / d_out_keys / d_out_lags /
+// d_out_lengths (the last two may be null), zeros behind them, the true count to d_out_counts.  The outputs overlap no input.  One
+// launch, no scratch; occurrence_segments_lds_bytes: the dynamic LDS of a workgroup (0 for a shape outside the caps).
+size_t occurrence_segments_lds_bytes(uint32_t cap_in, uint32_t per);
+hipError_t launch_occurrence_segments(const unsigned long long* d_keys, const int32_t* d_lags, const uint32_t* d_lengths,
+                                      const unsigned long long* d_counts, uint32_t recordings, uint32_t cap_in, uint32_t per,
+                                      uint32_t cap_out, uint32_t* d_starts, unsigned long long* d_out_keys, int32_t* d_out_lags,
+                                      uint32_t* d_out_lengths, uint32_t* d_out_counts, hipStream_t stream);
+// launch_timeline_lengths for a uniform corpus, which keeps no offsets: n_sub for every key that names one of its `count` entries
+hipError_t launch_entry_lengths_uniform(const unsigned long long* d_keys, uint32_t n, uint64_t index_base, uint64_t count, uint32_t n_sub,
+                                        uint32_t* d_lengths, hipStream_t stream);
+
 // The host side the three families above share (recording_pass.cpp; DESIGN.md 4.4n states the protocol).
 // The query of a call: a handle (staged through the alignment's pair, under its event) or packed sub-fingerprints on the device
 // (through the builder of k_query.hip, under the packed calls' event), and the range it is compared over (0: the whole length)

@@ -24,7 +24,7 @@
 //               with its bit set goes to slot prefix + popcount(bits below o) of the row when that is below the capacity -- start
 //               order -- with the key as it came and the length as it came (re-read: the LDS copy is clipped); zeros from
 //               min(count, capacity) to the capacity; the true count.  Every word of the row is written exactly once.
-#include "internal.hpp"
+#include "segments_common.hpp"
 
 namespace lbad {
 namespace {
@@ -32,7 +32,6 @@ namespace {
 constexpr uint32_t kSgMaxThreads = 1024;
 constexpr uint32_t kSgMaxGrid = 1u << 16;        // most workgroups of a launch (they stride over the other recordings)
 constexpr uint32_t kSgCap = LBAD_SEGMENTS_MAX_SUBFINGERPRINTS;
-constexpr size_t kSgLdsBudget = 160 * 1024 - 64;
 
 // where a recording's state lies in the dynamic LDS, every block 8-byte aligned
 struct SgLayout {
@@ -54,20 +53,6 @@ __host__ __device__ constexpr SgLayout sg_layout(uint32_t per) {
 }
 static_assert(kSgCap <= 65535, "the order and the clipped lengths are 16 bits wide");
 static_assert(sg_layout(kSgCap).bytes <= kSgLdsBudget, "the state of the longest recording fits a workgroup's LDS");
-
-// the bits of mask word w that [o, e) covers; the caller passes only words the span reaches (o / 64 <= w <= (e - 1) / 64)
-__device__ __forceinline__ unsigned long long sg_span_bits(uint32_t w, uint32_t o, uint32_t e) {
-    const uint32_t lo = w == (o >> 6) ? (o & 63u) : 0u;
-    const uint32_t hi = w == ((e - 1u) >> 6) ? ((e - 1u) & 63u) : 63u;
-    return (~0ull << lo) & (~0ull >> (63u - hi));
-}
-
-__device__ __forceinline__ void sg_wave_sync() {
-    // LDS operations of one wave execute in order; this only stops the compiler from moving them
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ __launch_bounds__(kSgMaxThreads) void timeline_segments_kernel(const unsigned long long* __restrict__ in_keys,
                                                                           const uint32_t* __restrict__ in_lengths, uint32_t recordings,

@@ -297,6 +297,23 @@ OSStatus LBAudioDetectiveFingerprintClips(LBAudioDetectiveRef inDetective, const
 OSStatus LBAudioDetectiveFingerprintClipsFormat(LBAudioDetectiveRef inDetective, const void* inClips,
                                                 UInt32 inSampleFormat, UInt64 inNumberOfClips,
                                                 UInt64 inSamplesPerClip, Boolean* outBooleans);
+/* Frame phases.  A sub-fingerprint is one frame of 128 rows, and a clip's frame grid starts at its first sample; a
+ * recording that starts anywhere else shares no frame with it.  inPhases (P: 1, 2, 4, 8, 16 or 32) grids, h = 128 / P rows
+ * apart: phase p of a signal x[0, L) is the signal x[p * h * stride, L), and its sub-fingerprints are those of
+ * LBAudioDetectiveProcessPCM on that signal, bit for bit.  Their number: 0 when L is shorter than the offset, else
+ * LBAudioDetectiveGetSubfingerprintCount(d, L - p * h * stride) -- count_0 or count_0 - 1.  0 for a P outside the six values
+ * or inPhase >= inPhases. */
+UInt64 LBAudioDetectiveGetSubfingerprintCountAtPhase(LBAudioDetectiveRef inDetective, UInt64 inNumberOfSamples, UInt32 inPhases,
+                                                     UInt32 inPhase);
+/* The batch call at inPhases phases: outPacked = DEVICE, [inNumberOfClips][inPhases][count_0] x LBAD_PACKED_BYTES with
+ * count_0 = LBAudioDetectiveGetSubfingerprintCount(d, inSamplesPerClip); the slots at and behind a phase's count are zero.
+ * The windows of a clip are transformed ONCE (stage 1 as in the batch call, plus at most one frame of rows per clip for the
+ * phases' last frames), stage 2 runs per (phase, frame) with frames at a row hop.  inSampleFormat as above; asynchronous on
+ * inStream; walks the clips in chunks under LBAudioDetectiveSetScratchLimit.  inPhases == 1 writes what
+ * LBAudioDetectiveFingerprintClipsDeviceFormat writes.  kLBAudioDetectiveArgumentInvalid for another P. */
+OSStatus LBAudioDetectiveFingerprintClipsDevicePhases(LBAudioDetectiveRef inDetective, const void* inClips, UInt32 inSampleFormat,
+                                                      UInt64 inNumberOfClips, UInt64 inSamplesPerClip, UInt32 inPhases,
+                                                      void* outPacked, void* inStream);
 /* Kernel selection for the batch path: 0 = automatic, 1 = generic kernels (any window size / band count / stride),
  * 2 = specialised kernels only -- ArgumentInvalid when the configuration has no specialised stage-1 kernel:
  *   - stride 64: pruned 1024-point FFT for bands that read only bins 0..21; streaming 2048- / 4096-point kernels that
@@ -402,6 +419,28 @@ LBAudioDetectiveFingerprintRef LBAudioDetectiveStreamCopyFingerprint(LBAudioDete
 typedef struct LBAudioDetectiveStreamBank* LBAudioDetectiveStreamBankRef;
 LBAudioDetectiveStreamBankRef LBAudioDetectiveStreamBankNew(LBAudioDetectiveRef inDetective, UInt32 inNumberOfChannels,
                                                             UInt32 inHistorySubfingerprints, UInt32 inFramesPerPass);
+/* A PHASED bank: the same at inPhases (1, 2, 4, 8, 16 or 32) frame phases (LBAudioDetectiveGetSubfingerprintCountAtPhase).  Its N
+ * channels present N x inPhases VIRTUAL channels, v = c x inPhases + p: after channel c has received L samples in any chunking,
+ * virtual channel v holds the sub-fingerprints of phase p of those L samples, bit for bit.  Every window of a channel is
+ * transformed once, whatever inPhases: per channel the bank keeps the carried samples and a ring of its last 128 frame rows, a
+ * push transforms the new windows (in groups of four rows, a group as soon as its last window is there) and runs stage 2 at a
+ * row hop on every (channel, phase) frame they complete.  Which call takes which index: PushDevice / Push take N sample counts
+ * and ResetChannels real channels (all phases of each start again); outNewCounts has N x inPhases entries and outNewPacked is
+ * in virtual-channel order, then time order; GetCounts' totals have N x inPhases entries, its pending samples N; WindowDevice
+ * and CopyFingerprint take virtual channel indices -- so every ...Packed...Device query runs on a phased bank's windows as it
+ * is.  inFramesPerPass bounds the frames of one stage-2 launch and (x 128 rows) the windows staged for one stage-1 launch; 0: N x
+ * inPhases.  It does NOT bound a push's memory as it does in the unphased bank: the rows a push transforms are kept for the whole
+ * push (stage 2 reads them at every phase), one block of new windows x pitch steps x 4 bytes that grows to the largest push and
+ * stays -- 88 KB per channel for one second at 44.1 kHz / stride 64 / 32 pitch steps.  NULL as LBAudioDetectiveStreamBankNew,
+ * and for another inPhases, N x inPhases above 2^24 or a stride above the window.  Beside that block the bank holds, per channel,
+ * the unphased bank's samples, 128 x pitch steps x 4 bytes of rows and 32 x history x inPhases bytes. */
+LBAudioDetectiveStreamBankRef LBAudioDetectiveStreamBankNewPhased(LBAudioDetectiveRef inDetective, UInt32 inNumberOfChannels,
+                                                                  UInt32 inHistorySubfingerprints, UInt32 inFramesPerPass,
+                                                                  UInt32 inPhases);
+UInt32 LBAudioDetectiveStreamBankGetPhases(LBAudioDetectiveStreamBankRef inBank);   /* 1 for an unphased bank, 0 for NULL */
+/* host mirror of a phased bank's work since creation: windows transformed by stage 1 and frames selected by stage 2, over all
+ * channels (either pointer may be NULL, not both); kLBAudioDetectiveArgumentInvalid for an unphased bank */
+OSStatus LBAudioDetectiveStreamBankGetWork(LBAudioDetectiveStreamBankRef inBank, UInt64* outWindowsTransformed, UInt64* outFramesSelected);
 void LBAudioDetectiveStreamBankDispose(LBAudioDetectiveStreamBankRef inBank);   /* waits for the bank's launches */
 /* inSamples: DEVICE float32, the channels' new samples one after the other in channel order (4-byte aligned; a channel's run may
  * start at any sample; they are read until the call's launches have run).  inSampleCounts: HOST, one count per channel, 0 =

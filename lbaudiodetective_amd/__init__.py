@@ -15,7 +15,7 @@ from .api import (  # noqa: F401
     debug_recording_batch_plan, debug_set_recording_batch_form, debug_occurrences_batch_plan, debug_set_occurrences_batch_form,
     debug_occurrences_tail_plan, decode_tail_occurrences, debug_recording_tail_plan, decode_tail_matches,
     debug_occurrences_tail_peaks_plan, debug_timeline_tail_plan, LiveTimeline,
-    occurrence_segments, occurrence_segments_device, decode_occurrence_segments,
+    occurrence_segments, occurrence_segments_device, decode_occurrence_segments, phase_sample_offset,
 )
 from .sharded import (  # noqa: F401
     ShardedCorpus, broadcast_fingerprint, gather_packed, gather_topk_aligned, make_comm, merge_topk_aligned, merge_topk_keys, shard_range,
@@ -34,5 +34,5 @@ __all__ = [
     "timeline_segments_device", "decode_segments", "debug_recording_batch_plan", "debug_set_recording_batch_form",
     "debug_occurrences_batch_plan", "debug_set_occurrences_batch_form", "debug_occurrences_tail_plan", "decode_tail_occurrences",
     "debug_recording_tail_plan", "decode_tail_matches", "debug_occurrences_tail_peaks_plan", "debug_timeline_tail_plan", "LiveTimeline",
-    "occurrence_segments", "occurrence_segments_device", "decode_occurrence_segments",
+    "occurrence_segments", "occurrence_segments_device", "decode_occurrence_segments", "phase_sample_offset",
 ]

@@ -117,6 +117,8 @@ _SIGNATURES = {
     "LBAudioDetectiveComparePCM": (OSStatus, [Ref, C.c_void_p, UInt64, C.c_void_p, UInt64, UInt32, _P(Float32)]),
     "LBAudioDetectiveFingerprintClipsDevice": (OSStatus, [Ref, C.c_void_p, UInt64, UInt64, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveFingerprintClipsDeviceFormat": (OSStatus, [Ref, C.c_void_p, UInt32, UInt64, UInt64, C.c_void_p, C.c_void_p]),
+    "LBAudioDetectiveGetSubfingerprintCountAtPhase": (UInt64, [Ref, UInt64, UInt32, UInt32]),
+    "LBAudioDetectiveFingerprintClipsDevicePhases": (OSStatus, [Ref, C.c_void_p, UInt32, UInt64, UInt64, UInt32, C.c_void_p, C.c_void_p]),
     "LBAudioDetectiveSetFilePipeline": (OSStatus, [Ref, UInt32]),
     "LBAudioDetectiveGetCompactLayout": (OSStatus, [Ref, _P(UInt32), _P(UInt32)]),
     "LBAudioDetectiveGetCompactBands": (OSStatus, [Ref, _P(UInt32), _P(UInt32)]),
@@ -127,6 +129,9 @@ _SIGNATURES = {
     "LBAudioDetectiveStreamPush": (OSStatus, [Ref, C.c_void_p, UInt64, _P(UInt32)]),
     "LBAudioDetectiveStreamCopyFingerprint": (Ref, [Ref]),
     "LBAudioDetectiveStreamBankNew": (Ref, [Ref, UInt32, UInt32, UInt32]),
+    "LBAudioDetectiveStreamBankNewPhased": (Ref, [Ref, UInt32, UInt32, UInt32, UInt32]),
+    "LBAudioDetectiveStreamBankGetPhases": (UInt32, [Ref]),
+    "LBAudioDetectiveStreamBankGetWork": (OSStatus, [Ref, _P(UInt64), _P(UInt64)]),
     "LBAudioDetectiveStreamBankDispose": (None, [Ref]),
     "LBAudioDetectiveStreamBankPushDevice": (OSStatus, [Ref, C.c_void_p, _P(UInt32), _P(UInt32), C.c_void_p, UInt64, _P(UInt64), C.c_void_p]),
     "LBAudioDetectiveStreamBankPush": (OSStatus, [Ref, C.c_void_p, _P(UInt32), _P(UInt32), C.c_void_p, UInt64, _P(UInt64), C.c_void_p]),

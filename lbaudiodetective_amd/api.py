@@ -421,6 +421,28 @@ class Detective:
                "FingerprintClipsDeviceTapsFormat")
         return out, raw, haar
 
+    def subfingerprint_count_at_phase(self, n_samples: int, phases: int, phase: int) -> int:
+        """Sub-fingerprints of phase `phase` of `phases` (1, 2, 4, ... 32) of a signal of n_samples: the count of the signal without
+        its first phase_sample_offset(phases, phase, stride) samples; 0 for a phase count or phase that does not exist."""
+        return int(self._L.LBAudioDetectiveGetSubfingerprintCountAtPhase(self._ref, n_samples, phases, phase))
+
+    def fingerprint_clips_device_phases(self, clips, phases: int, out=None, stream=None):
+        """The device batch at `phases` frame phases: clips [n, samples] (cuda; float32, int16 or int32) -> uint32
+        [n, phases, count_0, 8], row (c, p) the packed sub-fingerprints of clip c without its first
+        phase_sample_offset(phases, p, stride) samples, zero at and behind subfingerprint_count_at_phase(samples, phases, p).
+        The windows of a clip are transformed once whatever `phases`.  Asynchronous on the given (default: current) stream."""
+        import torch
+        assert clips.is_cuda and clips.is_contiguous() and clips.dtype in (torch.float32, torch.int16, torch.int32)
+        n, spc = clips.shape
+        per = self.subfingerprint_count(spc)
+        if out is None:
+            out = torch.empty((n, int(phases), per, N.PACKED_WORDS), dtype=torch.int32, device=clips.device).view(torch.uint32)
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= n * int(phases) * per * N.PACKED_BYTES
+        fmt = {torch.float32: 0, torch.int16: 1, torch.int32: 2}[clips.dtype]
+        _check(self._L.LBAudioDetectiveFingerprintClipsDevicePhases(self._ref, clips.data_ptr(), fmt, n, spc, int(phases), out.data_ptr(),
+                                                                   _stream_ptr(stream)), "FingerprintClipsDevicePhases")
+        return out
+
     def stage1_choice(self, fmt: int, n_clips: int, samples_per_clip: int, address: int = 0, taps: bool = False,
                       tail: bool = False, variant: int = 0, waves: int = 0, cache: bool = True) -> "Stage1Choice":
         """debug_stage1_choice for this detective's settings; variant and tuning are not readable from the handle and are
@@ -428,6 +450,15 @@ class Detective:
         return debug_stage1_choice(self.processing_sample_rate, self.window_size, self.analysis_stride, self.number_of_pitch_steps,
                                    self.subfingerprint_length, variant, waves, cache, fmt, n_clips, samples_per_clip, address % 8,
                                    taps, tail)
+
+
+def phase_sample_offset(phases: int, phase: int, stride: int) -> int:
+    """First sample of frame phase `phase` of `phases`: phase * (128 / phases) * stride.  Sub-fingerprint j of that phase starts
+    phase_sample_offset(...) + j * 128 * stride samples into the signal."""
+    phases, phase = int(phases), int(phase)
+    if phases not in (1, 2, 4, 8, 16, 32) or not 0 <= phase < phases:
+        raise ValueError(f"no phase {phase} of {phases}")
+    return phase * (N.ROWS_PER_FRAME // phases) * int(stride)
 
 
 STAGE1_FAMILIES = ("generic", "pruned", "stream2", "full", "stream")
@@ -545,15 +576,48 @@ class StreamBank:
     """LBAudioDetectiveStreamBankRef: `n_channels` live channels whose carried partial frames and `history` most recent
     sub-fingerprints stay on the device.  A push takes new samples of any of the channels and fingerprints every frame they
     complete in one launch chain; `window_device` hands the most recent sub-fingerprints of some channels to the packed queries.
-    frames_per_pass bounds the staging memory (0: one frame per channel); results do not depend on it."""
+    frames_per_pass bounds the staging memory (0: one frame per channel); results do not depend on it.
 
-    def __init__(self, detective: Detective, n_channels: int, history: int, frames_per_pass: int = 0):
+    phases given (1, 2, 4, ... 32; 1 included) makes a PHASED bank (LBAudioDetectiveStreamBankNewPhased): n_channels * phases
+    virtual channels, virtual(c, p) holding the sub-fingerprints of channel c's samples without the first
+    phase_sample_offset(phases, p, stride) -- every frame grid `128 / phases` rows apart, from ONE transform of the channel's
+    windows.  Pushes and reset take the real channels; new counts, totals, window_device, fingerprint and every query built on
+    window_device take virtual channel indices.  Without `phases` the bank is the unphased one (LBAudioDetectiveStreamBankNew),
+    as it always was: `phases` and `virtual_channels` then read 1 and n_channels, `phased` False."""
+
+    def __init__(self, detective: Detective, n_channels: int, history: int, frames_per_pass: int = 0, phases: int = None):
         self._L = N.lib()
         self._det = detective            # keep the detective alive
         self.n_channels, self.history = int(n_channels), int(history)
-        self._ref = self._L.LBAudioDetectiveStreamBankNew(detective._ref, n_channels, history, frames_per_pass)
+        self.phased = phases is not None
+        self.phases = int(phases) if self.phased else 1
+        self.virtual_channels = self.n_channels * self.phases
+        if self.phased:
+            self._ref = self._L.LBAudioDetectiveStreamBankNewPhased(detective._ref, n_channels, history, frames_per_pass, self.phases)
+        else:
+            self._ref = self._L.LBAudioDetectiveStreamBankNew(detective._ref, n_channels, history, frames_per_pass)
         if not self._ref:
-            raise LBAudioDetectiveError(1, "StreamBankNew")
+            raise LBAudioDetectiveError(1, "StreamBankNewPhased" if self.phased else "StreamBankNew")
+
+    def virtual(self, channel: int, phase: int = 0) -> int:
+        """The virtual channel of (channel, phase): channel * phases + phase."""
+        if not 0 <= channel < self.n_channels or not 0 <= phase < self.phases:
+            raise IndexError(f"(channel {channel}, phase {phase}) of a bank of {self.n_channels} x {self.phases}")
+        return channel * self.phases + phase
+
+    def work(self):
+        """LBAudioDetectiveStreamBankGetWork (a phased bank): (windows transformed, frames selected) since creation."""
+        w, f = N.UInt64(0), N.UInt64(0)
+        _check(self._L.LBAudioDetectiveStreamBankGetWork(self._ref, C.byref(w), C.byref(f)), "StreamBankGetWork")
+        return int(w.value), int(f.value)
+
+    def _new_room(self, n) -> int:
+        """room for the sub-fingerprints a push of n samples per channel completes: their number for an unphased bank (the host
+        can tell alone); for a phased bank a bound, n / (128 stride) + 1 per virtual channel -- _push hands back the filled part"""
+        if not self.phased:
+            return int(debug_stream_bank_plan(self._det.window_size, self._det.analysis_stride, self.history, self.pending(), n)[0].sum())
+        hop = N.ROWS_PER_FRAME * self._det.analysis_stride
+        return sum(self.phases * (int(x) // hop + 1) for x in n if x)
 
     def dispose(self):
         if self._ref:
@@ -572,14 +636,13 @@ class StreamBank:
             raise ValueError("counts must have one value per channel")
         if new_out is True:              # sized from the plan, which the host can make alone
             import torch
-            ready = debug_stream_bank_plan(self._det.window_size, self._det.analysis_stride, self.history, self.pending(), n)[0]
-            new_out = torch.empty((int(ready.sum()), N.PACKED_BYTES), dtype=torch.uint8, device=device)
+            new_out = torch.empty((self._new_room(n), N.PACKED_BYTES), dtype=torch.uint8, device=device)
         capacity = 0
         if new_out is not None:
             if not new_out.is_cuda or not new_out.is_contiguous():
                 raise ValueError("new_out must be a contiguous device tensor")
             capacity = new_out.numel() * new_out.element_size() // N.PACKED_BYTES
-        new_counts = np.zeros(self.n_channels, np.uint32)
+        new_counts = np.zeros(self.virtual_channels, np.uint32)
         total = N.UInt64(0)
         _check(fn(self._ref, samples_ptr, npt, new_counts.ctypes.data_as(C.POINTER(N.UInt32)),
                   _dev_ptr(new_out) if new_out is not None and new_out.numel() else None, capacity, C.byref(total), _stream_ptr(stream)), what)
@@ -590,9 +653,10 @@ class StreamBank:
 
     def push_device(self, samples, counts, new_out=None, stream=None):
         """LBAudioDetectiveStreamBankPushDevice: `samples`, a float32 device tensor holding the channels' new samples one after
-        the other in channel order; `counts`, one host integer per channel.  new_out: None, True (a tensor of exactly the new
-        sub-fingerprints is made) or a contiguous device tensor with room for them -> (new_counts uint32 [n_channels] on the host,
-        the new sub-fingerprints uint8 [total, 32] on the device in channel order then time order, or None).  Asynchronous on
+        the other in channel order; `counts`, one host integer per channel.  new_out: None, True (a tensor for the new
+        sub-fingerprints is made) or a contiguous device tensor with room for them -> (new_counts uint32 [virtual_channels] on the
+        host -- [n_channels] for an unphased bank --, the new sub-fingerprints uint8 [total, 32] on the device in (virtual) channel
+        order then time order, or None).  Asynchronous on
         `stream`; `samples` must stay untouched until the stream has run the call."""
         import torch
         assert samples.is_cuda and samples.is_contiguous() and samples.dtype == torch.float32
@@ -613,7 +677,7 @@ class StreamBank:
 
     def totals(self) -> np.ndarray:
         """sub-fingerprints of every channel since creation / its last reset (uint64, the host mirror)"""
-        out = np.zeros(self.n_channels, np.uint64)
+        out = np.zeros(self.virtual_channels, np.uint64)
         _check(self._L.LBAudioDetectiveStreamBankGetCounts(self._ref, out.ctypes.data_as(C.POINTER(N.UInt64)), None), "StreamBankGetCounts")
         return out
 
@@ -639,8 +703,8 @@ class StreamBank:
 
     def fingerprint(self, channel: int) -> Fingerprint:
         """LBAudioDetectiveStreamBankCopyFingerprint: the min(total, history) most recent sub-fingerprints of one channel."""
-        if not 0 <= channel < self.n_channels:
-            raise IndexError(f"channel {channel} of a bank of {self.n_channels}")
+        if not 0 <= channel < self.virtual_channels:
+            raise IndexError(f"channel {channel} of a bank of {self.virtual_channels}")
         ref = self._L.LBAudioDetectiveStreamBankCopyFingerprint(self._ref, channel)
         if not ref:
             raise LBAudioDetectiveError(1, "StreamBankCopyFingerprint")

@@ -244,6 +244,21 @@ void stage1_choice_words(const Stage1Choice& ch, const Stage1Call& c, const Plan
     w[11] = (uint32_t)ch.per;
 }
 
+// The stage-1 launch of a choice: the ONE switch over the families (the batch call and the phases call both launch through it)
+static hipError_t launch_stage1(const LBAudioDetective* d, const Plan& p, const Stage1Choice& ch, const void* pcm_in, uint32_t fmt,
+                                uint64_t nc, uint64_t spc, uint32_t frames_per_clip, float* frames_out, hipStream_t stream) {
+    switch (ch.family) {
+        case Stage1Family::Pruned:
+            return launch_rows_pruned(p, p.d_bin_const, pcm_in, fmt, nc, spc, frames_per_clip, frames_out, stream, ch.compact,
+                                      d->band_form);
+        case Stage1Family::Stream2: return launch_rows_stream2(p, pcm_in, fmt, nc, spc, frames_per_clip, frames_out, stream);
+        case Stage1Family::Full: return launch_rows_full(p, pcm_in, fmt, nc, spc, frames_per_clip, frames_out, stream);
+        case Stage1Family::Stream: return launch_rows_stream(p, pcm_in, fmt, nc, spc, frames_per_clip, frames_out, stream);
+        case Stage1Family::Generic: break;
+    }
+    return launch_fft_bands(p, pcm_in, fmt, nc, spc, frames_per_clip, frames_out, stream);
+}
+
 // The batch hot path: every clip -> frames_per_clip packed sub-fingerprints.
 OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, uint32_t fmt, uint64_t n_clips,
                                   uint64_t spc, uint32_t* d_packed, float* d_raw, float* d_haar, hipStream_t stream,
@@ -268,16 +283,7 @@ OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, ui
     LBAD_HIP(order.begin());
     const bool compact = ch.compact;
     auto stage1 = [&](const void* pcm_in, uint64_t nc, float* frames_out) -> hipError_t {
-        switch (ch.family) {
-            case Stage1Family::Pruned:
-                return launch_rows_pruned(p, p.d_bin_const, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream, compact,
-                                          d->band_form);
-            case Stage1Family::Stream2: return launch_rows_stream2(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
-            case Stage1Family::Full: return launch_rows_full(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
-            case Stage1Family::Stream: return launch_rows_stream(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
-            case Stage1Family::Generic: break;
-        }
-        return launch_fft_bands(p, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
+        return launch_stage1(d, p, ch, pcm_in, fmt, nc, spc, (uint32_t)per, frames_out, stream);
     };
     auto stage2 = [&](float* frames_in, uint64_t nf, uint32_t* packed_out, float* haar_out) -> hipError_t {
         if (compact && haar_out) {      // the sparse form writes the columns that can be non-zero; the others are +0.0
@@ -320,6 +326,75 @@ OSStatus fingerprint_clips_device(LBAudioDetective* d, const void* d_pcm_raw, ui
         LBAD_HIP(stage2(d->d_frames, nc * per, d_packed + c0 * per * kPackedWords,
                         d_haar ? d_haar + c0 * per * frame_floats : nullptr));
         LBAD_HIP(mark());
+    }
+    return noErr;
+}
+
+// ---- frame phases ------------------------------------------------------------------
+bool valid_phases(uint32_t phases) { return phases >= 1 && phases <= 32 && (phases & (phases - 1)) == 0; }
+
+uint64_t subfingerprint_count_at_phase(uint64_t n_samples, uint32_t window, uint32_t stride, uint32_t phases, uint32_t phase) {
+    if (!valid_phases(phases) || phase >= phases) return 0;
+    const uint64_t off = (uint64_t)phase * (kRowsPerFrame / phases) * stride;
+    return n_samples < off ? 0 : subfingerprint_count(n_samples - off, window, stride);
+}
+
+// The batch path at P phases: stage 1 as fingerprint_clips_device runs it (the clip's count_0 frames are the first
+// 128 count_0 rows of its row run), ONE more frame of stage 1 per clip whose last row is the last row any phase reads (only
+// where a phase p > 0 has count_0 frames), then stage 2 at a row hop over [clip][phase][count_0] slots.  The decision is
+// stage1_choose's and the stage-1 launches are launch_stage1's, as in the batch call; the chunking makes room for the tail
+// frame.  No timing marks: LBAudioDetectiveSetStageTiming / GetStageTimes cover the batch call only.
+OSStatus fingerprint_clips_device_phases(LBAudioDetective* d, const void* d_pcm_raw, uint32_t fmt, uint64_t n_clips, uint64_t spc,
+                                         uint32_t phases, uint32_t* d_packed, hipStream_t stream) {
+    if (fmt > 2 || !valid_phases(phases)) return kLBAudioDetectiveArgumentInvalid;
+    LBAD_LOCK(d);
+    const size_t elem = fmt == 1 ? 2 : 4;
+    const char* d_pcm = static_cast<const char*>(d_pcm_raw);
+    OSStatus st = ensure_plan(d);
+    if (st != noErr) return st;
+    const Plan& p = d->plan;
+    Stage1Call call;
+    call.variant = d->variant; call.fmt = fmt; call.n_clips = n_clips; call.spc = spc;
+    call.ptr_mod8 = (uint32_t)(reinterpret_cast<uintptr_t>(d_pcm_raw) % 8);
+    const Stage1Choice ch = stage1_choose(p, call);
+    if (ch.status != noErr || !ch.launches) return ch.status;
+    if (d->band_form == 2 && !p.lanes_ok) return kLBAudioDetectiveArgumentInvalid;
+    const uint64_t per = ch.per;
+    StageHop hop;
+    hop.phases = phases;
+    hop.hop = kRowsPerFrame / phases;
+    hop.count0 = (uint32_t)per;
+    hop.full_phases = 1;              // (the count falls with the phase: the phases with count_0 frames come first)
+    while (hop.full_phases < phases && subfingerprint_count_at_phase(spc, p.window, p.stride, phases, hop.full_phases) == per) ++hop.full_phases;
+    const bool has_tail = hop.full_phases > 1;
+    // the tail frame: the 128 rows that end with the last row of phase full_phases - 1.  Its first row is a multiple of
+    // hop >= 4 rows, so the clips stay as aligned for stage 1 as they are (8 bytes or more at every sample format)
+    hop.tail_row0 = (hop.full_phases - 1) * hop.hop + kRowsPerFrame * ((uint32_t)per - 1);
+    if (per * phases > 0x7fffffffull) return kLBAudioDetectiveArgumentInvalid;
+    StreamOrder order{d, stream};
+    LBAD_HIP(order.begin());
+    const bool compact = ch.compact;
+    auto stage1 = [&](const void* pcm_in, uint64_t nc, uint32_t frames_per_clip, float* frames_out) -> hipError_t {
+        return launch_stage1(d, p, ch, pcm_in, fmt, nc, spc, frames_per_clip, frames_out, stream);
+    };
+    const uint64_t frame_floats = (uint64_t)kRowsPerFrame * p.bands;
+    const uint64_t clip_frames = per + (has_tail ? 1 : 0);
+    uint64_t chunk = (d->scratch_limit / sizeof(float)) / (clip_frames * frame_floats);
+    if (chunk == 0) chunk = 1;
+    if (chunk > 0x7fffffffull / (per * phases)) chunk = 0x7fffffffull / (per * phases);
+    if (chunk > n_clips) chunk = n_clips;
+    st = d->d_frames.reserve(chunk * clip_frames * frame_floats);
+    if (st != noErr) return st;
+    float* const d_tail = d->d_frames + chunk * per * frame_floats;
+    hop.tail = has_tail ? d_tail : nullptr;
+    for (uint64_t c0 = 0; c0 < n_clips; c0 += chunk) {
+        const uint64_t nc = (n_clips - c0) < chunk ? (n_clips - c0) : chunk;
+        const char* pcm = d_pcm + c0 * spc * elem;
+        LBAD_HIP(stage1(pcm, nc, (uint32_t)per, d->d_frames));
+        if (has_tail) LBAD_HIP(stage1(pcm + (uint64_t)hop.tail_row0 * p.stride * elem, nc, 1, d_tail));
+        uint32_t* out = d_packed + c0 * phases * per * kPackedWords;
+        LBAD_HIP(ch.stage2_select32 ? launch_haar_select32_hop(p, d->d_frames, hop, nc, out, stream, compact)
+                                    : launch_haar_select_hop(p, d->d_frames, hop, nc, out, stream));
     }
     return noErr;
 }
@@ -627,6 +702,22 @@ OSStatus LBAudioDetectiveGetStageTimes(LBAudioDetectiveRef d, Float32* outStage1
 
 UInt64 LBAudioDetectiveGetSubfingerprintCount(LBAudioDetectiveRef d, UInt64 inNumberOfSamples) {
     return lbad::subfingerprint_count(inNumberOfSamples, d->window, d->stride);
+}
+
+UInt64 LBAudioDetectiveGetSubfingerprintCountAtPhase(LBAudioDetectiveRef d, UInt64 inNumberOfSamples, UInt32 inPhases, UInt32 inPhase) {
+    if (!d) return 0;
+    return lbad::subfingerprint_count_at_phase(inNumberOfSamples, d->window, d->stride, inPhases, inPhase);
+}
+
+OSStatus LBAudioDetectiveFingerprintClipsDevicePhases(LBAudioDetectiveRef d, const void* inClips, UInt32 inSampleFormat,
+                                                      UInt64 inNumberOfClips, UInt64 inSamplesPerClip, UInt32 inPhases, void* outPacked,
+                                                      void* inStream) {
+    if (!d || !lbad::valid_phases(inPhases) || (!inClips && inNumberOfClips)) return kLBAudioDetectiveArgumentInvalid;
+    // (clips shorter than a frame have no output: none is asked for)
+    if (!outPacked && inNumberOfClips && lbad::subfingerprint_count(inSamplesPerClip, d->window, d->stride) != 0)
+        return kLBAudioDetectiveArgumentInvalid;
+    return lbad::fingerprint_clips_device_phases(d, inClips, inSampleFormat, inNumberOfClips, inSamplesPerClip, inPhases,
+                                                 static_cast<uint32_t*>(outPacked), static_cast<hipStream_t>(inStream));
 }
 
 OSStatus LBAudioDetectiveFingerprintClipsDeviceTapsFormat(LBAudioDetectiveRef d, const void* inClips, UInt32 inSampleFormat,

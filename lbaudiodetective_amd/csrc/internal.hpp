@@ -159,6 +159,8 @@ struct FileTail {
 // fmt: 0 float32, 1 int16, 2 int32 samples
 hipError_t launch_fft_bands(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips,
                             uint64_t samples_per_clip, uint32_t frames_per_clip, float* d_frames, hipStream_t stream);
+hipError_t launch_fft_bands_windows(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips, uint64_t samples_per_clip,
+                                    uint32_t windows_per_clip, float* d_frames, hipStream_t stream);
 // frame rows -> packed sub-fingerprints.  d_haar (optional) receives the decomposed frames.
 hipError_t launch_haar_select(const Plan& plan, float* d_frames, uint64_t n_frames, uint32_t* d_packed,
                               float* d_haar_out, hipStream_t stream);
@@ -199,6 +201,77 @@ bool haar_select32_supported(const Plan& plan);
 hipError_t launch_haar_select32(const Plan& plan, const float* d_frames, uint64_t n_frames, uint32_t* d_packed,
                                 float* d_haar_out, hipStream_t stream, bool compact = false);
 void plan_sparse(Plan& plan);    // fills plan.sparse from plan.table
+
+// ---- stage 2 at a row hop (frame phases) ------------------------------------------------------------
+// The hop forms of stage 2 read a frame's 128 rows from TWO row runs: rows [0, split) at run A's rows
+// a_row0 + ((a_first + r) & mask), rows [split, 128) at run B's rows b_row0 + (r - split).  Two ways to say which:
+//
+// batch (list == null): P phases of a clip; frame j of phase p is the 128 rows from row p * hop + 128 j of the clip's row run.
+//   The run's first 128 * count0 rows are what stage 1 wrote for the clip (A = d_frames, clip * 128 * count0 rows in); the rows
+//   behind them, which only a phase's last frame reads, are in B = `tail`: per clip ONE frame of rows, the run's rows
+//   tail_row0 .. tail_row0 + 127 (tail_row0 <= 128 * count0: a straddling frame reads from both).  Phases 0 .. full_phases - 1
+//   have count0 frames, the others count0 - 1; the output is [clip][phase][count0] slots, zero at and behind a phase's count.
+// list (the phased stream bank): workgroup g takes list[g]; A = d_frames is the channels' row rings (128 rows each, row number
+//   t of a channel at t mod 128: mask 127), B = `tail` the rows the push has just transformed; output slot g.
+struct HopFrame {
+    uint64_t a_row0, b_row0;
+    uint32_t a_first, split;            // split <= 128
+    uint32_t pad[2];
+};
+static_assert(sizeof(HopFrame) == 32, "HopFrame is uploaded as it is");
+struct StageHop {
+    const float* tail = nullptr;
+    uint32_t phases = 1, hop = kRowsPerFrame;
+    uint32_t count0 = 0, full_phases = 1;
+    uint32_t tail_row0 = 0;
+    const HopFrame* list = nullptr;
+    uint32_t n_list = 0;
+};
+inline bool stage_hop_valid(const StageHop& h) {
+    if (h.list) return h.n_list <= 0x7fffffffu;
+    const uint64_t last = (uint64_t)(h.full_phases - 1) * h.hop + (uint64_t)kRowsPerFrame * h.count0;   // behind the last row any frame reads
+    return h.phases >= 1 && h.phases <= 32 && (h.phases & (h.phases - 1)) == 0 && h.hop * h.phases == kRowsPerFrame && h.count0 >= 1 &&
+           h.count0 <= 0xFFFFFFFFu / kRowsPerFrame - 1 && h.full_phases >= 1 && h.full_phases <= h.phases &&
+           (h.tail ? (uint64_t)h.tail_row0 <= (uint64_t)kRowsPerFrame * h.count0 && last <= (uint64_t)h.tail_row0 + kRowsPerFrame
+                   : h.full_phases == 1);
+}
+inline uint64_t stage_hop_frames(const StageHop& h, uint64_t n_clips) { return h.list ? h.n_list : n_clips * h.phases * h.count0; }
+#if defined(__HIPCC__)
+struct HopSource {
+    uint64_t a_row0, b_row0;
+    uint32_t a_first, split, mask;
+    bool empty;                         // a slot at or behind its phase's count: zeros
+};
+// what workgroup `slot` reads (workgroup-uniform)
+__device__ __forceinline__ HopSource hop_source(const StageHop& h, uint32_t slot) {
+    HopSource s;
+    if (h.list) {
+        const HopFrame f = h.list[slot];
+        s.a_row0 = f.a_row0; s.b_row0 = f.b_row0; s.a_first = f.a_first; s.split = f.split;
+        s.mask = kRowsPerFrame - 1;
+        s.empty = false;
+        return s;
+    }
+    const uint32_t j = slot % h.count0, cp = slot / h.count0;
+    const uint32_t phase = cp % h.phases, clip = cp / h.phases;
+    const uint32_t first = phase * h.hop + kRowsPerFrame * j, main_rows = kRowsPerFrame * h.count0;
+    s.empty = j >= h.count0 - (phase < h.full_phases ? 0u : 1u);
+    s.a_row0 = (uint64_t)clip * main_rows;
+    s.a_first = first;
+    s.mask = 0xFFFFFFFFu;
+    s.split = first < main_rows ? main_rows - first : 0u;      // (>= 128: the whole frame is in A)
+    s.b_row0 = (uint64_t)clip * kRowsPerFrame + (main_rows - h.tail_row0);
+    return s;
+}
+// row `row` of the frame; rows of row_dw floats
+__device__ __forceinline__ const float* hop_row(const float* run_a, const float* run_b, const HopSource& s, uint32_t row, uint32_t row_dw) {
+    return row < s.split ? run_a + (s.a_row0 + ((s.a_first + row) & s.mask)) * row_dw : run_b + (s.b_row0 + (row - s.split)) * row_dw;
+}
+#endif
+hipError_t launch_haar_select32_hop(const Plan& plan, const float* d_frames, const StageHop& hop, uint64_t n_clips, uint32_t* d_packed,
+                                    hipStream_t stream, bool compact = false);
+hipError_t launch_haar_select_hop(const Plan& plan, const float* d_frames, const StageHop& hop, uint64_t n_clips, uint32_t* d_packed,
+                                  hipStream_t stream);
 
 // ---- stage 1: ONE decision per call (api_detective.cpp: stage1_choose), and per kernel file ONE function that names the
 // template instance -- each launcher dispatches on what its function returns and LBAudioDetectiveDebugStage1Choice reports the
@@ -1041,6 +1114,22 @@ hipError_t launch_bank_stage(const BankDev& b, const BankRow* d_rows, uint32_t n
 // the caller's block, then what every row's channel carries on -- into the other side where it completed a frame.  Two launches.
 hipError_t launch_bank_commit(const BankDev& b, const BankRow* d_rows, uint32_t n_rows, const float* d_fresh, const uint32_t* d_packed,
                               uint32_t total, void* d_out, hipStream_t stream);
+// the two halves of launch_bank_commit alone (the phased bank: its sample rows and its sub-fingerprint rows are two tables)
+hipError_t launch_bank_commit_rows(const BankDev& b, const BankRow* d_rows, uint32_t n_rows, const uint32_t* d_packed, uint32_t total,
+                                   void* d_out, hipStream_t stream);
+hipError_t launch_bank_commit_carry(const BankDev& b, const BankRow* d_rows, uint32_t n_rows, const float* d_fresh, hipStream_t stream);
+// the phased bank's row rings (k_stream_bank_phased.hip): per real channel the last 128 rows of `row_dw` floats, row number t of
+// a channel at t mod 128.  One PhasedRow per channel that transformed windows in the push: its last min(n_new, 128) new rows
+// (d_new_rows + (new_row0 + i) * row_dw) go to their ring slots.
+struct PhasedRow {
+    uint64_t new_row0;                  // the channel's first new row among the push's new rows
+    uint32_t n_new, ring_at;            // new rows; ring slot of the first of them: the channel's row count mod 128
+    uint32_t channel;
+    uint32_t pad[3];
+};
+static_assert(sizeof(PhasedRow) == 32, "PhasedRow is uploaded as it is");
+hipError_t launch_bank_row_ring(float* d_row_ring, uint32_t row_dw, const PhasedRow* d_rows, uint32_t n_rows, const float* d_new_rows,
+                                hipStream_t stream);
 // d_list[j] = (channel, ring slot of the oldest of its q rows) -> d_out[j][q][32 bytes] (16-byte aligned); n_list * q <= 2^31
 hipError_t launch_bank_window(const BankDev& b, const uint2* d_list, uint64_t n_list, uint32_t q, void* d_out, hipStream_t stream);
 
@@ -1103,6 +1192,9 @@ hipError_t launch_synth_corpus(uint32_t seed, uint64_t first, uint64_t n_entries
 
 // ---- shared between the api_*.cpp files ------------------------------------------------------------------
 uint64_t subfingerprint_count(uint64_t n_samples, uint32_t window, uint32_t stride);
+// frame phases (api_detective.cpp): P is a power of two up to 32; the count of phase p is that of the signal without its first p * (128 / P) * stride samples
+bool valid_phases(uint32_t phases);
+uint64_t subfingerprint_count_at_phase(uint64_t n_samples, uint32_t window, uint32_t stride, uint32_t phases, uint32_t phase);
 OSStatus ensure_plan(struct ::LBAudioDetective* d);
 // the batch hot path on device memory; tails: end-of-file treatment of files laid out inside ONE float32 clip
 OSStatus fingerprint_clips_device(struct ::LBAudioDetective* d, const void* d_pcm, uint32_t fmt, uint64_t n_clips,

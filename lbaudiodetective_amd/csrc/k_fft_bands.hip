@@ -384,12 +384,11 @@ __global__ __launch_bounds__(WPB * 64) void fft_bands_kernel(
 
 template <int LOG2W, int WPB, bool CACHED>
 hipError_t launch_variant(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips, uint64_t samples_per_clip,
-                          uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {
+                          uint32_t windows_per_clip, float* d_frames, hipStream_t stream) {
     constexpr size_t cache_bytes = CACHED ? (size_t)Passes<LOG2W>::cache_slots * sizeof(float2) : 0;
     const uint32_t nread = bins_padded(plan.table.kmin, plan.table.kmax);
     const size_t lds = cache_bytes + ((size_t)2 * nread + (size_t)WPB * (point_floats<LOG2W>() + nread)) * sizeof(float);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const uint32_t windows_per_clip = frames_per_clip * kRowsPerFrame;
     const uint64_t n_windows = n_clips * windows_per_clip;
     if (n_windows == 0) return hipSuccess;
     auto kern = fft_bands_kernel<LOG2W, WPB, CACHED>;
@@ -461,12 +460,12 @@ FftBandsInstance choose_one(const Plan& plan) {
 
 template <int LOG2W>
 hipError_t launch_one(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips, uint64_t samples_per_clip,
-                      uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {
+                      uint32_t windows_per_clip, float* d_frames, hipStream_t stream) {
     const FftBandsInstance c = choose_one<LOG2W>(plan);
 #define LBAD_GO(w)                                                                                               \
     if (c.wpb == w) {                                                                                            \
-        if (c.cached) return launch_variant<LOG2W, w, true>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream); \
-        return launch_variant<LOG2W, w, false>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream); \
+        if (c.cached) return launch_variant<LOG2W, w, true>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream); \
+        return launch_variant<LOG2W, w, false>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream); \
     }
     if constexpr (LOG2W == 11) {
         LBAD_GO(12) LBAD_GO(8) LBAD_GO(4) LBAD_GO(2) LBAD_GO(1)
@@ -499,21 +498,35 @@ FftBandsInstance fft_bands_instance(const Plan& plan) {
     }
 }
 
-hipError_t launch_fft_bands(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips,
-                            uint64_t samples_per_clip, uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {
+// the instance for the plan's window size, clips of windows_per_clip windows: rows [n_clips * windows_per_clip][bands]
+static hipError_t launch_windows(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips, uint64_t samples_per_clip,
+                                 uint32_t windows_per_clip, float* d_frames, hipStream_t stream) {
     switch (plan.log2w) {
-        case 4: return launch_one<4>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-        case 5: return launch_one<5>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-        case 6: return launch_one<6>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-        case 7: return launch_one<7>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-        case 8: return launch_one<8>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-        case 9: return launch_one<9>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-        case 10: return launch_one<10>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-        case 11: return launch_one<11>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-        case 12: return launch_one<12>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
-        case 13: return launch_one<13>(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip, d_frames, stream);
+        case 4: return launch_one<4>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
+        case 5: return launch_one<5>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
+        case 6: return launch_one<6>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
+        case 7: return launch_one<7>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
+        case 8: return launch_one<8>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
+        case 9: return launch_one<9>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
+        case 10: return launch_one<10>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
+        case 11: return launch_one<11>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
+        case 12: return launch_one<12>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
+        case 13: return launch_one<13>(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
         default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_fft_bands(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips,
+                            uint64_t samples_per_clip, uint32_t frames_per_clip, float* d_frames, hipStream_t stream) {
+    return launch_windows(plan, d_pcm, fmt, n_clips, samples_per_clip, frames_per_clip * kRowsPerFrame, d_frames, stream);
+}
+
+// the same kernels for clips of any number of windows (the phased stream bank's row runs); refuses a clip without a window or
+// shorter than its windows need
+hipError_t launch_fft_bands_windows(const Plan& plan, const void* d_pcm, uint32_t fmt, uint64_t n_clips, uint64_t samples_per_clip,
+                                    uint32_t windows_per_clip, float* d_frames, hipStream_t stream) {
+    if (windows_per_clip == 0 || samples_per_clip < (uint64_t)plan.window + (uint64_t)(windows_per_clip - 1) * plan.stride) return hipErrorInvalidValue;
+    return launch_windows(plan, d_pcm, fmt, n_clips, samples_per_clip, windows_per_clip, d_frames, stream);
 }
 
 }  // namespace lbad

@@ -86,12 +86,21 @@ __device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t x) {
     return x;
 }
 
+// LBAD_STAGE2_HOP (k_haar_select_hop.hip compiles this file a second time with it): the same kernel under another name with
+// frames at a row hop, as in k_haar_select32.hip.  The instances of this file are not touched.
+#ifdef LBAD_STAGE2_HOP
+#define LBAD_STAGE2_KERNEL haar_select_hop_kernel
+#define LBAD_STAGE2_HOP_PARAM , const StageHop hop
+#else
+#define LBAD_STAGE2_KERNEL haar_select_kernel
+#define LBAD_STAGE2_HOP_PARAM
+#endif
 // PER = coefficients per thread (128 x bands / 256, rounded up to 8 / 16 / 32): the select works on registers
 template <int PER>
-__global__ __launch_bounds__(kThreads) void haar_select_kernel(const float* __restrict__ frames, uint32_t bands,
+__global__ __launch_bounds__(kThreads) void LBAD_STAGE2_KERNEL(const float* __restrict__ frames, uint32_t bands,
                                                                float root_bands, uint32_t keep, uint32_t subfp_len,
                                                                uint32_t* __restrict__ packed,
-                                                               float* __restrict__ haar_out) {
+                                                               float* __restrict__ haar_out LBAD_STAGE2_HOP_PARAM) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const uint32_t n = kRowsPerFrame * bands;
     float* a = smem;                   // the frame, then the finished coefficients
@@ -105,8 +114,19 @@ __global__ __launch_bounds__(kThreads) void haar_select_kernel(const float* __re
 
     const int t = threadIdx.x;
     const uint64_t frame = blockIdx.x;
+#ifdef LBAD_STAGE2_HOP
+    // the frame's two row runs (internal.hpp: StageHop); a slot at or behind its phase's count is zero (workgroup-uniform:
+    // nobody waits at a barrier)
+    const HopSource hop_src = hop_source(hop, blockIdx.x);
+    if (hop_src.empty) {
+        if (t < (int)kPackedWords) packed[frame * kPackedWords + t] = 0u;
+        return;
+    }
+    for (uint32_t i = t; i < n; i += kThreads) a[i] = hop_row(frames, hop.tail, hop_src, i / bands, bands)[i % bands];
+#else
     const float* src = frames + frame * n;
     for (uint32_t i = t; i < n; i += kThreads) a[i] = src[i];
+#endif
     if (t < (int)kPackedWords) s_bits[t] = 0;
     if (t < (int)kCand) {
         s_rank[t] = 0;
@@ -284,8 +304,18 @@ __global__ __launch_bounds__(kThreads) void haar_select_kernel(const float* __re
 
 }  // namespace
 
+#ifdef LBAD_STAGE2_HOP
+#define LBAD_STAGE2_HOP_ARG , hop
+hipError_t launch_haar_select_hop(const Plan& plan, const float* d_frames, const StageHop& hop, uint64_t n_clips, uint32_t* d_packed,
+                                  hipStream_t stream) {
+    if (!stage_hop_valid(hop)) return hipErrorInvalidValue;
+    const uint64_t n_frames = stage_hop_frames(hop, n_clips);
+    float* const d_haar_out = nullptr;
+#else
+#define LBAD_STAGE2_HOP_ARG
 hipError_t launch_haar_select(const Plan& plan, float* d_frames, uint64_t n_frames, uint32_t* d_packed,
                               float* d_haar_out, hipStream_t stream) {
+#endif
     if (n_frames == 0) return hipSuccess;
     if (n_frames > 0x7fffffffull) return hipErrorInvalidValue;
     size_t lds = (size_t)(5 * kRowsPerFrame * plan.bands / 2) * sizeof(float);            // frame, row-pass result, running sums
@@ -299,12 +329,12 @@ hipError_t launch_haar_select(const Plan& plan, float* d_frames, uint64_t n_fram
             if (e != hipSuccess) return e;
         }
         hipLaunchKernelGGL(kern, dim3((uint32_t)n_frames), dim3(kThreads), lds, stream, d_frames, plan.bands,
-                           std::sqrt((float)plan.bands), plan.keep, plan.subfp_len, d_packed, d_haar_out);
+                           std::sqrt((float)plan.bands), plan.keep, plan.subfp_len, d_packed, d_haar_out LBAD_STAGE2_HOP_ARG);
         return hipGetLastError();
     };
-    if (per <= 8) return launch(haar_select_kernel<8>);
-    if (per <= 16) return launch(haar_select_kernel<16>);
-    return launch(haar_select_kernel<32>);
+    if (per <= 8) return launch(LBAD_STAGE2_KERNEL<8>);
+    if (per <= 16) return launch(LBAD_STAGE2_KERNEL<16>);
+    return launch(LBAD_STAGE2_KERNEL<32>);
 }
 
 }  // namespace lbad

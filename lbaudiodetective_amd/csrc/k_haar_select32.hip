@@ -422,10 +422,22 @@ typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f3u __attribute__((ext_vector_type(3), aligned(4)));
 typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
 
+// LBAD_STAGE2_HOP (k_haar_select32_hop.hip compiles this file a second time with it): the same kernel under another name
+// with frames at a row hop -- workgroup (clip, phase, j) reads the 128 rows from row phase * hop + 128 j of its clip's row
+// run (StageHop, internal.hpp) and writes slot [clip][phase][j] of `packed`.  The instances of this file are not touched.
+#ifdef LBAD_STAGE2_HOP
+#define LBAD_STAGE2_KERNEL haar_select32_hop_kernel
+#define LBAD_STAGE2_HOP_PARAM , const StageHop hop
+#define LBAD_FRAME_ROW(row_dw, row) hop_row(frames, hop.tail, hop_src, (uint32_t)(row), (uint32_t)(row_dw))
+#else
+#define LBAD_STAGE2_KERNEL haar_select32_kernel
+#define LBAD_STAGE2_HOP_PARAM
+#define LBAD_FRAME_ROW(row_dw, row) frames + frame * (kRowsPerFrame * row_dw) + (row) * row_dw
+#endif
 template <int COLS, bool SPARSE, uint32_t RMASK = 0u, bool HAS_LEFT = false>
-__global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 6 : 7) void haar_select32_kernel(const float* __restrict__ frames, uint32_t keep,
+__global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 6 : 7) void LBAD_STAGE2_KERNEL(const float* __restrict__ frames, uint32_t keep,
                                                                           uint32_t subfp_len, uint32_t* __restrict__ packed,
-                                                                          float* __restrict__ haar_out, const SparseArgs sp) {
+                                                                          float* __restrict__ haar_out, const SparseArgs sp LBAD_STAGE2_HOP_PARAM) {
     static_assert(!SPARSE || COLS == 32, "the sparse form is for 32 bands");
     constexpr int kCols = COLS;
     constexpr int kThreads = SPARSE ? 192 : COLS * 8;
@@ -448,6 +460,15 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
 
     const int t = threadIdx.x;
     const uint64_t frame = blockIdx.x;
+#ifdef LBAD_STAGE2_HOP
+    // the frame's two row runs (internal.hpp: StageHop); a slot at or behind its phase's count is zero (workgroup-uniform:
+    // nobody waits at a barrier)
+    const HopSource hop_src = hop_source(hop, blockIdx.x);
+    if (hop_src.empty) {
+        if (threadIdx.x < kPackedWords) packed[frame * kPackedWords + threadIdx.x] = 0u;
+        return;
+    }
+#endif
     const float root2 = __fsqrt_rn(2.0f);
 #ifdef LBAD_EXP_TIMELINE
     long long ts[8];
@@ -469,7 +490,7 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
         if constexpr (SPARSE && RMASK != 0u) {
             constexpr int kRight = __builtin_popcount(RMASK), kRow = kRight + (HAS_LEFT ? 1 : 0);
             const bool mine = t < (int)kRowsPerFrame;
-            const float* rowp = frames + frame * (kRowsPerFrame * kRow) + (mine ? t : 0) * kRow;
+            const float* rowp = LBAD_FRAME_ROW(kRow, mine ? t : 0);
             float got[kRow + 3];
 #pragma unroll
             for (int q = 0; q + 4 <= kRow; q += 4) {
@@ -492,7 +513,7 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
             left_value = HAS_LEFT ? got[kRight] : 0.0f;
         } else if constexpr (SPARSE) {
             const bool mine = t < (int)kRowsPerFrame;
-            const float* rowp = frames + frame * (kRowsPerFrame * sp.row_dw) + (mine ? t : 0) * sp.row_dw;
+            const float* rowp = LBAD_FRAME_ROW(sp.row_dw, mine ? t : 0);
             // branch-free: an empty band reads the row's first float and drops it (sixteen loads in flight together)
             float got[16];
 #pragma unroll
@@ -508,7 +529,7 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
             }
             left_value = sp.left < 32u ? got_left : 0.0f;
         } else {
-            const float4* src = reinterpret_cast<const float4*>(frames + frame * (kRowsPerFrame * kCols) + (t / H) * kCols + 16 * (t % H));
+            const float4* src = reinterpret_cast<const float4*>(LBAD_FRAME_ROW(kCols, t / H) + 16 * (t % H));
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float4 v = src[q];
@@ -1038,12 +1059,22 @@ __global__ __launch_bounds__(SPARSE ? 192 : COLS * 8, SPARSE ? 8 : COLS == 64 ? 
 
 }  // namespace
 
+#ifdef LBAD_STAGE2_HOP
+#define LBAD_STAGE2_HOP_ARG , hop
+hipError_t launch_haar_select32_hop(const Plan& plan, const float* d_frames, const StageHop& hop, uint64_t n_clips, uint32_t* d_packed,
+                                    hipStream_t stream, bool compact) {
+    if (!stage_hop_valid(hop)) return hipErrorInvalidValue;
+    const uint64_t n_frames = stage_hop_frames(hop, n_clips);
+    float* const d_haar_out = nullptr;
+#else
+#define LBAD_STAGE2_HOP_ARG
 bool haar_select32_supported(const Plan& p) {
     return (p.bands == 16 || p.bands == 32 || p.bands == 64) && p.keep <= kCand && p.keep >= 1;
 }
 
 hipError_t launch_haar_select32(const Plan& plan, const float* d_frames, uint64_t n_frames, uint32_t* d_packed,
                                 float* d_haar_out, hipStream_t stream, bool compact) {
+#endif
     if (n_frames == 0) return hipSuccess;
     if (n_frames > 0x7fffffffull) return hipErrorInvalidValue;
     SparseArgs sp = {};
@@ -1065,22 +1096,27 @@ hipError_t launch_haar_select32(const Plan& plan, const float* d_frames, uint64_
         for (uint32_t j = 0; j < 16; ++j)
             if (plan.sparse.pos_right[j] != 0xFF) rmask |= 1u << j;
         if (rmask == kRmask44k && plan.sparse.left < 32)
-            hipLaunchKernelGGL((haar_select32_kernel<32, true, kRmask44k, true>), dim3((uint32_t)n_frames), dim3(192), 0, stream, d_frames,
-                               plan.keep, plan.subfp_len, d_packed, d_haar_out, sp);
+            hipLaunchKernelGGL((LBAD_STAGE2_KERNEL<32, true, kRmask44k, true>), dim3((uint32_t)n_frames), dim3(192), 0, stream, d_frames,
+                               plan.keep, plan.subfp_len, d_packed, d_haar_out, sp LBAD_STAGE2_HOP_ARG);
+#ifdef LBAD_STAGE2_HOP
+        else                     // the hop form has no instance with run-time band positions: no call has compact rows of another plan
+            return hipErrorInvalidValue;
+#else
         else
-            hipLaunchKernelGGL((haar_select32_kernel<32, true>), dim3((uint32_t)n_frames), dim3(192), 0, stream, d_frames, plan.keep,
-                               plan.subfp_len, d_packed, d_haar_out, sp);
+            hipLaunchKernelGGL((LBAD_STAGE2_KERNEL<32, true>), dim3((uint32_t)n_frames), dim3(192), 0, stream, d_frames, plan.keep,
+                               plan.subfp_len, d_packed, d_haar_out, sp LBAD_STAGE2_HOP_ARG);
+#endif
         return hipGetLastError();
     }
     if (plan.bands == 16)
-        hipLaunchKernelGGL((haar_select32_kernel<16, false>), dim3((uint32_t)n_frames), dim3(128), 0, stream, d_frames, plan.keep,
-                           plan.subfp_len, d_packed, d_haar_out, sp);
+        hipLaunchKernelGGL((LBAD_STAGE2_KERNEL<16, false>), dim3((uint32_t)n_frames), dim3(128), 0, stream, d_frames, plan.keep,
+                           plan.subfp_len, d_packed, d_haar_out, sp LBAD_STAGE2_HOP_ARG);
     else if (plan.bands == 64)
-        hipLaunchKernelGGL((haar_select32_kernel<64, false>), dim3((uint32_t)n_frames), dim3(512), 0, stream, d_frames, plan.keep,
-                           plan.subfp_len, d_packed, d_haar_out, sp);
+        hipLaunchKernelGGL((LBAD_STAGE2_KERNEL<64, false>), dim3((uint32_t)n_frames), dim3(512), 0, stream, d_frames, plan.keep,
+                           plan.subfp_len, d_packed, d_haar_out, sp LBAD_STAGE2_HOP_ARG);
     else
-        hipLaunchKernelGGL((haar_select32_kernel<32, false>), dim3((uint32_t)n_frames), dim3(256), 0, stream, d_frames, plan.keep,
-                           plan.subfp_len, d_packed, d_haar_out, sp);
+        hipLaunchKernelGGL((LBAD_STAGE2_KERNEL<32, false>), dim3((uint32_t)n_frames), dim3(256), 0, stream, d_frames, plan.keep,
+                           plan.subfp_len, d_packed, d_haar_out, sp LBAD_STAGE2_HOP_ARG);
     return hipGetLastError();
 }
 

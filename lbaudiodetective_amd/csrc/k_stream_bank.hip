@@ -157,18 +157,25 @@ hipError_t launch_bank_stage(const BankDev& b, const BankRow* d_rows, uint32_t n
     return hipGetLastError();
 }
 
-hipError_t launch_bank_commit(const BankDev& b, const BankRow* d_rows, uint32_t n_rows, const float* d_fresh, const uint32_t* d_packed,
-                              uint32_t total, void* d_out, hipStream_t stream) {
+hipError_t launch_bank_commit_rows(const BankDev& b, const BankRow* d_rows, uint32_t n_rows, const uint32_t* d_packed, uint32_t total,
+                                   void* d_out, hipStream_t stream) {
+    if (n_rows == 0 || total == 0) return hipSuccess;
+    hipLaunchKernelGGL(bank_commit_rows_kernel, dim3(strided_grid(bank_blocks(2ull * total), kBankMaxGrid)), dim3(kBankThreads), 0,
+                       stream, b, d_rows, n_rows, reinterpret_cast<const uint4*>(d_packed), total, static_cast<uint4*>(d_out));
+    return hipGetLastError();
+}
+
+hipError_t launch_bank_commit_carry(const BankDev& b, const BankRow* d_rows, uint32_t n_rows, const float* d_fresh, hipStream_t stream) {
     if (n_rows == 0) return hipSuccess;
-    if (total) {
-        hipLaunchKernelGGL(bank_commit_rows_kernel, dim3(strided_grid(bank_blocks(2ull * total), kBankMaxGrid)), dim3(kBankThreads), 0,
-                           stream, b, d_rows, n_rows, reinterpret_cast<const uint4*>(d_packed), total, static_cast<uint4*>(d_out));
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
     hipLaunchKernelGGL(bank_commit_carry_kernel, dim3(strided_grid(n_rows, kBankMaxGrid)), dim3(kBankThreads), 0, stream, b, d_rows,
                        n_rows, d_fresh);
     return hipGetLastError();
+}
+
+hipError_t launch_bank_commit(const BankDev& b, const BankRow* d_rows, uint32_t n_rows, const float* d_fresh, const uint32_t* d_packed,
+                              uint32_t total, void* d_out, hipStream_t stream) {
+    const hipError_t e = launch_bank_commit_rows(b, d_rows, n_rows, d_packed, total, d_out, stream);
+    return e != hipSuccess ? e : launch_bank_commit_carry(b, d_rows, n_rows, d_fresh, stream);
 }
 
 hipError_t launch_bank_window(const BankDev& b, const uint2* d_list, uint64_t n_list, uint32_t q, void* d_out, hipStream_t stream) {
